@@ -2,6 +2,7 @@
 """bench.py -- throughput of the fused iterated-Laplacian filter on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--scaling strong|weak] [--no-cpu] [--no-extra]
+                    [--dump-outputs DIR]
 
 A "step" is ONE whole filter application (all n_steps Chebyshev/Laplacian steps) of the workload's field(s),
 inputs already resident in HBM.  metric = grid-cells * Laplacian-steps / second (BASELINE.json).
@@ -279,7 +280,43 @@ def parse():
     ap.add_argument("--multi", type=int, default=0, help="recurrence steps fused per HBM pass (0 = library default, 1 = off)")
     ap.add_argument("--strip", type=int, default=0, help="rows per wave strip of the temporally blocked kernel (0 = auto)")
     ap.add_argument("--prefetch", type=int, default=0, help="operand rows in flight per wave (0 = default)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64, at most 64 MB "
+                         "in all: larger outputs as a fixed, seeded sample of their cells); --gpus 1 only")
     return ap.parse_args()
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+DUMP_SEED = 20240601
+
+
+def dump_outputs(outs, directory):
+    """Write the outputs of the timed path's last step to `directory` as <name>.npy: `filtered` (a scalar field) or `filtered_u` /
+    `filtered_v` (a vector field), in the dtype the caller received.  When they exceed DUMP_LIMIT_BYTES together, every array is
+    replaced by the same share of its cells, picked from the flattened array by a generator with a fixed seed and kept in flat-index
+    order: the same arguments give the same cells, run after run and build after build.  Returns a record for the result line."""
+    import torch
+
+    names = ["filtered"] if len(outs) == 1 else ["filtered_u", "filtered_v"]
+    total = sum(o.numel() * o.element_size() for o in outs)
+    budget = DUMP_LIMIT_BYTES - 1024 * len(outs)          # (room for the .npy headers)
+    frac = 1.0 if total <= budget else budget / total
+    os.makedirs(directory, exist_ok=True)
+    rec = {"dir": directory, "files": {}, "sampled": frac < 1.0, "seed": DUMP_SEED if frac < 1.0 else None}
+    for k, (name, o) in enumerate(zip(names, outs)):
+        if o.dtype not in (torch.float32, torch.float64):
+            raise SystemExit(f"bench.py --dump-outputs: output {name} has dtype {o.dtype}, not float32 / float64")
+        if frac < 1.0:
+            n = o.numel()
+            rng = np.random.default_rng([DUMP_SEED, k])
+            idx = np.unique(rng.integers(0, n, size=int(n * frac)))
+            arr = o.reshape(-1)[torch.from_numpy(idx).to(o.device)].cpu().numpy()
+        else:
+            arr = o.cpu().numpy()
+        path = os.path.join(directory, name + ".npy")
+        np.save(path, arr)
+        rec["files"][name] = {"shape": list(arr.shape), "of_shape": list(o.shape), "dtype": str(arr.dtype)}
+    return rec
 
 
 def main_single(args):
@@ -309,6 +346,8 @@ def main_single(args):
                    "n_steps": r["n_steps"], "global_grid": [args.ny, args.nx], "parallelism": "single GPU"},
     }
     out["roofline"] = roofline_of(args.config, r, args.steps, not tuned)
+    if args.dump_outputs:
+        out["dump_outputs"] = dump_outputs(r["outs"], args.dump_outputs)
     nbatch_main = r["nbatch"]
     failed = []
     # ---- parity of the TIMED workload's output -----------------------------------------------------------------
@@ -437,6 +476,8 @@ def main():
     args = parse()
     if args.nlev <= 0 and args.config == 6:
         args.nlev = 0
+    if args.dump_outputs and (args.gpus > 1 or args.kinds):
+        raise SystemExit("bench.py: --dump-outputs writes the single-GPU workload's outputs (--gpus 1, not --kinds)")
     world = int(os.environ.get("WORLD_SIZE", "0"))
     if world == 0 and args.gpus > 1:
         from bench_multi import self_launch

@@ -112,3 +112,39 @@ def test_kinds_line_has_a_roofline_per_kind():
         rf = k["roofline"]
         assert k["value"] > 0 and rf["kernel"].startswith("gcmf::k_") and 0 < rf["frac"] < 1 and rf["launches_of_it_per_application"] >= 1
         assert k["parity"]["rel_err"] <= 1e-12 and k["parity"]["nan_pattern_equal"] is True
+
+
+def test_dump_outputs_writes_the_timed_result(tmp_path):
+    """`--dump-outputs DIR`: the last timed step's result lands in DIR as .npy, bit for bit what the same filter returns on the GPU in this
+    process, and the same arguments give the same file whatever the number of timed steps -- which `--steps` sets exactly."""
+    import numpy as np
+    import torch
+
+    from gcm_filters_amd import Filter, FilterShape, GridType, testing as T
+
+    shape = (240, 360)
+    dumps = []
+    for steps in (3, 7):
+        d = str(tmp_path / f"s{steps}")
+        r = _run(["--steps", str(steps), "--warmup", "1", "--no-extra", "--no-cpu", "--ny", str(shape[0]), "--nx", str(shape[1]),
+                  "--dump-outputs", d])
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = _json_line(r.stdout)
+        assert line["steps"] == steps and sum(line["timing"]["applications_per_block"]) == steps and line["ms_per_step"] > 0
+        assert line["dump_outputs"]["sampled"] is False and sorted(os.listdir(d)) == ["filtered.npy"]
+        dumps.append(np.load(os.path.join(d, "filtered.npy")))
+    assert dumps[0].dtype == np.float64 and dumps[0].shape == shape
+    assert np.array_equal(dumps[0], dumps[1], equal_nan=True)
+    wl = T.baseline_workload(3, shape)
+    fk = wl["fk"]
+    flt = Filter(grid_type=GridType[wl["grid"]], grid_vars=wl["grid_vars"], filter_scale=fk["filter_scale"], dx_min=fk["dx_min"],
+                 filter_shape=FilterShape[fk["filter_shape"]])
+    want = flt.apply(torch.from_numpy(wl["fields"][0]).to("cuda")).cpu().numpy()
+    assert np.array_equal(dumps[0], want, equal_nan=True)
+
+
+def test_dump_outputs_is_refused_for_several_ranks(tmp_path):
+    d = tmp_path / "dump"
+    r = _run(["--gpus", "2", "--steps", "1", "--dump-outputs", str(d)], {"GCMF_BENCH_SHARE_GPU": "1"})
+    assert r.returncode != 0 and "--dump-outputs" in r.stderr
+    assert not d.exists()

@@ -431,8 +431,6 @@ def test_f32_flux_kinds_backward_evaluation(grid, n_steps, kwargs):
     if nb > 1:
         f = np.stack([f + 0.1 * i for i in range(nb)])
     if "wet_mask" not in gv:       # (round 4: the REGULAR kinds run k_ringc<float> too; no land there, and NaN spreads -- kernels.py:113-121)
-        if kwargs.get("nanland") or kwargs.get("nanwet"):
-            pytest.skip("no land / no nan_to_num on REGULAR")
         land = np.zeros(shape, bool)
     else:
         land = gv["wet_mask"] == 0
@@ -470,7 +468,9 @@ def test_f32_flux_kinds_backward_evaluation(grid, n_steps, kwargs):
         assert np.array_equal(np.isnan(g), np.isnan(want))
         assert np.nanmax(np.abs(g - want)) <= 1e-4 * np.nanmax(np.abs(want))
     assert np.nanmax(np.abs(got - want)) <= 2.5 * np.nanmax(np.abs(fwd - want)) + 2e-6 * np.nanmax(np.abs(want))   # same accuracy class as the reference's scheme
-    if kwargs.get("nanwet"):
+    if kwargs.get("nanwet") and "wet_mask" not in gv:
+        assert np.isnan(got).sum() > nb         # no nan_to_num on the REGULAR kinds: the NaN spreads, as in the oracle
+    elif kwargs.get("nanwet"):
         assert nfb > 0
     elif not (grid.startswith("MOM5") and kwargs.get("nanland")):
         assert nfb == 0

@@ -106,6 +106,8 @@ def test_bit_exact_recurrence(grid, kind, golden_generated):
     backward kernel exists) is held to 1e-13 of the same vectors and to the identical NaN pattern."""
     from gcm_filters_amd.filter import FilterSpec, _create_filter_func
     name = f"{grid}/{kind}"
+    if name not in golden_generated and kind == "gauss/nanland":
+        name = f"{grid}/gauss"      # a grid without land: NaN on its land cells leaves the plain field (make_golden.py stores it once)
     if name not in golden_generated:
         pytest.skip("no such case")
     g, fields, gv, fk = MG.build_case(name)
@@ -137,10 +139,10 @@ def test_config1_regular_512(golden_generated):
 @pytest.mark.parametrize("grid", ["REGULAR", "REGULAR_WITH_LAND", "IRREGULAR_WITH_LAND", "MOM5T", "VECTOR_C_GRID",
                                   "VECTOR_B_GRID", "TRIPOLAR_POP_WITH_LAND", "TRIPOLAR_REGULAR_WITH_LAND_AREA_WEIGHTED"])
 def test_ragged_shapes(grid, shape):
-    if grid.startswith("TRIPOLAR") and shape[1] % 2:
-        pytest.skip("tripolar grids need an even nx (the reference raises for odd nx)")
-    if shape[0] < 3 and grid.startswith("TRIPOLAR"):
-        pytest.skip("degenerate")
+    if grid.startswith("TRIPOLAR"):
+        # the nearest shape a tripole grid allows: an even nx (the reference's fold check fails for odd nx) and a land row plus at least
+        # two rows beneath the seam
+        shape = (max(shape[0], 3), shape[1] + shape[1] % 2)
     vec = grid in T.VECTOR_GRIDS
     if vec:
         fields, gv = T.vector_case(grid, shape)

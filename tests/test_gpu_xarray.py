@@ -2,7 +2,7 @@
 ``xarray.apply_ufunc`` down to libgcmf, nothing monkeypatched but the xarray module itself (xarray is not installed in
 this image: tests/fake_xarray.py models the documented semantics Filter relies on, incl. dask="parallelized" calling
 filter_func concurrently from worker threads, block by block).  Every test also runs against the INSTALLED xarray (dask-backed inputs
-where dask imports) wherever there is one -- skipped here.  Mirrors upstream tests/test_filter.py:172-252."""
+where dask imports) wherever there is one -- not collected where there is none.  Mirrors upstream tests/test_filter.py:172-252."""
 import sys
 
 import numpy as np
@@ -15,9 +15,14 @@ from oracle import gcmf_oracle as O
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(params=XARRAY_KINDS)
+def _xarray_installed():
+    import importlib.util
+    return importlib.util.find_spec("xarray") is not None
+
+
+@pytest.fixture(params=[k for k in XARRAY_KINDS if k != "real" or _xarray_installed()])
 def xr(request, monkeypatch):
-    """The model of xarray (always) and the installed xarray (+ dask-backed inputs) wherever it imports."""
+    """The model of xarray (always) and the installed xarray (+ dask-backed inputs) wherever it imports (collected only there)."""
     return xarray_backend(request.param, monkeypatch)
 
 

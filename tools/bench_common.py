@@ -209,7 +209,7 @@ def load_traffic(cfg, kernel_ran, geometry=None):
 
 def run_single(cfg, args, dev, steps, warmup, scale=0.0, levels=None, tuned=False, evaluation="auto"):
     """Time `steps` filter applications of BASELINE config `cfg` on this process's GPU.  Returns a dict with the raw
-    measurements, the workload and the device outputs of the last application."""
+    measurements, the workload and the device outputs of the last timed application."""
     import torch
 
     from gcm_filters_amd import Filter, FilterShape, GridType, _lib, testing as T
@@ -286,6 +286,7 @@ def run_single(cfg, args, dev, steps, warmup, scale=0.0, levels=None, tuned=Fals
         torch.cuda.synchronize()
         block_s.append(time.perf_counter() - t0)
     elapsed = sum(block_s)
+    timed_outs = outs   # what the last timed application returned (parity checks, bench.py --dump-outputs)
     plan.last_kernel()  # reset
     outs = run()   # (untimed) names the dominant kernel of the plan now in use
     torch.cuda.synchronize()
@@ -303,7 +304,7 @@ def run_single(cfg, args, dev, steps, warmup, scale=0.0, levels=None, tuned=Fals
         dom_ms, dom_n, dom_min, dom_max = dom_ms + ms, dom_n + nl, min(dom_min, lo), max(dom_max, hi)
     plan.set_timing(False)
     return dict(dom_ms=dom_ms, dom_n=dom_n, dom_min=dom_min, dom_max=dom_max, dom_reps=dom_reps, wl=wl, grid=grid, fk=fk, itemsize=itemsize, nbatch=nbatch, n_steps=n_steps, elapsed=elapsed,
-                kernel_ms=kernel_ms, launches=launches, outs=list(outs), kernel=plan.last_kernel(), geometry=plan.last_kernel_geometry(),
+                kernel_ms=kernel_ms, launches=launches, outs=list(timed_outs), kernel=plan.last_kernel(), geometry=plan.last_kernel_geometry(),
                 flt=flt, d_in=d_in, cells=args.ny * args.nx * nbatch, block_s=block_s, per_block=per_block, replans=replans)
 
 
