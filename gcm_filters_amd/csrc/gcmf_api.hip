@@ -138,19 +138,18 @@ int advance_multi(gcmf_plan *pl, const MultiArgs &m, hipStream_t s, int *launche
   const int rows = g.rows, S = m.S;
   const bool band = g.fold && m.row_hi == rows;
   int rc;
-  auto blocked = [&](const MultiArgs &a) { return backward ? launch_ringc(pl, a, s) : launch_scalar_multi(pl, a, s); };
+  auto blocked = [&](const MultiArgs &a) -> int {   // (between the dominant kernel's timing events)
+    int r;
+    if ((r = dom_begin(pl, s)) || (r = backward ? launch_ringc(pl, a, s) : launch_scalar_multi(pl, a, s)) || (r = dom_end(pl, s))) return r;
+    if (launches) ++*launches;
+    return GCMF_OK;
+  };
   // Short launches on the seam's plan (round 6): the band AFTER the blocked launch, in its stream, 1024 threads per tile.  Beside a launch
   // that lasts no longer than itself the band is the slower of the two (its waves share the SIMDs with the marching waves) and the fork /
   // join costs ~5 us on top: a 1080 x 1440 tripolar grid took 294 us against 215 us for the same grid without a seam.
   const bool seq = band && pl->band_seq_cells > 0 && (long long)m.nbatch * (m.row_hi - m.row_lo) * g.nx <= pl->band_seq_cells;
   pl->alone_now = !band || seq;
-  if (!band) {
-    if ((rc = dom_begin(pl, s))) return rc;
-    if ((rc = blocked(m))) return rc;
-    if ((rc = dom_end(pl, s))) return rc;
-    if (launches) ++*launches;
-    return GCMF_OK;
-  }
+  if (!band) return blocked(m);
   if (backward && ringc_zip_fold_ok(pl, m)) {   // (round 6) the seam's rows inside the launch: strips that start at the seam, zipped with their mirror windows
     MultiArgs mz = m;
     mz.zip_fold = 1;
@@ -177,12 +176,7 @@ int advance_multi(gcmf_plan *pl, const MultiArgs &m, hipStream_t s, int *launche
   // The seam rows in ONE launch (k_fold_band, gcmf_foldband.hip) on a side stream beside the blocked launch: neither reads what
   // the other writes (the band reads rows >= rows - 2S of the input planes, the two write disjoint rows of the output planes).
   if (seq) {
-    if (mm.row_hi > mm.row_lo) {
-      if ((rc = dom_begin(pl, s))) return rc;
-      if ((rc = blocked(mm))) return rc;
-      if ((rc = dom_end(pl, s))) return rc;
-      if (launches) ++*launches;
-    }
+    if (mm.row_hi > mm.row_lo && (rc = blocked(mm))) return rc;
     if ((rc = launch_fold_band(pl, m, backward, s, true))) return rc;
     if (launches) ++*launches;
     return GCMF_OK;
@@ -201,12 +195,7 @@ int advance_multi(gcmf_plan *pl, const MultiArgs &m, hipStream_t s, int *launche
   if ((rc = launch_fold_band(pl, m, backward, pl->side))) return rc;
   if (launches) ++*launches;
   GCMF_HIP(hipEventRecord(pl->ev_join, pl->side));
-  if (mm.row_hi > mm.row_lo) {
-    if ((rc = dom_begin(pl, s))) return rc;
-    if ((rc = blocked(mm))) return rc;
-    if ((rc = dom_end(pl, s))) return rc;
-    if (launches) ++*launches;
-  }
+  if (mm.row_hi > mm.row_lo && (rc = blocked(mm))) return rc;
   GCMF_HIP(hipStreamWaitEvent(s, pl->ev_join, 0));
   return GCMF_OK;
 }
@@ -217,7 +206,7 @@ int step_dispatch(gcmf_plan *pl, const StepArgs &a, hipStream_t s) {
 
 // p[0..n_steps] on the device for k_land_fix; uploaded only when it changed (a pageable upload stalls the host behind
 // the stream)
-int ensure_dev_p(gcmf_plan *pl, const double *p, int n_steps, hipStream_t s) {
+static int ensure_dev_p(gcmf_plan *pl, const double *p, int n_steps, hipStream_t s) {
   const size_t n = (size_t)n_steps + 1;
   if (pl->dev_p_n < n) {
     if (pl->dev_p) GCMF_HIP(hipFree(pl->dev_p));
@@ -234,6 +223,64 @@ int ensure_dev_p(gcmf_plan *pl, const double *p, int n_steps, hipStream_t s) {
   }
   return GCMF_OK;
 }
+
+// The land-fix tail of a filter whose launches kept the isolated (land) cells out of their state: their own polynomial, from the
+// untouched input `in` into `out` (k_land_fix)
+int land_fix_tail(gcmf_plan *pl, const double *p, int n_steps, double c, const void *in, void *out, bool fb32, int64_t nbatch,
+                  hipStream_t s) {
+  int rc = ensure_dev_p(pl, p, n_steps, s);
+  if (rc) return rc;
+  return launch_land_fix(pl, in, out, pl->dev_p, n_steps, c, fb32 ? 1 : 0, nbatch, s);
+}
+// Stages the raw grid planes on the device (temporaries, unless they are there already), folds them into the plan (precompute), frees
+// the temporaries; scalar plans also get a row of zeros for k_ring.
+static int stage_grid(gcmf_plan *pl, const void *const *planes, int nplanes) {
+  const gcmf_plan_desc &d = pl->d;
+  const size_t plane_bytes = (size_t)d.ny * d.nx * dtype_size(d.dtype);
+  std::vector<const void *> dplanes(nplanes, nullptr);
+  std::vector<void *> staged;
+  int rc = GCMF_OK;
+  for (int k = 0; k < nplanes && rc == GCMF_OK; ++k) {
+    if (d.planes_on_device) {
+      dplanes[k] = planes[k];
+      continue;
+    }
+    int dup = -1;  // the same host array passed twice (e.g. wet_mask_t is wet_mask_q) is uploaded once
+    for (int q = 0; q < k; ++q)
+      if (planes[q] == planes[k]) dup = q;
+    if (dup >= 0) {
+      dplanes[k] = dplanes[dup];
+      continue;
+    }
+    void *p = nullptr;
+    hipError_t e3 = hipMalloc(&p, plane_bytes);
+    if (e3 == hipSuccess) {
+      staged.push_back(p);
+      e3 = hipMemcpyAsync(p, planes[k], plane_bytes, hipMemcpyHostToDevice, pl->stream);
+    }
+    if (e3 != hipSuccess) {
+      set_error("staging grid plane %d failed: %s", k, hipGetErrorString(e3));
+      rc = GCMF_ERR_HIP;
+    }
+    dplanes[k] = p;
+  }
+  if (rc == GCMF_OK) rc = precompute(pl, dplanes.data(), d.planes_on_device ? nullptr : planes);
+  if (rc == GCMF_OK && pl->ncomp == 1) {  // a row of zeros for k_ring
+    void *z = nullptr;
+    const size_t zb = ((size_t)d.nx + 64) * 8 + 256;
+    if (hipMalloc(&z, zb) == hipSuccess && hipMemsetAsync(z, 0, zb, pl->stream) == hipSuccess) {
+      pl->owned.push_back(z);
+      pl->zero_row = z;
+      pl->ring_nfb = reinterpret_cast<unsigned *>((char *)z + zb - 8);  // beyond anything a (padded) row read touches
+    } else if (z) {
+      (void)hipFree(z);
+    }
+  }
+  (void)hipStreamSynchronize(pl->stream);
+  for (void *p : staged) (void)hipFree(p);
+  return rc;
+}
+
 }  // namespace gcmf
 
 using namespace gcmf;
@@ -398,50 +445,7 @@ int gcmf_plan_create(const gcmf_plan_desc *desc, const void *const *planes, int 
   PLAN_HIP(hipEventCreate(&pl->ev1));
   PLAN_HIP(hipEventCreateWithFlags(&pl->ev_busy, hipEventDisableTiming));
 
-  // stage the raw grid planes on the device (temporaries), fold them, free the temporaries
-  const size_t plane_bytes = (size_t)desc->ny * desc->nx * dtype_size(desc->dtype);
-  std::vector<const void *> dplanes(nplanes, nullptr);
-  std::vector<void *> staged;
-  int rc = GCMF_OK;
-  for (int k = 0; k < nplanes && rc == GCMF_OK; ++k) {
-    if (desc->planes_on_device) {
-      dplanes[k] = planes[k];
-      continue;
-    }
-    int dup = -1;  // the same host array passed twice (e.g. wet_mask_t is wet_mask_q) is uploaded once
-    for (int q = 0; q < k; ++q)
-      if (planes[q] == planes[k]) dup = q;
-    if (dup >= 0) {
-      dplanes[k] = dplanes[dup];
-      continue;
-    }
-    void *p = nullptr;
-    hipError_t e3 = hipMalloc(&p, plane_bytes);
-    if (e3 == hipSuccess) {
-      staged.push_back(p);
-      e3 = hipMemcpyAsync(p, planes[k], plane_bytes, hipMemcpyHostToDevice, pl->stream);
-    }
-    if (e3 != hipSuccess) {
-      set_error("staging grid plane %d failed: %s", k, hipGetErrorString(e3));
-      rc = GCMF_ERR_HIP;
-    }
-    dplanes[k] = p;
-  }
-  if (rc == GCMF_OK) rc = precompute(pl, dplanes.data(), desc->planes_on_device ? nullptr : planes);
-  if (rc == GCMF_OK && pl->ncomp == 1) {  // a row of zeros for k_ring
-    void *z = nullptr;
-    const size_t zb = ((size_t)desc->nx + 64) * 8 + 256;
-    if (hipMalloc(&z, zb) == hipSuccess && hipMemsetAsync(z, 0, zb, pl->stream) == hipSuccess) {
-      pl->owned.push_back(z);
-      pl->zero_row = z;
-      pl->ring_nfb = reinterpret_cast<unsigned *>((char *)z + zb - 8);  // beyond anything a (padded) row read touches
-    } else if (z) {
-      (void)hipFree(z);
-    }
-  }
-  (void)hipStreamSynchronize(pl->stream);
-  for (void *p : staged) (void)hipFree(p);
-  if (rc != GCMF_OK) return fail(rc);
+  if (int rc = stage_grid(pl, planes, nplanes)) return fail(rc);
   *out = pl;
   return GCMF_OK;
 #undef PLAN_HIP
@@ -457,50 +461,308 @@ int gcmf_plan_rows(const gcmf_plan *pl, int64_t *rows_alloc, int64_t *first_owne
 
 static const int64_t MAX_LAUNCH_BATCH = 32768;  // batch entries per launch (gridDim.y of the scalar kernels)
 
-// Shared driver of gcmf_apply and gcmf_laplacian; the plan's mutex is held and the device is current.
-// `timed` = false: the caller (the pipelined host path) brackets the launches with the timing events itself.
-static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double c, const void *const *in,
-                            void *const *out, int64_t nbatch, uint32_t flags, void *stream, bool lapl_only,
-                            bool timed) {
-  const bool on_dev = flags & GCMF_DEVICE_PTRS;
-  // device pointers: run on exactly the caller's stream (NULL = the HIP default stream) so the work is
-  // ordered with the caller's own kernels; host pointers: the plan's private stream unless one is given
-  hipStream_t s = (on_dev || stream) ? (hipStream_t)stream : pl->stream;
-  const bool f32 = pl->d.dtype == GCMF_F32;
-  const bool fb32 = f32 && (flags & GCMF_OUT_F32);
-  const size_t ts = dtype_size(pl->d.dtype);
-  const size_t fbs = lapl_only ? ts : ((f32 && !fb32) ? 8 : ts);  // element size of fbar == element size of `out`
-  const size_t ncell = (size_t)nbatch * pl->d.ny * pl->d.nx;
-  const int nc = pl->ncomp;
-  const bool prep = pl->area_weighted && !lapl_only;
+// What the evaluation schedules of one gcmf_apply / gcmf_laplacian call share: the stream, the caller's fields (on the device), the work
+// planes of every component (F2: the second fbar plane of the scalar blocked schedule), the polynomial and the launch count.
+struct ApplyCtx {
+  gcmf_plan *pl;
+  hipStream_t s;
+  const void *din[2];
+  void *dout[2], *A[2], *B[2], *Cb[2], *Db[2], *F[2], *F2, *Pp[2];
+  const double *p;
+  int n_steps, rows, launches;
+  double c;
+  int64_t nbatch;
+  bool fb32;
+};
 
-  // work layout per component: [A][B][fbar] (+ [prepared T0]) (+ host staging: [in][out])
-  const size_t szT = align_up(ncell * ts, 256), szF = align_up(ncell * fbs, 256);
-  const bool use_multi = !lapl_only && pl->multi_s >= 2 && n_steps >= 2 && multi_supported(pl, 2);
-  const bool use_vmulti = !lapl_only && pl->multi_s >= 2 && n_steps >= 2 && vec_multi_supported(pl, nbatch, 2);
-  size_t per = 0;
-  const size_t oA = per; per += szT;
-  const size_t oB = per; per += szT;
-  const size_t oC = per; if (use_multi || use_vmulti) per += szT;
-  const size_t oD = per; if (use_multi || use_vmulti) per += szT;
-  const size_t oF = per; per += szF;
-  // second fbar plane (scalar blocked schedule): k_ring re-does a strip from its inputs when it meets a NaN / inf,
-  // so a launch must not accumulate fbar in place
-  const size_t oF2 = per; if (use_multi) per += szF;
-  // flux kinds only: the land-mask kernels have a NaN-only mode that already makes NaN on land free, there the two
-  // extra passes would only cost (measured -6 %)
-  const bool zero_land = use_multi && land_ok(pl, n_steps);  // n_steps < 4096: k_land_fix keeps p in LDS
-  const size_t oP = per; if (prep) per += szT;
-  const size_t oIn = per; if (!on_dev) per += szT;
-  const size_t oOut = per; if (!on_dev) per += szF;
-  int rc = ensure_work(pl, per * nc);
-  if (rc) return rc;
-  // the plan's work buffers are shared by all calls: a call enqueued on another stream (dask worker threads with
-  // their own streams) must not start before the previous one has finished with them
-  // (the wait is needed only when this call is on ANOTHER stream than the last one: a stream orders its own work.  The event is
-  // recorded lazily, here, on the previous call's stream -- behind everything that stream was given since, which is later
-  // than necessary but correct -- so back-to-back calls on one stream pay for no event at all: two queue packets less per
-  // application, ~8 us of a 512x512 filter)
+static int lapl_step(ApplyCtx &x) {
+  StepArgs a{};
+  for (int k = 0; k < x.pl->ncomp; ++k) { a.t1[k] = x.din[k]; a.t0[k] = x.dout[k]; a.fb_out[k] = nullptr; }
+  a.mode = STEP_LAPL; a.nbatch = x.nbatch; a.row_lo = 0; a.row_hi = x.rows;
+  const int rc = step_dispatch(x.pl, a, x.s);
+  if (!rc) ++x.launches;
+  return rc;
+}
+
+// Small fields: the whole polynomial on the chip in ONE launch (64 levels at a time; gcmf_resident.hip) -- the field, both states
+// and the coefficients live in registers / LDS, nothing but the result goes back to memory.  Same bits as the strip-marching launches.
+static int sched_resident(ApplyCtx &x) {
+  gcmf_plan *pl = x.pl;
+  pl->res_lo = pl->res_hi = 0;   // (launch_resident notes the serial numbers of this application's launches)
+  void *pool[4] = {x.A[0], x.B[0], x.Cb[0], x.Db[0]};
+  const void *u = nullptr, *v = nullptr;
+  double pk[64];
+  int rc;
+  for (int lvl = 1; lvl <= x.n_steps;) {
+    const int L = std::min(64, x.n_steps - lvl + 1);
+    void *fr[2];
+    free_planes(pool, 1, u, v, fr);
+    MultiArgs m = backward_args(x.p, x.n_steps, x.c, lvl, L, u, v, fr, x.din[0], x.dout[0], pk);
+    m.fb_is_f32 = x.fb32; m.nbatch = 1; m.row_lo = 0; m.row_hi = x.rows;
+    if ((rc = dom_begin(pl, x.s))) return rc;
+    if ((rc = launch_resident(pl, m, pk, L, x.s))) return rc;
+    if ((rc = dom_end(pl, x.s))) return rc;
+    ++x.launches;
+    u = fr[0]; v = fr[1];
+    lvl += L;
+  }
+  return GCMF_OK;
+}
+
+// OPT-IN ("single_launch"): the whole polynomial in ONE persistent launch (gcmf_ringc_one.hip).  false: it did not run (the process
+// may not run persistent kernels now), the caller runs the back-to-back launches of sched_backward_scalar instead (same bits).
+static bool sched_single_launch(ApplyCtx &x) {
+  gcmf_plan *pl = x.pl;
+  void *pool[4] = {x.A[0], x.B[0], x.Cb[0], x.Db[0]};
+  if (dom_begin(pl, x.s)) return false;
+  const int r1 = launch_ringc_one(pl, ringc_one_depth(pl, x.n_steps, x.nbatch), x.p, x.n_steps, x.c, x.din[0], x.dout[0], pool, x.s);
+  if (dom_end(pl, x.s)) return false;
+  if (r1 == GCMF_OK) ++x.launches;
+  return r1 == GCMF_OK;
+}
+
+// Backward (Clenshaw) evaluation, gcmf_ringc_impl.hpp: state (b_{k+1}, b_{k+2}) in a pool of four planes, the constant input read by
+// every launch, no fbar planes.  The first launch forms b_n = p[n] f as it loads f; level l = 1..n uses p[n - l]; the last launch
+// writes the result.  depths: clenshaw_cut's launches.
+static int sched_backward_scalar(ApplyCtx &x, const int *depths, int n_clen) {
+  void *pool[4] = {x.A[0], x.B[0], x.Cb[0], x.Db[0]};
+  const void *u = nullptr, *v = nullptr;
+  int rc;
+  for (int q = 0, lvl = 1; q < n_clen; lvl += depths[q++]) {
+    void *fr[2];
+    free_planes(pool, 1, u, v, fr);
+    MultiArgs m = backward_args(x.p, x.n_steps, x.c, lvl, depths[q], u, v, fr, x.din[0], x.dout[0]);
+    m.fb_is_f32 = x.fb32; m.nbatch = x.nbatch; m.row_lo = 0; m.row_hi = x.rows;
+    if ((rc = advance_multi(x.pl, m, x.s, &x.launches, true))) return rc;   // (+ the tripole band on tripolar plans)
+    u = fr[0]; v = fr[1];
+  }
+  return GCMF_OK;
+}
+
+// Temporally blocked schedule (scalar kinds): each launch advances S steps and reads/writes every plane once.  prepare/finalize are
+// fused into the first / last launch.  State buffers rotate through a pool of four because a launch may not overwrite the planes its
+// neighbours' halos are still reading.
+static int sched_forward_scalar(ApplyCtx &x) {
+  gcmf_plan *pl = x.pl;
+  const double *p = x.p;
+  const int n_steps = x.n_steps;
+  // flux kinds only: the land-mask kernels have a NaN-only mode that already makes NaN on land free, there the two extra passes
+  // would only cost
+  const bool zero_land = land_ok(pl, n_steps);  // n_steps < 4096: k_land_fix keeps p in LDS
+  void *pool[4] = {x.A[0], x.B[0], x.Cb[0], x.Db[0]};
+  void *Fcur = x.F[0], *Fnext = x.F2;   // fbar ping-pongs between two planes (see oF2)
+  const void *u = x.din[0], *v = nullptr;
+  bool land_zeroed = false;  // the first blocked launch kept the isolated cells out of the state
+  int rc;
+  for (int k = 1; k <= n_steps;) {
+    const int S = deepest_depth(n_steps - k + 1, std::min(8, pl->multi_s), [&](int d) { return multi_supported(pl, d); });
+    void *fr[2];
+    free_planes(pool, 1, u, v, fr);
+    const bool is_last = (k + S - 1 == n_steps);
+    if (S >= 2) {
+      MultiArgs m{};
+      m.u0 = u; m.v0 = v; m.uo = fr[0]; m.vo = fr[1];
+      m.fb_in = Fcur; m.fb_out = is_last ? x.dout[0] : Fnext;
+      std::swap(Fcur, Fnext);
+      m.first = (k == 1); m.last = is_last; m.S = S; m.fb_is_f32 = x.fb32;
+      m.land_zero = land_zeroed ? 1 : 0;
+      // the first launch may drop land on load if k_land_fix restores it at the end (not for a one-launch filter)
+      m.ring_first = (k == 1 && !is_last && (zero_land || pl->n_land == 0)) ? 1 : 0;
+      for (int t = 0; t < S; ++t) m.pk[t] = p[k + t];
+      m.p0 = p[0]; m.c = x.c; m.nbatch = x.nbatch; m.row_lo = 0; m.row_hi = x.rows;
+      if ((rc = advance_multi(pl, m, x.s, &x.launches))) return rc;
+      u = fr[0]; v = fr[1];
+      if (k == 1 && zero_land && !is_last) {  // keep the isolated cells out of the state from here on
+        if (!ring_supported(pl, m)) {
+          if ((rc = launch_zero_land(pl, fr[0], fr[1], x.nbatch, x.s))) return rc;
+        }   // (k_ring's first launch and k_fold_band took the land as zero while they loaded the field)
+        land_zeroed = true;
+      }
+    } else {
+      StepArgs a1{};
+      a1.mode = (k == 1 ? GCMF_STEP_FIRST : 0u) | (is_last ? GCMF_STEP_LAST : 0u);
+      a1.coef0 = (k == 1) ? p[0] : p[k]; a1.coef1 = p[1]; a1.c = x.c; a1.fb_is_f32 = x.fb32; a1.nbatch = x.nbatch;
+      a1.row_lo = 0; a1.row_hi = x.rows;
+      const void *src = u;
+      if (k == 1 && pl->area_weighted) {  // the single-step kernel wants T_0 = field*area materialised
+        if ((rc = launch_prepare(pl, x.din, x.Pp, x.nbatch, 0, x.rows, x.s))) return rc;
+        ++x.launches;
+        src = x.Pp[0];
+      }
+      a1.t1[0] = src; a1.t2[0] = v; a1.t0[0] = fr[0]; a1.fb_in[0] = Fcur; a1.fb_out[0] = is_last ? x.dout[0] : Fcur;
+      if ((rc = step_dispatch(pl, a1, x.s))) return rc;
+      ++x.launches;
+      v = src; u = fr[0];
+    }
+    k += S;
+  }
+  if (land_zeroed)  // the isolated cells' own polynomial, from the caller's untouched input
+    return land_fix_tail(pl, p, n_steps, x.c, x.din[0], x.dout[0], x.fb32, x.nbatch, x.s);
+  return GCMF_OK;
+}
+
+// C-grid (B-grid with GCMF_CLENSHAW=2: it is bit-exact with numpy forward, so backward is an option there like for the land-mask kinds):
+// the polynomial evaluated backwards (k_cgrid_stream2c / k_bgrid_stream2c): state (b_{k+1}, b_{k+2}) in a pool of four plane pairs, the
+// constant input (u, v) read by every launch, no fbar planes.  Level l = 1..n uses p[n - l]; the first launch forms b_n = p[n] f as it
+// loads f, the last one writes the result.  Four levels per launch keep two operand rows in flight, five spill (DESIGN_HISTORY.md,
+// round 6); deeper launches exist only in k_cgrid_ring (gcmf_cgrid_ring.hip), whose 16-byte accesses need the caller's planes aligned.
+static int sched_backward_vec(ApplyCtx &x) {
+  gcmf_plan *pl = x.pl;
+  void *pool[8] = {x.A[0], x.A[1], x.B[0], x.B[1], x.Cb[0], x.Cb[1], x.Db[0], x.Db[1]};
+  const void *u[2] = {x.din[0], x.din[1]}, *v[2] = {nullptr, nullptr};
+  const bool al16 = ptr_al16(x.din[0]) && ptr_al16(x.din[1]) && ptr_al16(x.dout[0]) && ptr_al16(x.dout[1]);
+  const int ring_smax = cgrid_ring_smax(pl, x.nbatch);
+  const int smax = std::min(pl->multi_s, std::max(4, al16 ? ring_smax : std::min(5, ring_smax)));
+  int rc;
+  for (int lvl = 1; lvl <= x.n_steps;) {
+    const int S = vec_backward_next_depth(pl, x.nbatch, x.n_steps - lvl + 1, smax);
+    void *fr[4];
+    free_planes(pool, 2, u[0], v[0], fr);
+    VecMultiArgs m = backward_args_vec(x.p, x.n_steps, x.c, lvl, S, u, v, fr, x.din, x.dout);
+    m.fb_is_f32 = x.fb32; m.nbatch = x.nbatch; m.row_lo = 0; m.row_hi = x.rows;
+    if ((rc = dom_begin(pl, x.s))) return rc;
+    if ((rc = launch_vec_multi(pl, m, x.s))) return rc;
+    if ((rc = dom_end(pl, x.s))) return rc;
+    for (int q = 0; q < 2; ++q) { u[q] = fr[2 + q]; v[q] = fr[q]; }
+    lvl += S;
+    ++x.launches;
+  }
+  return GCMF_OK;
+}
+
+// vector kinds: S = 2..6 steps per pass, (T_{k-1}, T_{k-2}) -> (T_{k+S-2}, T_{k+S-1}).  Neither output may overwrite T_{k-2}: the halo
+// rows / columns a strip recomputes need its neighbours' T_{k-2}.  The state rotates through four buffers.  A lone last step runs the
+// single-step kernel.
+static int sched_forward_vec(ApplyCtx &x) {
+  gcmf_plan *pl = x.pl;
+  const double *p = x.p;
+  const int n_steps = x.n_steps;
+  void *pool[8] = {x.A[0], x.A[1], x.B[0], x.B[1], x.Cb[0], x.Cb[1], x.Db[0], x.Db[1]};
+  const void *u[2] = {x.din[0], x.din[1]}, *v[2] = {nullptr, nullptr};
+  int rc;
+  for (int k = 1; k <= n_steps;) {
+    const int left = n_steps - k + 1;
+    void *fr[4];
+    free_planes(pool, 2, u[0], v[0], fr);
+    int S = deepest_depth(left, std::min(6, pl->multi_s), [&](int d) { return vec_multi_supported(pl, x.nbatch, d); });
+    if (S == 1 && left >= 2) S = 2;
+    if (S >= 2) {
+      const bool is_last = (k + S - 1 == n_steps);
+      VecMultiArgs m{};
+      for (int q = 0; q < 2; ++q) {
+        m.u0[q] = u[q]; m.uprev[q] = v[q]; m.u1o[q] = fr[q]; m.u2o[q] = fr[2 + q];
+        m.fb_in[q] = x.F[q]; m.fb_out[q] = is_last ? x.dout[q] : x.F[q];
+      }
+      for (int t = 0; t < S; ++t) m.pk[t] = p[k + t];
+      m.p0 = p[0]; m.c = x.c; m.S = S;
+      m.first = (k == 1); m.last = is_last; m.fb_is_f32 = x.fb32; m.nbatch = x.nbatch; m.row_lo = 0; m.row_hi = x.rows;
+      if ((rc = dom_begin(pl, x.s))) return rc;
+      if ((rc = launch_vec_multi(pl, m, x.s))) return rc;
+      if ((rc = dom_end(pl, x.s))) return rc;
+      for (int q = 0; q < 2; ++q) { u[q] = fr[2 + q]; v[q] = fr[q]; }
+      k += S;
+    } else {
+      StepArgs a1{};
+      a1.mode = (k == 1 ? GCMF_STEP_FIRST : 0u) | GCMF_STEP_LAST;
+      a1.coef0 = (k == 1) ? p[0] : p[k]; a1.coef1 = p[1]; a1.c = x.c; a1.fb_is_f32 = x.fb32; a1.nbatch = x.nbatch;
+      a1.row_lo = 0; a1.row_hi = x.rows;
+      for (int q = 0; q < 2; ++q) {
+        a1.t1[q] = u[q]; a1.t2[q] = v[q]; a1.t0[q] = fr[q]; a1.fb_in[q] = x.F[q]; a1.fb_out[q] = x.dout[q];
+      }
+      if ((rc = step_dispatch(pl, a1, x.s))) return rc;
+      k += 1;
+    }
+    ++x.launches;
+  }
+  return GCMF_OK;
+}
+
+// One launch per step.  Step k reads T_{k-1} (stencil) and T_{k-2} (centre) and overwrites T_{k-2}'s buffer with T_k:
+//   k=1: X0 -> A      k=2: (A, X0) -> B      k=3: (B, A) -> A      k=4: (A, B) -> B ...
+static int sched_single_steps(ApplyCtx &x) {
+  gcmf_plan *pl = x.pl;
+  const double *p = x.p;
+  const int n_steps = x.n_steps, nc = pl->ncomp;
+  const void *x0[2] = {x.din[0], x.din[1]};
+  int rc;
+  if (pl->area_weighted) {  // T_0 = field * area
+    if ((rc = launch_prepare(pl, x.din, x.Pp, x.nbatch, 0, x.rows, x.s))) return rc;
+    ++x.launches;
+    for (int k = 0; k < nc; ++k) x0[k] = x.Pp[k];
+  }
+  for (int k = 1; k <= n_steps; ++k) {
+    StepArgs a{};
+    a.mode = (k == 1 ? GCMF_STEP_FIRST : 0u) | (k == n_steps ? GCMF_STEP_LAST : 0u);
+    a.coef0 = (k == 1) ? p[0] : p[k]; a.coef1 = p[1]; a.c = x.c; a.fb_is_f32 = x.fb32; a.nbatch = x.nbatch;
+    a.row_lo = 0; a.row_hi = x.rows;
+    for (int q = 0; q < nc; ++q) {
+      if (k == 1) { a.t1[q] = x0[q]; a.t2[q] = nullptr; a.t0[q] = x.A[q]; }
+      else if (k == 2) { a.t1[q] = x.A[q]; a.t2[q] = x0[q]; a.t0[q] = x.B[q]; }
+      else if (k % 2) { a.t1[q] = x.B[q]; a.t2[q] = x.A[q]; a.t0[q] = x.A[q]; }
+      else { a.t1[q] = x.A[q]; a.t2[q] = x.B[q]; a.t0[q] = x.B[q]; }
+      a.fb_in[q] = x.F[q];
+      a.fb_out[q] = (k == n_steps) ? x.dout[q] : x.F[q];
+    }
+    if ((rc = step_dispatch(pl, a, x.s))) return rc;
+    ++x.launches;
+  }
+  return GCMF_OK;
+}
+
+// The filter's schedule: the first of these that applies runs.  use_multi / use_vmulti: the scalar / vector blocked launches are on
+// offer (the work layout has their planes).
+static int run_schedule(ApplyCtx &x, uint32_t flags, bool use_multi, bool use_vmulti) {
+  gcmf_plan *pl = x.pl;
+  int depths[1024];
+  const bool fwd_only = flags & GCMF_FORWARD_RECURRENCE;   // the caller wants the reference's forward recurrence / accumulation
+  const bool back_f32 = pl->clenshaw_f32 || (flags & GCMF_BACKWARD_F32);   // f32 B-grid / scalar state backwards: only when asked for
+  const int n_clen = (use_multi && !fwd_only) ? clenshaw_cut(pl, x.n_steps, depths, 1024, back_f32, x.nbatch) : 0;
+  if (pl->res_lo) {   // the LAST call of this plan ran on the chip: did one of ITS launches time out?  (told once, to the plan whose
+    //                   output was poisoned -- never to an unrelated plan; the process runs the strip-marching launches from now on)
+    const unsigned lo = pl->res_lo, hi = pl->res_hi;
+    pl->res_lo = pl->res_hi = 0;
+    if (resident_take_failure(pl->d.device, lo, hi)) {
+      set_error("the previous on-chip / single-launch application of this plan (k_resident, k_ringc_one) timed out waiting for another "
+                "workgroup and its result is NaN (another process running persistent kernels on this GPU outside the lock file's reach?); "
+                "the back-to-back strip-marching launches are used from now on");
+      return GCMF_ERR_HIP;
+    }
+  }
+  bool resident = false;
+  int path = GCMF_PATH_STRIPS;
+  if (n_clen > 0 && x.nbatch == 1 && !(flags & GCMF_NO_RESIDENT)) {
+    int why = GCMF_RESIDENT_OFF;
+    resident = resident_supported(pl, 0, x.rows, std::min(x.n_steps, 64), x.n_steps, &why);   // (small whole grids; GCMF_RESIDENT=1: whatever fits)
+    if (!resident && why == GCMF_RESIDENT_LOCK_BUSY) path = GCMF_PATH_STRIPS_LOCK_BUSY;
+    if (!resident && why == GCMF_RESIDENT_DISABLED) path = GCMF_PATH_STRIPS_DISABLED;
+  }
+  if (resident) path = GCMF_PATH_RESIDENT;
+  pl->last_path = path;
+  ++pl->path_count[path];
+  if (n_clen > 0) {
+    int rc = GCMF_OK;
+    if (resident)
+      rc = sched_resident(x);
+    else if ((flags & GCMF_NO_RESIDENT) || ringc_one_depth(pl, x.n_steps, x.nbatch) <= 0 || !sched_single_launch(x))
+      rc = sched_backward_scalar(x, depths, n_clen);
+    if (rc || pl->n_land == 0) return rc;
+    // the isolated cells' own polynomial (forward recurrence, as the reference computes it)
+    return land_fix_tail(pl, x.p, x.n_steps, x.c, x.din[0], x.dout[0], x.fb32, x.nbatch, x.s);
+  }
+  if (use_multi) return sched_forward_scalar(x);
+  const bool vec_backward = (pl->kind == K_CGRID && pl->clenshaw >= 1) ||
+                            (pl->kind == K_BGRID && pl->clenshaw >= 2 && (pl->d.dtype == GCMF_F64 || back_f32));
+  if (use_vmulti && vec_backward && !fwd_only) return sched_backward_vec(x);
+  if (use_vmulti) return sched_forward_vec(x);
+  return sched_single_steps(x);
+}
+
+// The plan's work buffers are shared by all calls: a call enqueued on another stream (dask worker threads with their own streams) must
+// not start before the previous one has finished with them.  The wait is needed only when this call is on ANOTHER stream than the last
+// one: a stream orders its own work.  The event is recorded lazily, here, on the previous call's stream -- behind everything that stream
+// was given since, which is later than necessary but correct -- so back-to-back calls on one stream pay for no event at all (two queue
+// packets less per application).
+static int wait_for_work(gcmf_plan *pl, hipStream_t s) {
   if (pl->busy_valid && pl->busy_stream != s) {
     if (pl->busy_recorded || hipEventRecord(pl->ev_busy, pl->busy_stream) == hipSuccess) {
       GCMF_HIP(hipStreamWaitEvent(s, pl->ev_busy, 0));
@@ -509,324 +771,15 @@ static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double 
       GCMF_HIP(hipDeviceSynchronize());
     }
   }
-  char *w = (char *)pl->work;
-  const void *din[2];
-  void *dout[2], *A[2], *B[2], *Cb[2], *Db[2], *F[2], *Pp[2];
-  for (int k = 0; k < nc; ++k) {
-    char *base = w + per * k;
-    A[k] = base + oA;
-    B[k] = base + oB;
-    Cb[k] = base + oC;
-    Db[k] = base + oD;
-    F[k] = base + oF;
-    Pp[k] = base + oP;
-    if (on_dev) {
-      din[k] = in[k];
-      dout[k] = out[k];
-    } else {
-      din[k] = base + oIn;
-      dout[k] = base + oOut;
-      GCMF_HIP(hipMemcpyAsync(base + oIn, in[k], ncell * ts, hipMemcpyHostToDevice, s));
-    }
-  }
-  const int rows = (int)pl->rows_alloc;
-  int launches = 0;
-  const bool timing = pl->timing && timed;
-  if (timing) GCMF_HIP(hipEventRecord(pl->ev0, s));
-  if (lapl_only) {
-    StepArgs a{};
-    for (int k = 0; k < nc; ++k) { a.t1[k] = din[k]; a.t0[k] = dout[k]; a.fb_out[k] = nullptr; }
-    a.mode = STEP_LAPL;
-    a.nbatch = nbatch;
-    a.row_lo = 0;
-    a.row_hi = rows;
-    if ((rc = step_dispatch(pl, a, s))) return rc;
-    ++launches;
-  } else {
-    const void *x0[2] = {din[0], din[1]};
-    int depths[1024];
-    const bool fwd_only = flags & GCMF_FORWARD_RECURRENCE;   // the caller wants the reference's forward recurrence / accumulation
-    const bool back_f32 = pl->clenshaw_f32 || (flags & GCMF_BACKWARD_F32);   // f32 B-grid / scalar state backwards: only when asked for
-    const int n_clen = (use_multi && !fwd_only) ? clenshaw_cut(pl, n_steps, depths, 1024, back_f32, nbatch) : 0;
-    // Small fields: the whole polynomial on the chip in ONE launch (64 levels at a time; gcmf_resident.hip) -- the field, both states
-    // and the coefficients live in registers / LDS, nothing but the result goes back to memory.  Same bits as the launches below.
-    bool resident = false;
-    int path = GCMF_PATH_STRIPS;
-    if (pl->res_lo) {   // the LAST call of this plan ran on the chip: did one of ITS launches time out?  (told once, to the plan whose
-      //                   output was poisoned -- never to an unrelated plan; the process runs the strip-marching launches from now on)
-      const unsigned lo = pl->res_lo, hi = pl->res_hi;
-      pl->res_lo = pl->res_hi = 0;
-      if (resident_take_failure(pl->d.device, lo, hi)) {
-        set_error("the previous on-chip / single-launch application of this plan (k_resident, k_ringc_one) timed out waiting for another "
-                  "workgroup and its result is NaN (another process running persistent kernels on this GPU outside the lock file's reach?); "
-                  "the back-to-back strip-marching launches are used from now on");
-        return GCMF_ERR_HIP;
-      }
-    }
-    if (n_clen > 0 && nbatch == 1 && !(flags & GCMF_NO_RESIDENT)) {
-      int why = GCMF_RESIDENT_OFF;
-      resident = resident_supported(pl, 0, rows, std::min(n_steps, 64), n_steps, &why);   // (small whole grids; GCMF_RESIDENT=1: whatever fits)
-      if (!resident && why == GCMF_RESIDENT_LOCK_BUSY) path = GCMF_PATH_STRIPS_LOCK_BUSY;
-      if (!resident && why == GCMF_RESIDENT_DISABLED) path = GCMF_PATH_STRIPS_DISABLED;
-    }
-    if (resident) path = GCMF_PATH_RESIDENT;
-    pl->last_path = path;
-    ++pl->path_count[path];
-    if (resident) {
-      pl->res_lo = pl->res_hi = 0;   // (launch_resident notes the serial numbers of this application's launches)
-      void *pool[4] = {A[0], B[0], Cb[0], Db[0]};
-      const void *u = nullptr, *v = nullptr;
-      double pkk[64];
-      for (int done = 0; done < n_steps;) {
-        const int L = std::min(64, n_steps - done);
-        void *fr[2] = {nullptr, nullptr};
-        int nf = 0;
-        for (int q = 0; q < 4 && nf < 2; ++q)
-          if (pool[q] != u && pool[q] != v) fr[nf++] = pool[q];
-        MultiArgs m{};
-        m.u0 = u; m.v0 = v; m.uo = fr[0]; m.vo = fr[1];
-        m.fb_in = din[0]; m.fb_out = dout[0];
-        m.first = (done == 0); m.last = (done + L == n_steps); m.S = L; m.fb_is_f32 = fb32;
-        for (int t = 0; t < L; ++t) pkk[t] = p[n_steps - (done + 1 + t)];
-        m.p0 = p[n_steps]; m.c = c; m.nbatch = 1; m.row_lo = 0; m.row_hi = rows;
-        if ((rc = dom_begin(pl, s))) return rc;
-        if ((rc = launch_resident(pl, m, pkk, L, s))) return rc;
-        if ((rc = dom_end(pl, s))) return rc;
-        ++launches;
-        u = fr[0]; v = fr[1];
-        done += L;
-      }
-      if (pl->n_land > 0) {
-        if ((rc = ensure_dev_p(pl, p, n_steps, s))) return rc;
-        if ((rc = launch_land_fix(pl, din[0], dout[0], pl->dev_p, n_steps, c, fb32 ? 1 : 0, nbatch, s))) return rc;
-      }
-    } else if (n_clen > 0 && !(flags & GCMF_NO_RESIDENT) && ringc_one_depth(pl, n_steps, nbatch) > 0 &&
-               [&]() -> bool {   // OPT-IN ("single_launch"): the whole polynomial in ONE persistent launch (gcmf_ringc_one.hip); taken when
-                 //               the process may run persistent kernels now, else the back-to-back launches below (same bits)
-                 void *pool[4] = {A[0], B[0], Cb[0], Db[0]};
-                 if (dom_begin(pl, s)) return false;
-                 const int r1 = launch_ringc_one(pl, ringc_one_depth(pl, n_steps, nbatch), p, n_steps, c, din[0], dout[0], pool, s);
-                 if (dom_end(pl, s)) return false;
-                 if (r1 == GCMF_OK) ++launches;
-                 return r1 == GCMF_OK;
-               }()) {
-      if (pl->n_land > 0) {
-        if ((rc = ensure_dev_p(pl, p, n_steps, s))) return rc;
-        if ((rc = launch_land_fix(pl, din[0], dout[0], pl->dev_p, n_steps, c, fb32 ? 1 : 0, nbatch, s))) return rc;
-      }
-    } else if (n_clen > 0) {
-      // Backward (Clenshaw) evaluation, gcmf_ringc_impl.hpp: state (b_{k+1}, b_{k+2}) in a pool of four planes, the constant
-      // input read by every launch, no fbar planes.  The first launch forms b_n = p[n] f as it loads f; level l = 1..n uses
-      // p[n - l]; the last launch writes the result.
-      void *pool[4] = {A[0], B[0], Cb[0], Db[0]};
-      const void *u = nullptr, *v = nullptr;
-      int lvl = 1;
-      for (int q = 0; q < n_clen; ++q) {
-        const int S = depths[q];
-        void *fr[2] = {nullptr, nullptr};
-        int nf = 0;
-        for (int q = 0; q < 4 && nf < 2; ++q)
-          if (pool[q] != u && pool[q] != v) fr[nf++] = pool[q];
-        MultiArgs m{};
-        m.u0 = u; m.v0 = v; m.uo = fr[0]; m.vo = fr[1];
-        m.fb_in = din[0]; m.fb_out = dout[0];
-        m.first = (q == 0); m.last = (q == n_clen - 1); m.S = S; m.fb_is_f32 = fb32;
-        for (int t = 0; t < S; ++t) m.pk[t] = p[n_steps - (lvl + t)];
-        m.p0 = p[n_steps]; m.c = c; m.nbatch = nbatch; m.row_lo = 0; m.row_hi = rows;
-        if ((rc = advance_multi(pl, m, s, &launches, true))) return rc;   // (+ the tripole band on tripolar plans)
-        u = fr[0]; v = fr[1];
-        lvl += S;
-      }
-      if (pl->n_land > 0) {  // the isolated cells' own polynomial (forward recurrence, as the reference computes it)
-        if ((rc = ensure_dev_p(pl, p, n_steps, s))) return rc;
-        if ((rc = launch_land_fix(pl, din[0], dout[0], pl->dev_p, n_steps, c, fb32 ? 1 : 0, nbatch, s))) return rc;
-      }
-    } else if (use_multi) {
-      // Temporally blocked schedule (scalar kinds): each launch advances S steps and reads/writes every plane
-      // once.  prepare/finalize are fused into the first / last launch.  State buffers rotate through a pool
-      // of four because a launch may not overwrite the planes its neighbours' halos are still reading.
-      void *pool[4] = {A[0], B[0], Cb[0], Db[0]};
-      void *Fcur = F[0], *Fnext = w + oF2;   // fbar ping-pongs between two planes (see oF2)
-      const void *u = x0[0], *v = nullptr;
-      int k = 1;
-      bool land_zeroed = false;  // the first blocked launch kept the isolated cells out of the state
-      while (k <= n_steps) {
-        const int left = n_steps - k + 1;
-        int S = 1;
-        const int cand[7] = {8, 7, 6, 5, 4, 3, 2};
-        for (int q = 0; q < 7; ++q)  // largest depth that does not strand a lone single step at the end
-          if (cand[q] <= left && left - cand[q] != 1 && cand[q] <= pl->multi_s && multi_supported(pl, cand[q])) {
-            S = cand[q];
-            break;
-          }
-        void *fr[2] = {nullptr, nullptr};
-        int nf = 0;
-        for (int q = 0; q < 4 && nf < 2; ++q)
-          if (pool[q] != u && pool[q] != v) fr[nf++] = pool[q];
-        const bool is_last = (k + S - 1 == n_steps);
-        if (S >= 2) {
-          MultiArgs m{};
-          m.u0 = u; m.v0 = v; m.uo = fr[0]; m.vo = fr[1];
-          m.fb_in = Fcur; m.fb_out = is_last ? dout[0] : Fnext;
-          std::swap(Fcur, Fnext);
-          m.first = (k == 1); m.last = is_last; m.S = S; m.fb_is_f32 = fb32;
-          m.land_zero = land_zeroed ? 1 : 0;
-          // the first launch may drop land on load if k_land_fix restores it at the end (not for a one-launch filter)
-          m.ring_first = (k == 1 && !is_last && (zero_land || pl->n_land == 0)) ? 1 : 0;
+  return GCMF_OK;
+}
 
-          for (int t = 0; t < S; ++t) m.pk[t] = p[k + t];
-          m.p0 = p[0]; m.c = c; m.nbatch = nbatch; m.row_lo = 0; m.row_hi = rows;
-          if ((rc = advance_multi(pl, m, s, &launches))) return rc;
-          --launches;  // counted once more below
-          u = fr[0]; v = fr[1];
-          if (k == 1 && zero_land && !is_last) {  // keep the isolated cells out of the state from here on
-            // (a first launch by k_ring already took them as zero while it loaded the field)
-            if (!ring_supported(pl, m)) {
-              if ((rc = launch_zero_land(pl, fr[0], fr[1], nbatch, s))) return rc;
-            }   // (k_ring's first launch and k_fold_band took the land as zero while they loaded the field)
-            land_zeroed = true;
-          }
-        } else {
-          StepArgs a1{};
-          a1.mode = (k == 1 ? GCMF_STEP_FIRST : 0u) | (is_last ? GCMF_STEP_LAST : 0u);
-          a1.coef0 = (k == 1) ? p[0] : p[k]; a1.coef1 = p[1]; a1.c = c; a1.fb_is_f32 = fb32; a1.nbatch = nbatch;
-          a1.row_lo = 0; a1.row_hi = rows;
-          const void *src = u;
-          if (k == 1 && prep) {  // the single-step kernel wants T_0 = field*area materialised
-            if ((rc = launch_prepare(pl, din, Pp, nbatch, 0, rows, s))) return rc;
-            ++launches;
-            src = Pp[0];
-          }
-          a1.t1[0] = src; a1.t2[0] = v; a1.t0[0] = fr[0]; a1.fb_in[0] = Fcur; a1.fb_out[0] = is_last ? dout[0] : Fcur;
-          if ((rc = step_dispatch(pl, a1, s))) return rc;
-          v = src; u = fr[0];
-        }
-        ++launches;
-        k += S;
-      }
-      if (land_zeroed) {  // the isolated cells' own polynomial, from the caller's untouched input
-        if ((rc = ensure_dev_p(pl, p, n_steps, s))) return rc;
-        if ((rc = launch_land_fix(pl, din[0], dout[0], pl->dev_p, n_steps, c, fb32 ? 1 : 0, nbatch, s))) return rc;
-      }
-    } else if (use_vmulti && ((pl->kind == K_CGRID && pl->clenshaw >= 1) ||
-                              (pl->kind == K_BGRID && pl->clenshaw >= 2 && (pl->d.dtype == GCMF_F64 || back_f32))) && !fwd_only &&
-               n_steps >= 2 && vec_multi_supported(pl, nbatch, 2)) {
-      // C-grid (B-grid with GCMF_CLENSHAW=2: it is bit-exact with numpy forward, so backward is an option there like for the land-mask
-      // kinds): the polynomial evaluated backwards (k_cgrid_stream2c / k_bgrid_stream2c): state (b_{k+1}, b_{k+2}) in a pool of four
-      // plane pairs, the constant input (u, v) read by every launch, no fbar planes.  Level l = 1..n uses p[n - l]; the first
-      // launch forms b_n = p[n] f as it loads f, the last one writes the result.
-      const void *u[2] = {x0[0], x0[1]}, *v[2] = {nullptr, nullptr};
-      void *pool[4][2] = {{A[0], A[1]}, {B[0], B[1]}, {Cb[0], Cb[1]}, {Db[0], Db[1]}};
-      // four levels per launch with two operand rows in flight: 353-357 G on config 5; five levels leave one row in flight and
-      // spill (305-310 G); the forward kernel at its best (five levels) 280 G
-      // (round 5: k_cgrid_ring, gcmf_cgrid_ring.hip, takes batched f32 levels four or five at a time)
-      // (launches deeper than five levels exist only in k_cgrid_ring, whose 16-byte accesses need the caller's planes aligned)
-      const bool al16 = ptr_al16(x0[0]) && ptr_al16(x0[1]) && ptr_al16(dout[0]) && ptr_al16(dout[1]);
-      const int smax = std::min(pl->multi_s, std::max(4, al16 ? cgrid_ring_smax(pl, nbatch) : std::min(5, cgrid_ring_smax(pl, nbatch))));
-      int lvl = 1;
-      while (lvl <= n_steps) {
-        const int left = n_steps - lvl + 1;
-        const int S = vec_backward_next_depth(pl, nbatch, left, smax);
-        void *fr[2][2];
-        int nf = 0;
-        for (int q = 0; q < 4 && nf < 2; ++q)
-          if (pool[q][0] != u[0] && pool[q][0] != v[0]) { fr[nf][0] = pool[q][0]; fr[nf][1] = pool[q][1]; ++nf; }
-        const bool is_last = (lvl + S - 1 == n_steps);
-        VecMultiArgs m{};
-        for (int q = 0; q < 2; ++q) {
-          m.u0[q] = u[q]; m.uprev[q] = v[q]; m.u1o[q] = fr[0][q]; m.u2o[q] = fr[1][q];
-          m.fb_in[q] = x0[q]; m.fb_out[q] = dout[q];
-        }
-        for (int t = 0; t < S; ++t) m.pk[t] = p[n_steps - (lvl + t)];
-        m.p0 = p[n_steps]; m.c = c; m.S = S; m.clen = 1;
-        m.first = (lvl == 1); m.last = is_last; m.fb_is_f32 = fb32; m.nbatch = nbatch; m.row_lo = 0; m.row_hi = rows;
-        if ((rc = dom_begin(pl, s))) return rc;
-        if ((rc = launch_vec_multi(pl, m, s))) return rc;
-        if ((rc = dom_end(pl, s))) return rc;
-        for (int q = 0; q < 2; ++q) { u[q] = fr[1][q]; v[q] = fr[0][q]; }
-        lvl += S;
-        ++launches;
-      }
-    } else if (use_vmulti) {
-      // vector kinds: S = 2..4 steps per pass, (T_{k-1}, T_{k-2}) -> (T_{k+S-2}, T_{k+S-1}).  Neither output may overwrite
-      // T_{k-2}: the halo rows / columns a strip recomputes need its neighbours' T_{k-2}.  The state rotates through
-      // four buffers.  A lone last step runs the single-step kernel.
-      const void *u[2] = {x0[0], x0[1]}, *v[2] = {nullptr, nullptr};
-      int k = 1;
-      while (k <= n_steps) {
-        const int left = n_steps - k + 1;
-        void *pool[4][2] = {{A[0], A[1]}, {B[0], B[1]}, {Cb[0], Cb[1]}, {Db[0], Db[1]}};
-        void *fr[2][2];
-        int nf = 0;
-        for (int q = 0; q < 4 && nf < 2; ++q)
-          if (pool[q][0] != u[0] && pool[q][0] != v[0]) { fr[nf][0] = pool[q][0]; fr[nf][1] = pool[q][1]; ++nf; }
-        int S = 1;
-        const int cand[5] = {6, 5, 4, 3, 2};
-        for (int q = 0; q < 5; ++q)  // largest depth that does not strand a lone single step at the end
-          if (cand[q] <= left && left - cand[q] != 1 && cand[q] <= pl->multi_s && vec_multi_supported(pl, nbatch, cand[q])) {
-            S = cand[q];
-            break;
-          }
-        if (S == 1 && left >= 2) S = 2;
-        if (S >= 2) {
-          const bool is_last = (k + S - 1 == n_steps);
-          VecMultiArgs m{};
-          for (int q = 0; q < 2; ++q) {
-            m.u0[q] = u[q]; m.uprev[q] = v[q]; m.u1o[q] = fr[0][q]; m.u2o[q] = fr[1][q];
-            m.fb_in[q] = F[q]; m.fb_out[q] = is_last ? dout[q] : F[q];
-          }
-          for (int t = 0; t < S; ++t) m.pk[t] = p[k + t];
-          m.p0 = p[0]; m.c = c; m.S = S;
-          m.first = (k == 1); m.last = is_last; m.fb_is_f32 = fb32; m.nbatch = nbatch; m.row_lo = 0; m.row_hi = rows;
-          if ((rc = dom_begin(pl, s))) return rc;
-          if ((rc = launch_vec_multi(pl, m, s))) return rc;
-          if ((rc = dom_end(pl, s))) return rc;
-          for (int q = 0; q < 2; ++q) { u[q] = fr[1][q]; v[q] = fr[0][q]; }
-          k += S;
-        } else {
-          StepArgs a1{};
-          a1.mode = (k == 1 ? GCMF_STEP_FIRST : 0u) | GCMF_STEP_LAST;
-          a1.coef0 = (k == 1) ? p[0] : p[k]; a1.coef1 = p[1]; a1.c = c; a1.fb_is_f32 = fb32; a1.nbatch = nbatch;
-          a1.row_lo = 0; a1.row_hi = rows;
-          for (int q = 0; q < 2; ++q) {
-            a1.t1[q] = u[q]; a1.t2[q] = v[q]; a1.t0[q] = fr[0][q]; a1.fb_in[q] = F[q]; a1.fb_out[q] = dout[q];
-          }
-          if ((rc = step_dispatch(pl, a1, s))) return rc;
-          k += 1;
-        }
-        ++launches;
-      }
-    } else {
-    if (prep) {  // T_0 = field * area
-      if ((rc = launch_prepare(pl, din, Pp, nbatch, 0, rows, s))) return rc;
-      ++launches;
-      for (int k = 0; k < nc; ++k) x0[k] = Pp[k];
-    }
-    // step k reads T_{k-1} (stencil) and T_{k-2} (centre) and overwrites T_{k-2}'s buffer with T_k:
-    //   k=1: X0 -> A      k=2: (A, X0) -> B      k=3: (B, A) -> A      k=4: (A, B) -> B ...
-    for (int k = 1; k <= n_steps; ++k) {
-      StepArgs a{};
-      a.mode = (k == 1 ? GCMF_STEP_FIRST : 0u) | (k == n_steps ? GCMF_STEP_LAST : 0u);
-      a.coef0 = (k == 1) ? p[0] : p[k];
-      a.coef1 = p[1];
-      a.c = c;
-      a.fb_is_f32 = fb32;
-      a.nbatch = nbatch;
-      a.row_lo = 0;
-      a.row_hi = rows;
-      for (int q = 0; q < nc; ++q) {
-        if (k == 1) { a.t1[q] = x0[q]; a.t2[q] = nullptr; a.t0[q] = A[q]; }
-        else if (k == 2) { a.t1[q] = A[q]; a.t2[q] = x0[q]; a.t0[q] = B[q]; }
-        else if (k % 2) { a.t1[q] = B[q]; a.t2[q] = A[q]; a.t0[q] = A[q]; }
-        else { a.t1[q] = A[q]; a.t2[q] = B[q]; a.t0[q] = B[q]; }
-        a.fb_in[q] = F[q];
-        a.fb_out[q] = (k == n_steps) ? dout[q] : F[q];
-      }
-      if ((rc = step_dispatch(pl, a, s))) return rc;
-      ++launches;
-    }
-    }
-  }
+// After the launches: the work buffers are marked busy, the result goes back to the host (host pointers: `out`, `out_bytes` per
+// component), a timed-out on-chip launch of this call is reported, and the timing events are read.
+static int finish_call(ApplyCtx &x, bool on_dev, void *const *out, size_t out_bytes, bool timing, bool timed) {
+  gcmf_plan *pl = x.pl;
+  const hipStream_t s = x.s;
+  int rc;
   if (timing) GCMF_HIP(hipEventRecord(pl->ev1, s));
   // "work buffers busy": recorded lazily by the NEXT call when it arrives on another stream (back-to-back calls on one stream pay for no
   // event).  That needs this stream to be alive then: a stream handed in by the caller (not the plan's own, not the null stream) may be
@@ -840,10 +793,10 @@ static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double 
   }
   pl->busy_stream = s;
   pl->busy_valid = true;
-  pl->last_launches = timed ? launches : pl->last_launches + launches;
+  pl->last_launches = timed ? x.launches : pl->last_launches + x.launches;
   if (!on_dev) {
-    for (int k = 0; k < nc; ++k)
-      GCMF_HIP(hipMemcpyAsync(out[k], dout[k], ncell * fbs, hipMemcpyDeviceToHost, s));
+    for (int k = 0; k < pl->ncomp; ++k)
+      GCMF_HIP(hipMemcpyAsync(out[k], x.dout[k], out_bytes, hipMemcpyDeviceToHost, s));
     GCMF_HIP(hipStreamSynchronize(s));
     const unsigned rlo = pl->res_lo, rhi = pl->res_hi;
     pl->res_lo = pl->res_hi = 0;   // (the stream is drained: nothing of this call is pending any more)
@@ -859,6 +812,63 @@ static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double 
   }
   if (pl->timing_detail && timed && (rc = dom_collect(pl))) return rc;
   return GCMF_OK;
+}
+
+// Shared driver of gcmf_apply and gcmf_laplacian; the plan's mutex is held and the device is current.
+// `timed` = false: the caller (the pipelined host path) brackets the launches with the timing events itself.
+static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double c, const void *const *in,
+                            void *const *out, int64_t nbatch, uint32_t flags, void *stream, bool lapl_only,
+                            bool timed) {
+  const bool on_dev = flags & GCMF_DEVICE_PTRS;
+  ApplyCtx x{};
+  x.pl = pl;
+  // device pointers: run on exactly the caller's stream (NULL = the HIP default stream) so the work is
+  // ordered with the caller's own kernels; host pointers: the plan's private stream unless one is given
+  x.s = (on_dev || stream) ? (hipStream_t)stream : pl->stream;
+  x.p = p; x.n_steps = n_steps; x.c = c; x.nbatch = nbatch; x.rows = (int)pl->rows_alloc;
+  const bool f32 = pl->d.dtype == GCMF_F32;
+  x.fb32 = f32 && (flags & GCMF_OUT_F32);
+  const size_t ts = dtype_size(pl->d.dtype);
+  const size_t fbs = lapl_only ? ts : ((f32 && !x.fb32) ? 8 : ts);  // element size of fbar == element size of `out`
+  const size_t ncell = (size_t)nbatch * pl->d.ny * pl->d.nx;
+  const bool prep = pl->area_weighted && !lapl_only;
+
+  // work layout per component: [A][B][fbar] (+ [prepared T0]) (+ host staging: [in][out])
+  const size_t szT = align_up(ncell * ts, 256), szF = align_up(ncell * fbs, 256);
+  const bool use_multi = !lapl_only && pl->multi_s >= 2 && n_steps >= 2 && multi_supported(pl, 2);
+  const bool use_vmulti = !lapl_only && pl->multi_s >= 2 && n_steps >= 2 && vec_multi_supported(pl, nbatch, 2);
+  size_t per = 0;
+  const size_t oA = per; per += szT;
+  const size_t oB = per; per += szT;
+  const size_t oC = per; if (use_multi || use_vmulti) per += szT;
+  const size_t oD = per; if (use_multi || use_vmulti) per += szT;
+  const size_t oF = per; per += szF;
+  // second fbar plane (scalar blocked schedule): k_ring re-does a strip from its inputs when it meets a NaN / inf,
+  // so a launch must not accumulate fbar in place
+  const size_t oF2 = per; if (use_multi) per += szF;
+  const size_t oP = per; if (prep) per += szT;
+  const size_t oIn = per; if (!on_dev) per += szT;
+  const size_t oOut = per; if (!on_dev) per += szF;
+  int rc = ensure_work(pl, per * pl->ncomp);
+  if (rc || (rc = wait_for_work(pl, x.s))) return rc;
+  char *w = (char *)pl->work;
+  x.F2 = w + oF2;
+  for (int k = 0; k < pl->ncomp; ++k) {
+    char *base = w + per * k;
+    x.A[k] = base + oA; x.B[k] = base + oB; x.Cb[k] = base + oC; x.Db[k] = base + oD; x.F[k] = base + oF; x.Pp[k] = base + oP;
+    if (on_dev) {
+      x.din[k] = in[k];
+      x.dout[k] = out[k];
+    } else {
+      x.din[k] = base + oIn;
+      x.dout[k] = base + oOut;
+      GCMF_HIP(hipMemcpyAsync(base + oIn, in[k], ncell * ts, hipMemcpyHostToDevice, x.s));
+    }
+  }
+  const bool timing = pl->timing && timed;
+  if (timing) GCMF_HIP(hipEventRecord(pl->ev0, x.s));
+  if ((rc = lapl_only ? lapl_step(x) : run_schedule(x, flags, use_multi, use_vmulti))) return rc;
+  return finish_call(x, on_dev, out, ncell * fbs, timing, timed);
 }
 
 // Host pointers and a batch of fields: the batch is cut into chunks of ~32 MB per component that stream through two

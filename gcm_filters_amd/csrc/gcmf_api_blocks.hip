@@ -6,7 +6,6 @@
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
-#include <vector>
 
 namespace gcmf {
 
@@ -121,9 +120,8 @@ int vec_backward_next_depth(const gcmf_plan *pl, int64_t nbatch, int left, int s
     const int nl = (left + smax - 1) / smax, S = (left + nl - 1) / nl;
     if (S >= 2 && S <= left && left - S != 1 && vec_multi_supported(pl, nbatch, S, true)) return S;
   }
-  for (int cand = smax; cand >= 2; --cand)
-    if (cand <= left && left - cand != 1 && vec_multi_supported(pl, nbatch, cand, true)) return cand;
-  return left;
+  const int S = deepest_depth(left, smax, [&](int d) { return vec_multi_supported(pl, nbatch, d, true); });
+  return S >= 2 ? S : left;
 }
 
 }  // namespace gcmf
@@ -326,10 +324,8 @@ int gcmf_land_fix(gcmf_plan *pl, const double *p, int n_steps, double c, const v
   if (!land_ok(pl, n_steps)) return GCMF_ERR_UNSUPPORTED;
   std::lock_guard<std::mutex> lk(pl->mu);
   GCMF_HIP(hipSetDevice(pl->d.device));
-  int rc = ensure_dev_p(pl, p, n_steps, (hipStream_t)stream);
-  if (rc) return rc;
-  const int fb32 = (pl->d.dtype == GCMF_F32 && (flags & GCMF_OUT_F32)) ? 1 : 0;
-  return launch_land_fix(pl, in[0], out[0], pl->dev_p, n_steps, c, fb32, nbatch, (hipStream_t)stream);
+  const bool fb32 = pl->d.dtype == GCMF_F32 && (flags & GCMF_OUT_F32);
+  return land_fix_tail(pl, p, n_steps, c, in[0], out[0], fb32, nbatch, (hipStream_t)stream);
 }
 
 // One whole filter application on this rank's slab, backward (Clenshaw) evaluation, scalar kinds: the choreography of
@@ -386,9 +382,8 @@ int gcmf_slab_apply_backward(gcmf_plan *pl, gcmf_comm *comm, gcmf_p2p *p2p, int 
   // f's ghost rows: the first launch forms b_n = p_n f on them, the later ones read f on the rows they compute.  Batches (round 6): the
   // rows of the first launch whose S-level cone stays inside the owned rows need none of them, so that exchange -- the only one of an
   // application when the ghost zone is as deep as the filter -- runs BESIDE them, and the two edge pieces follow (one launch cut in
-  // three).  MEASURED, round 6 (tools/measure_batched_scaling.py, 300-row slab of 2400 x 3600, same box, off / on): 16 fields RCCL 1.922 /
-  // 1.974 ms, mailboxes 1.969 / 2.076; 8 fields RCCL 1.185 / 1.134, mailboxes 1.158 / 1.214; config 4, 16 fields 1.672 / 1.742 -- the two
-  // edge pieces cost what the hidden exchange saves.  OFF unless GCMF_SLAB_OVERLAP_FIRST=1.
+  // three).  Measured in round 6 (DESIGN_HISTORY.md), the two edge pieces cost what the hidden exchange saves: OFF unless
+  // GCMF_SLAB_OVERLAP_FIRST=1.
   static const bool first_beside = getenv("GCMF_SLAB_OVERLAP_FIRST") && atoi(getenv("GCMF_SLAB_OVERLAP_FIRST")) != 0;
   bool first_pending = false;
   {
@@ -398,6 +393,18 @@ int gcmf_slab_apply_backward(gcmf_plan *pl, gcmf_comm *comm, gcmf_p2p *p2p, int 
     if (!first_pending && (rc = exchange_finish())) return rc;
   }
   const bool fb32 = (dtype == GCMF_F32) && (flags & GCMF_OUT_F32);
+  auto land_and_guard = [&]() -> int {   // after the last launch, whichever schedule ran
+    if (land_ok(pl, n_steps)) {
+      std::lock_guard<std::mutex> lk(pl->mu);
+      GCMF_HIP(hipSetDevice(pl->d.device));
+      if ((rc = land_fix_tail(pl, p, n_steps, c, X, out, fb32, nbatch, s))) return rc;
+    }
+    if (p2p && multi) {   // a failed exchange must not leave a plausible result (the stencils take NaN ghost rows as zero)
+      const size_t obytes = (size_t)nbatch * ra * nx * ((dtype == GCMF_F32 && fb32) ? 4 : 8);
+      if ((rc = gcmf_p2p_guard(p2p, out, (int64_t)(obytes / 16 * 16), stream))) return rc;
+    }
+    return GCMF_OK;
+  };
   void *u = nullptr, *v = nullptr;
   int valid = hs, lvl = 1;
   // ---- the slab fits on the chip: every stretch between two exchanges is ONE resident launch (gcmf_resident.hip) -- as many levels as
@@ -414,32 +421,28 @@ int gcmf_slab_apply_backward(gcmf_plan *pl, gcmf_comm *comm, gcmf_p2p *p2p, int 
       done += L;
     }
     if (fits) {
-      std::vector<double> pk(64);
+      double pk[64];
       for (int done = 0; done < n_steps;) {
         const int L = std::min(per, n_steps - done);
         if (multi && done > 0) {   // the ghost zone is used up: refresh it
           void *st[2] = {u, v};
           if ((rc = exchange_start(st, 2)) || (rc = exchange_finish())) return rc;
         }
-        void *fr[2] = {nullptr, nullptr};
-        int nf = 0;
-        for (int k = 0; k < 4 && nf < 2; ++k)
-          if (pool[k] != u && pool[k] != v) fr[nf++] = pool[k];
+        void *fr[2];
+        free_planes(pool, 1, u, v, fr);
         const int vo_ = multi ? hs - L : 0;
-        MultiArgs m{};
-        m.u0 = u; m.v0 = v; m.uo = fr[0]; m.vo = fr[1]; m.fb_in = X; m.fb_out = out;
-        for (int t = 0; t < L; ++t) pk[t] = p[n_steps - (done + 1 + t)];
-        m.p0 = p[n_steps]; m.c = c; m.S = L; m.first = (done == 0); m.last = (done + L == n_steps); m.nbatch = 1;
+        MultiArgs m = backward_args(p, n_steps, c, done + 1, L, u, v, fr, X, out, pk);
+        m.nbatch = 1;
         m.row_lo = (int)(fo - (gs ? vo_ : 0)); m.row_hi = (int)(fo + ro + (gn ? vo_ : 0));
         {
           std::lock_guard<std::mutex> lk(pl->mu);
           GCMF_HIP(hipSetDevice(pl->d.device));
-          if ((rc = launch_resident(pl, m, pk.data(), L, s))) return rc;
+          if ((rc = launch_resident(pl, m, pk, L, s))) return rc;
         }
         u = fr[0]; v = fr[1];
         done += L;
       }
-      goto land_and_guard;
+      return land_and_guard();
     }
   }
   for (int q = 0; q < ncut; ++q) {
@@ -449,17 +452,13 @@ int gcmf_slab_apply_backward(gcmf_plan *pl, gcmf_comm *comm, gcmf_p2p *p2p, int 
       if ((rc = exchange_start(st, 2)) || (rc = exchange_finish())) return rc;
       valid = hs;
     }
-    void *fr[2] = {nullptr, nullptr};
-    int nf = 0;
-    for (int k = 0; k < 4 && nf < 2; ++k)
-      if (pool[k] != u && pool[k] != v) fr[nf++] = pool[k];
+    void *fr[2];
+    free_planes(pool, 1, u, v, fr);
     int v_out = multi ? valid - S : 0;
     const int lo = (int)(fo - (gs ? v_out : 0)), hi = (int)(fo + ro + (gn ? v_out : 0));
     const bool last = (q == ncut - 1);
-    MultiArgs m{};
-    m.u0 = u; m.v0 = v; m.uo = fr[0]; m.vo = fr[1]; m.fb_in = X; m.fb_out = out;
-    for (int t = 0; t < S; ++t) m.pk[t] = p[n_steps - (lvl + t)];
-    m.p0 = p[n_steps]; m.c = c; m.S = S; m.first = (q == 0); m.last = last; m.nbatch = nbatch; m.fb_is_f32 = fb32 ? 1 : 0;
+    MultiArgs m = backward_args(p, n_steps, c, lvl, S, u, v, fr, X, out);
+    m.nbatch = nbatch; m.fb_is_f32 = fb32 ? 1 : 0;
     const int nxt = last ? 0 : cut[q + 1];
     const bool ovl = overlap && multi && !last && v_out < nxt && ro >= 4 * (int64_t)hs;
     auto launch = [&](int r0, int r1) -> int {
@@ -499,18 +498,7 @@ int gcmf_slab_apply_backward(gcmf_plan *pl, gcmf_comm *comm, gcmf_p2p *p2p, int 
     valid = v_out;
     lvl += S;
   }
-land_and_guard:
-  if (land_ok(pl, n_steps)) {
-    std::lock_guard<std::mutex> lk(pl->mu);
-    GCMF_HIP(hipSetDevice(pl->d.device));
-    if ((rc = ensure_dev_p(pl, p, n_steps, s))) return rc;
-    if ((rc = launch_land_fix(pl, X, out, pl->dev_p, n_steps, c, fb32 ? 1 : 0, nbatch, s))) return rc;
-  }
-  if (p2p && multi) {   // a failed exchange must not leave a plausible result (the stencils take NaN ghost rows as zero)
-    const size_t obytes = (size_t)nbatch * ra * nx * ((dtype == GCMF_F32 && fb32) ? 4 : 8);
-    if ((rc = gcmf_p2p_guard(p2p, out, (int64_t)(obytes / 16 * 16), stream))) return rc;
-  }
-  return GCMF_OK;
+  return land_and_guard();
 }
 
 
@@ -570,27 +558,18 @@ int gcmf_slab_apply_backward_vec(gcmf_plan *pl, gcmf_comm *comm, gcmf_p2p *p2p, 
       if ((rc = exchange(st, 4))) return rc;
       valid = hs;
     }
-    void *fr[2][2];
-    int nf = 0;
-    for (int q = 0; q < 4 && nf < 2; ++q)
-      if (pool[2 * q] != u[0] && pool[2 * q] != v[0]) { fr[nf][0] = pool[2 * q]; fr[nf][1] = pool[2 * q + 1]; ++nf; }
+    void *fr[4];
+    free_planes(pool, 2, u[0], v[0], fr);
     const int v_out = multi ? valid - S : 0;
-    const bool is_last = (lvl + S - 1 == n_steps);
-    VecMultiArgs m{};
-    for (int q = 0; q < 2; ++q) {
-      m.u0[q] = u[q]; m.uprev[q] = v[q]; m.u1o[q] = fr[0][q]; m.u2o[q] = fr[1][q];
-      m.fb_in[q] = X[q]; m.fb_out[q] = out[q];
-    }
-    for (int t = 0; t < S; ++t) m.pk[t] = p[n_steps - (lvl + t)];
-    m.p0 = p[n_steps]; m.c = c; m.S = S; m.clen = 1;
-    m.first = (lvl == 1); m.last = is_last; m.fb_is_f32 = fb32; m.nbatch = nbatch;
+    VecMultiArgs m = backward_args_vec(p, n_steps, c, lvl, S, u, v, fr, X, out);
+    m.fb_is_f32 = fb32; m.nbatch = nbatch;
     m.row_lo = (int)(fo - (gs ? v_out : 0)); m.row_hi = (int)(fo + ro + (gn ? v_out : 0));
     {
       std::lock_guard<std::mutex> lk(pl->mu);
       GCMF_HIP(hipSetDevice(pl->d.device));
       if ((rc = launch_vec_multi(pl, m, s))) return rc;
     }
-    for (int q = 0; q < 2; ++q) { u[q] = fr[1][q]; v[q] = fr[0][q]; }
+    for (int q = 0; q < 2; ++q) { u[q] = fr[2 + q]; v[q] = fr[q]; }
     valid = v_out;
     lvl += S;
   }
