@@ -30,6 +30,7 @@ EXPORTS = [
     "gcmf_last_timing", "gcmf_set_timing", "gcmf_set_tuning", "gcmf_set_option", "gcmf_last_error", "gcmf_version",
     "gcmf_multi_supported", "gcmf_cheb_multi", "gcmf_multi_supported_vec", "gcmf_cheb_multi_vec",
     "gcmf_has_land", "gcmf_zero_land", "gcmf_land_fix", "gcmf_last_kernel", "gcmf_last_kernel_timing", "gcmf_ring_fallbacks", "gcmf_clenshaw_cut",
+    "gcmf_clenshaw_cut_batch",
     "gcmf_comm_unique_id", "gcmf_comm_create", "gcmf_comm_destroy", "gcmf_halo_start", "gcmf_halo_finish", "gcmf_comm_info",
     "gcmf_build_id", "gcmf_last_kernel_geometry",
     "gcmf_slab_apply_backward", "gcmf_slab_backward_vec_supported", "gcmf_slab_apply_backward_vec", "gcmf_resident_supported", "gcmf_resident_levels", "gcmf_p2p_create", "gcmf_p2p_export", "gcmf_p2p_connect", "gcmf_p2p_start", "gcmf_p2p_finish", "gcmf_p2p_status", "gcmf_p2p_destroy", "gcmf_p2p_guard", "gcmf_p2p_seq", "gcmf_p2p_set_timeout_ms", "gcmf_p2p_debug_skip_post",
@@ -186,6 +187,8 @@ def load() -> C.CDLL:
         lib.gcmf_last_kernel_timing.restype = C.c_int
         lib.gcmf_clenshaw_cut.argtypes = [vp, C.c_int, C.POINTER(C.c_int), C.c_int]
         lib.gcmf_clenshaw_cut.restype = C.c_int
+        lib.gcmf_clenshaw_cut_batch.argtypes = [vp, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int]
+        lib.gcmf_clenshaw_cut_batch.restype = C.c_int
         lib.gcmf_ring_fallbacks.argtypes = [vp, C.POINTER(C.c_int64)]
         lib.gcmf_ring_fallbacks.restype = C.c_int
         lib.gcmf_last_kernel.argtypes = [vp, C.c_char_p, C.c_int]
@@ -368,10 +371,11 @@ class Plan:
         check(load().gcmf_resident_levels(self._h, vp(u), vp(v), vp(uo), vp(vo), vp(f), vp(out), pk.ctypes.data_as(C.POINTER(C.c_double)),
                                           len(pk), float(p0), float(c), int(mode), int(row_lo), int(row_hi), C.c_void_p(stream or None)))
 
-    def clenshaw_cut(self, n_steps: int):
-        """Launch depths of the backward evaluation gcmf_apply uses for this polynomial length ([] = forward recurrence)."""
+    def clenshaw_cut(self, n_steps: int, nbatch: int = 1):
+        """Launch depths of the backward evaluation gcmf_apply uses for this polynomial length and a batch of `nbatch` fields
+        ([] = forward recurrence).  The nine-level launches of tripolar plans depend on the batch (gcmf_clenshaw_cut_batch)."""
         buf = (C.c_int * 1024)()
-        n = load().gcmf_clenshaw_cut(self._h, int(n_steps), buf, 1024)
+        n = load().gcmf_clenshaw_cut_batch(self._h, int(n_steps), int(nbatch), buf, 1024)
         return [buf[i] for i in range(n)]
 
     def multi_supported_vec(self, S: int, nbatch: int) -> bool:

@@ -20,14 +20,15 @@ bool ringc9_ok(const gcmf_plan *pl) {
 }
 
 // ... and whole tripolar f64 flux grids whose launches advance the seam themselves (k_ringcz's fold strips, round 6): no k_fold_band (which
-// stops at eight levels) is involved then.  Depends on the batch: a packed batch keeps the band.
-static bool ringc9_fold_ok(const gcmf_plan *pl, int64_t nbatch) {
+// stops at eight levels) is involved then.  Depends on the launch's batch and rows: a packed batch, more than 64 fields or rows that stop
+// short of the seam keep the band.
+static bool ringc9_fold_ok(const gcmf_plan *pl, int64_t nbatch, int64_t row_lo, int64_t row_hi) {
   if (!(pl && pl->ringc9 && pl->kind == K_FLUX && pl->d.dtype == GCMF_F64 && pl->full && pl->g.fold && pl->g.rows >= 64)) return false;
   MultiArgs a{};
   a.S = 9;
   a.nbatch = nbatch;
-  a.row_lo = 0;
-  a.row_hi = pl->g.rows;
+  a.row_lo = (int)row_lo;
+  a.row_hi = (int)row_hi;
   return ringc_zip_fold_ok(pl, a);
 }
 
@@ -38,8 +39,24 @@ static bool ringc9_slab_ok(const gcmf_plan *pl) {
   return pl && pl->slab_nines && pl->ringc9 && pl->kind == K_FLUX && pl->d.dtype == GCMF_F64 && !pl->full && !pl->tripolar && !pl->g.fold && pl->g.rows >= 64;
 }
 
+// Whether one launch of S levels of the backward evaluation can run for a call with this batch on rows [row_lo, row_hi) of this plan:
+// nullptr if so, otherwise why not.  The one rule gcmf_cheb_multi(GCMF_STEP_CLENSHAW) and gcmf_slab_apply_backward hold a launch to;
+// every depth clenshaw_cut offers for a batch passes it on the plan's whole rows.
+const char *clenshaw_depth_refused(const gcmf_plan *pl, int S, bool first, int64_t nbatch, int64_t row_lo, int64_t row_hi) {
+  if (S < 5 || S > 9) return "a launch of the backward evaluation runs 5..9 levels";
+  if (S == 9 && !ringc9_ok(pl) && !ringc9_slab_ok(pl) && !ringc9_fold_ok(pl, nbatch, row_lo, row_hi)) {
+    if (pl->g.fold && pl->full)
+      return "nine levels on a tripolar plan need the seam advanced inside the launch (k_ringcz's fold strips: rows up to the seam, at "
+             "most 64 fields, a batch the launcher would not pack); k_fold_band stops at eight";
+    return "nine levels need an f64 flux-form plan of 64 rows or more (a whole grid, or a row slab with option slab_nines)";
+  }
+  if (first && S == 8 && pl->d.dtype != GCMF_F64) return "an f32-state evaluation never starts with eight levels";
+  return nullptr;
+}
+
 // Backward (Clenshaw) evaluation (gcmf_ringc_impl.hpp): whether gcmf_apply uses it for this plan and polynomial, and how the
-// n_steps levels are cut into launches of 5..8 (never leaving 1..4 or 9 behind).  plan->clenshaw = 1: the flux kinds, whose
+// n_steps levels are cut into launches of 5..8, or of up to nine where a nine-level kernel runs for this plan and batch (never leaving
+// 1..4 behind).  plan->clenshaw = 1: the flux kinds, whose
 // launches run at memcpy rate and gain the plane they no longer move (config 3: +10 %); 2: every scalar kind (the land-mask
 // kernel is bound by its instruction stream and gains nothing: 93 -> 92-95 us per launch).  Needs the isolated cells fixed up
 // by k_land_fix when there is land (land_ok).
@@ -57,7 +74,7 @@ int clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, 
   // (f32 state: the flux kinds since round 3, the REGULAR / land-mask kinds since round 4)
   if (!pl->ring || !pl->zero_row || pl->multi_s < 8 || !multi_supported(pl, 8)) return 0;
   if (pl->n_land > 0 && !land_ok(pl, n_steps)) return 0;
-  const bool nines_full = ringc9_ok(pl) || ringc9_fold_ok(pl, nbatch), nines = nines_full || ringc9_slab_ok(pl);
+  const bool nines_full = ringc9_ok(pl) || ringc9_fold_ok(pl, nbatch, 0, pl->g.rows), nines = nines_full || ringc9_slab_ok(pl);
   if (!(n_steps >= 10 || (n_steps >= 5 && n_steps <= 8) || (n_steps == 9 && nines))) return 0;
   int smax = pl->ringc_smax;
   if (!smax && nbatch == 1 && nines_full && pl->ringc_zip && (long long)pl->g.rows * pl->g.nx <= 2500000LL && n_steps >= 10) {
@@ -171,6 +188,11 @@ int gcmf_clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_dep
   return clenshaw_cut(pl, n_steps, depths, max_depths);
 }
 
+int gcmf_clenshaw_cut_batch(const gcmf_plan *pl, int n_steps, int64_t nbatch, int *depths, int max_depths) {
+  if (!pl || !depths || max_depths < 1 || nbatch < 1) return 0;
+  return clenshaw_cut(pl, n_steps, depths, max_depths, false, nbatch);
+}
+
 int gcmf_cheb_multi(gcmf_plan *pl, const void *u, const void *v, void *uo, void *vo, const void *fbar_in,
                     void *fbar_out, const double *pk, int S, double p0, double c, uint32_t mode, uint32_t flags,
                     int64_t nbatch, int64_t row_lo, int64_t row_hi, void *stream) {
@@ -179,11 +201,14 @@ int gcmf_cheb_multi(gcmf_plan *pl, const void *u, const void *v, void *uo, void 
     // b_n = p0 * f itself), fbar_in = the constant input f, pk[t] = coefficient of level t + 1, LAST: fbar_out = the result
     const bool first = mode & GCMF_STEP_FIRST, last = mode & GCMF_STEP_LAST;
     int probe[2];
-    // (is the backward evaluation on offer for this plan at all: a 10-level polynomial can always be cut, [5, 5]; an f32 filter never
-    // starts with eight levels, see clenshaw_cut)
-    if (pl->ncomp != 1 || S < 5 || S > ((ringc9_ok(pl) || ringc9_slab_ok(pl)) ? 9 : 8) || !pl->ring || !pl->zero_row || clenshaw_cut(pl, 10, probe, 2, false, 2) != 2 ||
-        (first && S == 8 && pl->d.dtype != GCMF_F64)) {
-      set_error("gcmf_cheb_multi: the backward evaluation is not available for this plan / depth %d", S);
+    // (is the backward evaluation on offer for this plan at all: a 10-level polynomial can always be cut, [5, 5])
+    if (pl->ncomp != 1 || !pl->ring || !pl->zero_row || clenshaw_cut(pl, 10, probe, 2, false, 2) != 2) {
+      set_error("gcmf_cheb_multi: the backward evaluation is not available for this plan");
+      return GCMF_ERR_UNSUPPORTED;
+    }
+    if (const char *why = clenshaw_depth_refused(pl, S, first, nbatch, row_lo, row_hi)) {
+      set_error("gcmf_cheb_multi: %d levels of the backward evaluation cannot run in one launch of %lld fields on rows [%lld, %lld) of this plan: %s",
+                S, (long long)nbatch, (long long)row_lo, (long long)row_hi, why);
       return GCMF_ERR_UNSUPPORTED;
     }
     if (!fbar_in || (!first && (!u || !v)) || (!last && (!uo || !vo)) || (last && !fbar_out) || (uo && (uo == u || uo == v)) ||
@@ -350,6 +375,13 @@ int gcmf_slab_apply_backward(gcmf_plan *pl, gcmf_comm *comm, gcmf_p2p *p2p, int 
   if (total != n_steps || (multi && (halo < deepest || !(comm || p2p))) || (comm && p2p)) {
     set_error("gcmf_slab_apply_backward: the cut does not add up to n_steps, the halo is shallower than a launch, or no exchange was given");
     return GCMF_ERR_INVALID_ARG;
+  }
+  for (int q = 0; q < ncut; ++q) {   // (the rows: the owned ones -- what a slab's launches reach beyond them does not decide a depth)
+    if (const char *why = clenshaw_depth_refused(pl, cut[q], q == 0, nbatch, pl->first_owned, pl->first_owned + pl->rows_owned)) {
+      set_error("gcmf_slab_apply_backward: launch %d of the cut (%d levels) cannot run for %lld fields on this plan: %s", q, cut[q],
+                (long long)nbatch, why);
+      return GCMF_ERR_UNSUPPORTED;
+    }
   }
   hipStream_t s = (hipStream_t)stream;
   {   // an on-chip launch of this plan's PREVIOUS application timed out (its result is NaN): told once, here (as gcmf_apply does)

@@ -75,9 +75,9 @@ class HipSlabEngine:
     def land_fix(self, p, c, ins, outs, nbatch):
         self.plan.land_fix(p, c, self._ptrs(ins), self._ptrs(outs), nbatch, stream=self._stream())
 
-    def clenshaw_cut(self, n_steps):
-        """Launch depths of the backward evaluation gcmf_apply uses for this plan and polynomial ([] = forward recurrence)."""
-        return self.plan.clenshaw_cut(n_steps) if self.plan.ncomp == 1 else []
+    def clenshaw_cut(self, n_steps, nbatch=1):
+        """Launch depths of the backward evaluation gcmf_apply uses for this plan, polynomial and batch ([] = forward recurrence)."""
+        return self.plan.clenshaw_cut(n_steps, nbatch) if self.plan.ncomp == 1 else []
 
     def multi(self, u, v, uo, vo, fb_in, fb_out, pk, p0, c, mode, nbatch, row_lo, row_hi):
         """S = len(pk) recurrence steps in one HBM pass (gcmf_cheb_multi_vec); per-component tensor lists."""
@@ -640,6 +640,10 @@ class SlabFilter:
         lone field on slabs of 700 rows and more (measured, experiments/scripts/slab_nines_ab.py: one field 600 rows 301 against 295 us,
         800 rows 358 against 372, 1200 rows 490 against 543; four fields 8-9 % at every height).  Every rank takes the same branch: the
         batch is the same everywhere and the tallest slab of the run was reduced over the ranks."""
+        if not self.multi and self.world == 1 and isinstance(self.engine, HipSlabEngine):
+            # one rank, no ghost rows: the plan is the whole grid, and its cut is gcmf_apply's for this batch (a tripolar grid takes nine levels
+            # per launch only while k_ringcz advances the seam, which depends on the batch); [] = the forward recurrence (n = 9 without nines)
+            return self.engine.clenshaw_cut(self.n_steps, nbatch)
         use9 = bool(self._cut9) and (nbatch >= 2 or getattr(self, "_rows_owned_max", 0) >= int(os.environ.get("GCMF_SLAB_NINES_MIN_ROWS", "700")))
         plan = getattr(self.engine, "plan", None)
         if hasattr(plan, "set_option") and self._cut9:
@@ -672,8 +676,8 @@ class SlabFilter:
         prepared = False
         keep_land_out = can_multi and hasattr(self.engine, "has_land") and self.engine.has_land()
         land_zeroed = False
-        if self.backward_cut:
-            cut = self._cut_for(nbatch)
+        cut = self._cut_for(nbatch) if self.backward_cut else []
+        if cut:
             if self.native_driver and self.ncomp == 1 and isinstance(self.engine, HipSlabEngine) and self.exchange_kind in ("native", "p2p"):
                 return self._apply_backward_native(cut, st, p, nbatch)
             return self._apply_backward(cut, st, p, nbatch)

@@ -210,14 +210,20 @@ int gcmf_multi_supported(const gcmf_plan *plan, int S);
  * and for VECTOR_C_GRID (f32 state: the whole recurrence then runs in f32, 2e-6 from the f64-accumulated forward result at
  * n = 44); env GCMF_CLENSHAW = 0 off / 1 those / 2 also the other f64 scalar types.  gcmf_cheb_multi_vec (vector slab callers)
  * runs the forward recurrence.
- * gcmf_clenshaw_cut: the launch depths (each 5..8, summing to n_steps) gcmf_apply uses for this plan and n_steps -- return value
- * = their number, 0 = it runs the forward recurrence.  A slab caller does the same with gcmf_cheb_multi and
+ * gcmf_clenshaw_cut_batch: the launch depths (each 5..9, summing to n_steps) gcmf_apply uses for this plan, n_steps and a batch of
+ * nbatch fields -- return value = their number, 0 = it runs the forward recurrence.  Nine levels per launch only where a launch of
+ * nine runs and that saves a launch: whole f64 flux-form grids of 64 rows or more (tripolar ones only while k_ringcz advances the
+ * seam inside the launch -- nx >= 256 and a multiple of 4, at most 64 fields, a batch the launcher would not pack -- so the answer
+ * depends on nbatch) and row slabs of such grids without a seam when option "slab_nines" is on.  gcmf_clenshaw_cut: the same for
+ * nbatch = 1.  gcmf_cheb_multi and gcmf_slab_apply_backward refuse (GCMF_ERR_UNSUPPORTED) a depth that cannot run for their own
+ * batch and rows, so a cut is to be taken for the batch it is run with.  A slab caller does the same with gcmf_cheb_multi and
  * GCMF_STEP_CLENSHAW:  level l = 1..n_steps computes b_{n-l};  launch with levels l0 .. l0+S-1:  u = b_{n-l0+1}, v = b_{n-l0+2}
  * (FIRST, l0 = 1: ignored, the launch forms b_n = p0 * f itself: pass p0 = p[n]),  fbar_in = f,  pk[t] = p[n - (l0 + t)],
  * uo = b_{n-l0-S+1}, vo = b_{n-l0-S+2};  LAST (l0 + S - 1 = n): fbar_out = the result (finalize() applied), uo / vo unused.
  * Isolated (land) cells are taken as zero throughout: run gcmf_land_fix on the result when gcmf_has_land(plan).
  */
 int gcmf_clenshaw_cut(const gcmf_plan *plan, int n_steps, int *depths, int max_depths);
+int gcmf_clenshaw_cut_batch(const gcmf_plan *plan, int n_steps, int64_t nbatch, int *depths, int max_depths);
 int gcmf_cheb_multi(gcmf_plan *plan, const void *u, const void *v, void *uo, void *vo, const void *fbar_in,
                     void *fbar_out, const double *pk, int S, double p0, double c, uint32_t mode, uint32_t flags,
                     int64_t nbatch, int64_t row_lo, int64_t row_hi, void *stream);
@@ -329,7 +335,7 @@ void gcmf_p2p_destroy(gcmf_p2p *p);
  * ghost-zone bookkeeping, the edge / interior split that overlaps the exchange, and the halo exchanges themselves (through `comm` --
  * RCCL -- or `p2p` -- mailboxes; both NULL for a slab without neighbours), all enqueued on `stream`.  X: this rank's input with its own rows
  * filled in, pool: four state planes, out: the result (f64; the state dtype with GCMF_OUT_F32), all (nbatch, rows_alloc, nx) device
- * arrays; cut / ncut: gcmf_clenshaw_cut; halo: ghost rows per side (>= the deepest launch); south / north: peer ranks or -1; overlap != 0:
+ * arrays; cut / ncut: gcmf_clenshaw_cut_batch for this nbatch; halo: ghost rows per side (>= the deepest launch); south / north: peer ranks or -1; overlap != 0:
  * post the exchange between the edge strips and the interior of the launch that uses up the ghost zone (slabs of >= 4 halo rows).
  * What gcm_filters_amd/distributed.py otherwise does from Python, ~15 us of host time per launch and 13-33 us per exchange. */
 int gcmf_slab_apply_backward(gcmf_plan *plan, gcmf_comm *comm, gcmf_p2p *p2p, int south, int north, const double *p, int n_steps, double c,
