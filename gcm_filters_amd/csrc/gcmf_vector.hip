@@ -257,9 +257,11 @@ template <typename T, typename FB> static int launch_vec(gcmf_plan *pl, const St
     const long long nblocks = (long long)((ntiles + 7) / 8) * 8 * a.nbatch;
     dim3 grid((unsigned)nblocks, 1, 1);
     hipLaunchKernelGGL((k_cgrid_step<T, FB>), grid, block, 0, s, P, ntx, ntiles, (int)a.nbatch);
+    note_kernel(pl, std::string("gcmf::k_cgrid_step<") + tyname<T>() + ", " + tyname<FB>() + ">", 1);
   } else {
     dim3 grid((g.nx + 63) / 64, (nrows + 4 * BG_ROWS - 1) / (4 * BG_ROWS), (unsigned)a.nbatch);
     hipLaunchKernelGGL((k_bgrid_step<T, FB>), grid, block, 0, s, P);
+    note_kernel(pl, std::string("gcmf::k_bgrid_step<") + tyname<T>() + ", " + tyname<FB>() + ">", 1);
   }
   GCMF_HIP(hipGetLastError());
   return GCMF_OK;

@@ -1,7 +1,9 @@
-"""Randomised GPU-vs-oracle sweep (not part of the test suite): grid types x shapes x dtypes x batches x n_steps."""
-import sys, time
+"""Randomised GPU-vs-oracle sweep (not part of the test suite): grid types x shapes x dtypes x batches x n_steps.
+
+Exits non-zero when any case failed: an error above tolerance, a NaN-pattern mismatch, or an exception (a launch that failed)."""
+import os, sys, time
 import numpy as np
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gcm_filters_amd import Filter, FilterShape, GridType, testing as T
 from gcm_filters_amd.kernels import clear_plan_cache
 from oracle import gcmf_oracle as O
@@ -11,6 +13,7 @@ EVAL = sys.argv[sys.argv.index("--eval") + 1] if "--eval" in sys.argv else "auto
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
 ncase = int(sys.argv[2]) if len(sys.argv) > 2 else 200
 worst = {}
+failures = []
 t0 = time.time()
 for it in range(ncase):
     grid = T.ALL_GRIDS[rng.integers(len(T.ALL_GRIDS))]
@@ -21,13 +24,15 @@ for it in range(ncase):
     vec = grid in T.VECTOR_GRIDS
     if "--tiny" in sys.argv:
         ny = int(rng.integers(1, 14)); nx = int(rng.integers(1, 14))
+    elif "--narrow" in sys.argv:   # tall, narrow grids: ghost columns wrap around x more than once, strips just above the depth bound
+        S = int(rng.integers(2, 10)); nx = int(rng.integers(1, 17)); ny = int(rng.integers(S + 1, 201))
     elif "--mid" in sys.argv:   # strips of 5..60 rows on whole grids: early-exit strips, both march directions, the level ramp
         ny = int(rng.integers(300, 1300)); nx = int(rng.integers(400, 1600))
     else:
         ny = int(rng.integers(3, 200)); nx = int(rng.integers(2, 700))
     if grid.startswith("TRIPOLAR"):
         nx += nx % 2; ny = max(ny, 4)
-    if rng.random() < 0.5: nx = (nx // 4 + 1) * 4      # vector-width friendly half of the time
+    if rng.random() < 0.5: nx = (nx // 4 + 1) * 4 if "--narrow" not in sys.argv else max(4, nx // 4 * 4)   # vector-width friendly half of the time
     if grid.startswith("TRIPOLAR"):
         nx += nx % 2; ny = max(ny, 2)
     shape = (ny, nx)
@@ -77,12 +82,14 @@ for it in range(ncase):
         with np.errstate(all="ignore"):
             want = O.filter_func_vec(spec, grid, *fields, gv) if vec else (O.filter_func(spec, grid, fields[0], gv),)
     except Exception as e:
-        print("EXC", grid, shape, dt, nb, n_steps, repr(e)[:200]); continue
+        print("EXC", grid, shape, dt, nb, n_steps, repr(e)[:200])
+        failures.append(("EXC", grid, shape, dt, nb, n_steps)); continue
     err = 0.0
     for g, w in zip(got, want):
         assert g.dtype == w.dtype and g.shape == w.shape, (grid, g.dtype, w.dtype)
         if not np.array_equal(np.isnan(g), np.isnan(w)):
-            print("NANPATTERN", grid, shape, dt, nb, n_steps); err = np.inf; break
+            print("NANPATTERN", grid, shape, dt, nb, n_steps); err = np.inf
+            failures.append(("NANPATTERN", grid, shape, dt, nb, n_steps)); break
         ok = np.isfinite(w)
         sc = np.abs(w[ok]).max() if ok.any() else 1.0
         if sc > 0 and ok.any():
@@ -92,6 +99,10 @@ for it in range(ncase):
     worst[key] = max(worst.get(key, 0.0), err)
     if not err <= tol:
         print("FAIL", grid, shape, dt, nb, shp, n_steps, err)
+        if np.isfinite(err):
+            failures.append(("FAIL", grid, shape, dt, nb, n_steps))
     if it % 50 == 49: clear_plan_cache()
 print(f"{ncase} cases in {time.time()-t0:.1f} s; worst relative errors:")
 for k in sorted(worst): print("  ", k, f"{worst[k]:.2e}")
+print(f"{len(failures)} failed case(s)")
+sys.exit(1 if failures else 0)
