@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- throughput of the fused iterated-Laplacian filter on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--scaling strong|weak] [--no-cpu] [--no-extra]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config {2,3,4,5}] [--scaling strong|weak] [--full [--no-cpu] [--no-extra]]
                     [--dump-outputs DIR]
 
 A "step" is ONE whole filter application (all n_steps Chebyshev/Laplacian steps) of the workload's field(s),
@@ -16,8 +16,10 @@ xGMI (gcm_filters_amd/distributed.py); the default is STRONG scaling (the one BA
 figure (N x ny rows) is measured in the same run and printed as `weak`.  Config 5 (50 levels) shards its levels
 over the ranks: no communication at all.
 
-Prints ONE JSON line on rank 0 (task contract) with `roofline`, `cpu_baseline`, `parity` and `extra_configs`.
-The run FAILS (exit 1) if the timed workload's output differs from the oracle / the reference-generated probes.
+Prints ONE JSON line on rank 0 (task contract).  N = 1: a plain run sets up, warms up, times the K steps, writes --dump-outputs and
+prints the line (`value`, `ms_per_step`, the spread of the timed blocks) -- nothing else.  `--full` adds `roofline`, `parity`,
+`cpu_baseline`, `extra_configs`, `host_path` and `summary`, and then the run FAILS (exit 1) if the timed workload's output differs from
+the oracle / the reference-generated probes.  The N > 1 line and `--kinds` do not depend on `--full`.
 """
 import argparse
 import json
@@ -268,8 +270,13 @@ def parse():
     ap.add_argument("--exchange", choices=["auto", "native", "torch", "p2p"], default="auto",
                     help="N>1 halo exchange: native = RCCL send / recv issued by libgcmf on a side stream; torch = torch.distributed P2P; "
                          "p2p = peer stores into IPC-mapped mailboxes + flags on the compute stream (csrc/gcmf_p2p.hip, one node)")
-    ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg (and the oracle parity check)")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra_configs measurements (configs 2, 4, 5)")
+    ap.add_argument("--full", action="store_true",
+                    help="--gpus 1: besides the headline figure, measure and check everything else (roofline of the dominant kernel, parity "
+                         "against the oracle and the reference probes, cpu_baseline, extra_configs, host_path, summary); without it the run "
+                         "sets up, warms up, times the K steps, writes --dump-outputs and prints the result line")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the cpu_baseline leg (and the oracle parity check)")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra_configs measurements (configs 1, 2, 4, 5, the smaller grids, "
+                                                            "the single launch) and host_path")
     ap.add_argument("--no-replan", action="store_true", help="keep ONE plan for all timed blocks (profiling runs: one placement)")
     ap.add_argument("--kinds", action="store_true", help="instead of the BASELINE line: one roofline record per Laplacian kind that is not a "
                     "BASELINE config (B-grid, MOM5U/T, the area-weighted and tripolar regular kinds) at --ny x --nx (tools/bench_kinds.py)")
@@ -328,7 +335,7 @@ def main_single(args):
     # north-star gate (fp64).  f32 state: SURVEY 8d's gate is 1e-4; held to 1e-5 here -- config 5 (n_steps 44) measures 1.1e-6 against
     # the reference's probes (the reference's own f32 path is 3e-6 off f64 arithmetic, the default here 1.8e-6)
     tol = lambda itemsize: 1e-6 if itemsize == 8 else 1e-5
-    r = run_single(args.config, args, dev, args.steps, args.warmup, scale=args.filter_scale, tuned=tuned)
+    r = run_single(args.config, args, dev, args.steps, args.warmup, scale=args.filter_scale, tuned=tuned, kernel_timing=args.full)
     sp = spread_of(r)
     fk = r["fk"]
     out = {
@@ -345,9 +352,13 @@ def main_single(args):
                    "filter": f"{fk['filter_shape']} filter_scale={fk['filter_scale']:.6g} dx_min={fk['dx_min']:.6g}",
                    "n_steps": r["n_steps"], "global_grid": [args.ny, args.nx], "parallelism": "single GPU"},
     }
-    out["roofline"] = roofline_of(args.config, r, args.steps, not tuned)
+    if args.full:
+        out["roofline"] = roofline_of(args.config, r, args.steps, not tuned)
     if args.dump_outputs:
         out["dump_outputs"] = dump_outputs(r["outs"], args.dump_outputs)
+    if not args.full:   # a plain run: the headline figure and nothing else
+        print(json.dumps(out))
+        return 0
     nbatch_main = r["nbatch"]
     failed = []
     # ---- parity of the TIMED workload's output -----------------------------------------------------------------

@@ -75,7 +75,7 @@ def test_hung_multi_rank_run_is_killed_by_the_parent():
 
 
 def test_single_gpu_line_carries_parity_and_roofline():
-    r = _run(["--steps", "2", "--warmup", "1", "--no-extra", "--cpu-steps", "3"])
+    r = _run(["--steps", "2", "--warmup", "1", "--full", "--no-extra", "--cpu-steps", "3"])
     assert r.returncode == 0, r.stderr[-2000:]
     line = _json_line(r.stdout)
     assert line["n_gpus"] == 1 and line["config"]["n_steps"] == 63
@@ -99,6 +99,29 @@ def test_single_gpu_line_carries_parity_and_roofline():
     assert list(line)[-1] == "summary" and len(json.dumps(line["summary"])) <= 1500
     row = line["summary"]["cfg3"]
     assert abs(row[0] - line["value"] / 1e9) < 0.06 and abs(row[1] - rf["frac"]) < 1e-3 and row[3] <= 1e-6
+
+
+def test_plain_line_is_the_headline_alone(tmp_path):
+    """Without `--full` the run sets up, warms up, times the K steps, writes --dump-outputs and prints the line: the contract's fields and
+    the spread of the timed blocks, none of the records that take measurements or checks of their own.  `--full` adds them and leaves the
+    timed result as it is."""
+    import numpy as np
+
+    lines, dumps = {}, {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-cpu", "--no-extra"])):
+        d = str(tmp_path / mode)
+        r = _run(["--steps", "3", "--warmup", "1", "--ny", "240", "--nx", "360", "--dump-outputs", d, *extra])
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[mode] = _json_line(r.stdout)
+        dumps[mode] = np.load(os.path.join(d, "filtered.npy"))
+    plain, full = lines["plain"], lines["full"]
+    assert plain["metric"] == "grid-cells*Laplacian-steps/sec" and plain["unit"] == "cell-steps/s" and plain["higher_is_better"] is True
+    assert plain["dtype"] == "f64" and plain["value"] > 0 and plain["ms_per_step"] > 0 and plain["steps"] == 3 and plain["warmup"] == 1
+    assert sum(plain["timing"]["applications_per_block"]) == 3 and plain["value_min"] <= plain["value"] <= plain["value_max"]
+    assert not {"roofline", "parity", "cpu_baseline", "cpu_baseline_pool", "extra_configs", "host_path", "summary"} & set(plain)
+    assert set(plain) <= set(full) and full["roofline"]["kernel"].startswith("gcmf::k_") and list(full)[-1] == "summary"
+    assert full["parity"]["tolerance"] == 1e-6 and full["cpu_baseline"] is None
+    assert np.array_equal(dumps["plain"], dumps["full"], equal_nan=True)
 
 
 def test_kinds_line_has_a_roofline_per_kind():

@@ -12,7 +12,7 @@ for i in range(n):
     for val in (a, b):
         for cfg in cfgs:
             env = dict(os.environ, **{var: val})
-            out = subprocess.run([sys.executable, os.path.join(here, "bench.py"), "--config", str(cfg), "--no-cpu", "--no-extra"],
+            out = subprocess.run([sys.executable, os.path.join(here, "bench.py"), "--config", str(cfg), "--full", "--no-cpu", "--no-extra"],
                                  capture_output=True, text=True, env=env).stdout.strip().splitlines()[-1]
             d = json.loads(out)
             res.setdefault((cfg, val), []).append((d["value"] / 1e9, d["roofline"]["avg_launch_ms"] * 1e3))

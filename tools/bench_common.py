@@ -207,9 +207,10 @@ def load_traffic(cfg, kernel_ran, geometry=None):
     return rec, f"profiles/hbm_traffic.json:{key} <- {rec.get('source')} ({prof}, geometry {want})"
 
 
-def run_single(cfg, args, dev, steps, warmup, scale=0.0, levels=None, tuned=False, evaluation="auto"):
+def run_single(cfg, args, dev, steps, warmup, scale=0.0, levels=None, tuned=False, evaluation="auto", kernel_timing=True):
     """Time `steps` filter applications of BASELINE config `cfg` on this process's GPU.  Returns a dict with the raw
-    measurements, the workload and the device outputs of the last timed application."""
+    measurements, the workload and the device outputs of the last timed application.  kernel_timing: after the timed region,
+    time the dominant kernel's launches in a second, untimed pass (what roofline_of needs); without it the dom_* figures are 0."""
     import torch
 
     from gcm_filters_amd import Filter, FilterShape, GridType, _lib, testing as T
@@ -287,22 +288,24 @@ def run_single(cfg, args, dev, steps, warmup, scale=0.0, levels=None, tuned=Fals
         block_s.append(time.perf_counter() - t0)
     elapsed = sum(block_s)
     timed_outs = outs   # what the last timed application returned (parity checks, bench.py --dump-outputs)
-    plan.last_kernel()  # reset
-    outs = run()   # (untimed) names the dominant kernel of the plan now in use
-    torch.cuda.synchronize()
-    # kernel-level timing in a second, untimed pass: an event pair around the whole recurrence and one around every
-    # launch of the dominant kernel, recorded on the stream the kernels run on
-    plan.set_timing(2)
     dom_ms, dom_n, dom_min, dom_max = 0.0, 0, 1e30, 0.0
     kernel_ms, launches = 0.0, 0
-    dom_reps = max(1, min(steps, 3))
-    for _ in range(dom_reps):
-        run()
-        ms, nl = plan.last_timing()
-        kernel_ms, launches = kernel_ms + ms, launches + nl
-        ms, nl, lo, hi = plan.last_kernel_timing()
-        dom_ms, dom_n, dom_min, dom_max = dom_ms + ms, dom_n + nl, min(dom_min, lo), max(dom_max, hi)
-    plan.set_timing(False)
+    dom_reps = 0
+    if kernel_timing:
+        plan.last_kernel()  # reset
+        outs = run()   # (untimed) names the dominant kernel of the plan now in use
+        torch.cuda.synchronize()
+        # kernel-level timing in a second, untimed pass: an event pair around the whole recurrence and one around every
+        # launch of the dominant kernel, recorded on the stream the kernels run on
+        plan.set_timing(2)
+        dom_reps = max(1, min(steps, 3))
+        for _ in range(dom_reps):
+            run()
+            ms, nl = plan.last_timing()
+            kernel_ms, launches = kernel_ms + ms, launches + nl
+            ms, nl, lo, hi = plan.last_kernel_timing()
+            dom_ms, dom_n, dom_min, dom_max = dom_ms + ms, dom_n + nl, min(dom_min, lo), max(dom_max, hi)
+        plan.set_timing(False)
     return dict(dom_ms=dom_ms, dom_n=dom_n, dom_min=dom_min, dom_max=dom_max, dom_reps=dom_reps, wl=wl, grid=grid, fk=fk, itemsize=itemsize, nbatch=nbatch, n_steps=n_steps, elapsed=elapsed,
                 kernel_ms=kernel_ms, launches=launches, outs=list(timed_outs), kernel=plan.last_kernel(), geometry=plan.last_kernel_geometry(),
                 flt=flt, d_in=d_in, cells=args.ny * args.nx * nbatch, block_s=block_s, per_block=per_block, replans=replans)
