@@ -297,3 +297,169 @@ def free_port(tries: int = 64) -> int:
     with socket.socket() as sk:       # give up on the preference
         sk.bind(("127.0.0.1", 0))
         return sk.getsockname()[1]
+
+
+# ------------------------------------------------------------------------------------------------
+# coastlines the reference's fixture never draws (tests/test_gpu_coastlines.py, make_golden.py --coastlines, tools/fuzz_gpu.py --coast)
+# ------------------------------------------------------------------------------------------------
+COASTLINES = ("open_south", "speckle", "checker", "channels", "lakes", "one_land_cell", "all_land", "on_the_cuts", "fold")
+BACKWARD_WINDOWS = (112, 108, 240)     # useful columns of a backward scalar window: f64 at S <= 8, f64 at S = 9, f32
+
+
+def coastline_names(tripolar=False):
+    """The coastlines defined for a grid kind: `fold` needs the tripole seam, `open_south` a wet southernmost row."""
+    return tuple(n for n in COASTLINES if n != ("open_south" if tripolar else "fold"))
+
+
+def coastline(name, shape, seed=0, tripolar=False, cuts=()):
+    """Wet mask (1 = ocean, 0 = land; float64) of coastline `name` on `shape` (ny >= 24, nx >= 24), from PCG64(seed).
+
+    open_south     rows 0 and ny-1 wet along most of x, a land band in mid-grid, land blocks that straddle the x seam
+    speckle        each cell land with probability 0.35
+    checker        (i + j) % 2
+    channels       one-cell meridional walls every 11 columns, each pierced by a one-cell strait every 13 rows; one zonal wall
+    lakes          all land but a one-cell lake, a 1 x 4 lake, a 2 x 2 lake across the x seam and (not tripolar) one across the y seam
+    one_land_cell  all ocean but one cell at an odd column
+    all_land       zeros
+    on_the_cuts    rectangles whose edges fall on either side of the window cuts (BACKWARD_WINDOWS) and of the strip cuts `cuts`
+    fold           (tripolar only) land on the northernmost row: a run, a single cell, one of the middle pair, one of the end pair,
+                   and a 3-row block that touches the seam -- none of them mirrored
+
+    `tripolar=True` forces row 0 to land (the tripolar kinds refuse anything else) and is the only thing that does."""
+    ny, nx = shape
+    if ny < 24 or nx < 24:
+        raise ValueError(f"coastline: shape {shape} is smaller than 24 x 24")
+    if name not in COASTLINES:
+        raise KeyError(name)
+    if name == ("open_south" if tripolar else "fold"):
+        raise ValueError(f"coastline {name!r} is not defined for tripolar={tripolar}")
+    rng = Generator(PCG64(seed))
+    m = np.ones((ny, nx))
+    if name == "open_south":
+        m[ny // 2 - 2 : ny // 2 + 1, nx // 5 : 4 * nx // 5] = 0          # the mid-grid band
+        m[0, nx // 3 : nx // 3 + 3] = 0                                   # rows 0 and ny-1: wet but for two short, shifted runs
+        m[ny - 1, nx // 3 + 1 : nx // 3 + 6] = 0
+        for j0, h in ((ny // 4, 5), (ny - 2, 2), (0, 1)):                 # blocks across the x seam; the second and third also meet in y
+            m[j0 : j0 + h, nx - 3 :] = 0
+            m[j0 : j0 + h, :2] = 0
+        for _ in range(6):                                                # a few seeded one-cell islands, rows 0 and ny-1 included
+            m[int(rng.integers(0, ny)), int(rng.integers(3, nx - 3))] = 0
+        jj = rng.integers(0, nx, 2)
+        m[0, jj[0]] = m[ny - 1, jj[0]] = 1                                # (never close the y seam in this column)
+    elif name == "speckle":
+        m = (rng.random((ny, nx)) >= 0.35).astype(np.float64)
+    elif name == "checker":
+        m = ((np.arange(ny)[:, None] + np.arange(nx)[None, :]) % 2).astype(np.float64)
+    elif name == "channels":
+        m[:, 5::11] = 0
+        m[6::13, :] = 1                                                   # the straits
+        m[ny // 2 + 1, :] = 0                                             # the zonal wall (the meridional walls cross it)
+        m[ny // 2 + 1, 3::17] = 1
+    elif name == "lakes":
+        m[:] = 0
+        m[ny // 3, (nx // 3) | 1] = 1
+        m[2 * ny // 3, ((nx // 2) | 1) : ((nx // 2) | 1) + 4] = 1
+        m[ny // 2 : ny // 2 + 2, nx - 1] = m[ny // 2 : ny // 2 + 2, 0] = 1
+        if not tripolar:
+            m[ny - 1, nx // 4 + 1 : nx // 4 + 3] = m[0, nx // 4 + 1 : nx // 4 + 3] = 1
+    elif name == "one_land_cell":
+        m[ny // 2, (nx // 2) | 1] = 0
+    elif name == "all_land":
+        m[:] = 0
+    elif name == "on_the_cuts":
+        band = 0
+
+        def rows_of(k):                       # row bands of three, spread over the grid (they may meet on small grids)
+            j0 = 2 + (7 * k) % (ny - 6)
+            return slice(j0, j0 + 3)
+
+        for wi in BACKWARD_WINDOWS:
+            if wi + 4 >= nx:
+                continue
+            for i0, i1 in ((wi - 4, wi), (wi, wi + 3), (wi + 1, wi + 4), (wi - 3, wi + 1)):
+                m[rows_of(band), i0:i1] = 0
+                band += 1
+        col = 0
+        for h in cuts:
+            for hh in range(h, ny - 4, h):
+                for j0, j1 in ((hh - 3, hh), (hh, hh + 3), (hh + 1, hh + 4), (hh - 2, hh + 1)):
+                    i0 = 3 + (9 * col) % (nx - 10)
+                    m[j0:j1, i0 : i0 + 5] = 0
+                    col += 1
+    elif name == "fold":
+        m[ny - 1, 5:9] = 0
+        m[ny - 1, nx - 1 - 20] = 0
+        m[ny - 1, nx // 2 - 1] = 0
+        m[ny - 1, 0] = 0
+        m[ny - 3 :, nx // 4 : nx // 4 + 5] = 0
+        for _ in range(8):                                                # seeded cells one and two rows below the seam
+            m[ny - 2 - int(rng.integers(0, 2)), int(rng.integers(0, nx))] = 0
+    if tripolar:
+        m[0, :] = 0
+    return m
+
+
+def mixed_words(mask, vec):
+    """Fraction of the aligned words of `vec` cells (along x; a ragged last word is left out) that hold both land and water."""
+    ny, nx = mask.shape
+    w = mask[:, : nx - nx % vec].reshape(ny, -1, vec).sum(axis=-1)
+    return float(((w > 0) & (w < vec)).mean())
+
+
+def closed_in_cells(mask):
+    """Wet cells of a periodic mask whose four neighbours are all land."""
+    n = sum(np.roll(mask, s, axis=a) for a in (-2, -1) for s in (1, -1))
+    return (mask == 1) & (n == 0)
+
+
+def kappa_with_zeros(shape, seed_w=11, seed_s=12):
+    """(kappa_w, kappa_s) for IRREGULAR_WITH_LAND: `smooth_kappa` with a rectangular patch of exact zeros in kappa_w and one row of
+    exact zeros in kappa_s -- wet cells closed in by kappa alone; the patch sits away from both planes' maxima (which stay exactly 1)."""
+    ny, nx = shape
+    kw, ks = smooth_kappa(shape, seed_w), smooth_kappa(shape, seed_s)
+    jw, iw = np.unravel_index(np.argmax(kw), kw.shape)
+    j0, i0 = (jw + ny // 2) % (ny - 6), (iw + nx // 2) % (nx - 9)
+    kw[j0 : j0 + 6, i0 : i0 + 9] = 0.0
+    js = (np.unravel_index(np.argmax(ks), ks.shape)[0] + ny // 3) % ny
+    ks[js, :] = 0.0
+    assert kw.max() == 1.0 and ks.max() == 1.0
+    return kw, ks
+
+
+def cgrid_coast_vars(name, shape, seed=0, independent_q=False):
+    """The VECTOR_C_GRID recipe of the coastline sweep: wet_mask_t = coastline(name), wet_mask_q = 1 where all four surrounding
+    t-cells (j, i), (j+1, i), (j, i+1), (j+1, i+1), periodic, are wet -- or, `independent_q`, a speckle of its own seed --
+    kappa_iso = smooth_kappa(13), kappa_aniso = 0.5 smooth_kappa(14); the metrics are vector_grid_vars'."""
+    gv = dict(vector_grid_vars("VECTOR_C_GRID", shape))
+    t = coastline(name, shape, seed)
+    if independent_q:
+        q = coastline("speckle", shape, seed + 1000)
+    else:
+        q = t * np.roll(t, -1, axis=0) * np.roll(t, -1, axis=1) * np.roll(np.roll(t, -1, axis=0), -1, axis=1)
+    gv["wet_mask_t"], gv["wet_mask_q"] = t, q
+    gv["kappa_iso"] = smooth_kappa(shape, 13)
+    gv["kappa_aniso"] = 0.5 * smooth_kappa(shape, 14)
+    return {k: gv[k] for k in FIXTURE_ARG_ORDER["VECTOR_C_GRID"]}
+
+
+LAND_TREATMENTS = ("nan", "finite", "mixed")
+
+
+def treat_land(field, wet, how, seed=0):
+    """Values on land of a field (any leading dims over a 2-D `wet`): `nan` on all land, `finite` (the field's own values) on all land,
+    `mixed`: NaN on a seeded half of the land plus three NaN in wet cells (per leading index the same cells)."""
+    if how == "finite":
+        return field.copy()
+    land = np.broadcast_to(wet == 0, field.shape)
+    if how == "nan":
+        return np.where(land, np.nan, field)
+    if how != "mixed":
+        raise KeyError(how)
+    rng = Generator(PCG64(seed))
+    half = rng.random(wet.shape) < 0.5
+    out = np.where(land & half, np.nan, field)
+    jj, ii = np.nonzero(wet)
+    if jj.size:
+        for k in rng.integers(0, jj.size, 3):
+            out[..., jj[k], ii[k]] = np.nan
+    return out

@@ -19,6 +19,10 @@ Outputs (committed):
   reference_gridbatched.npz (`--gridbatched`) grid variables with a leading level dim (wet_mask(z, y, x), kappa(z, y, x), ...)
                            against fields of shape (2, z, y, x): L(f) and the Gaussian filter from the imported reference.
 
+  reference_coastlines.npz, reference_coastlines_lap.npz (`--coastlines`) every land kind x every coastline of
+                           gcm_filters_amd.testing.COASTLINES (and two C-grid mask variants) at 40 x 64: the 24-step Gaussian filter
+                           and L(f) from the imported reference, in three treatments of the values on land.
+
 `--out DIR` writes into DIR instead of this directory (to check that the committed files regenerate).
 
 No reference source text is copied anywhere: only numbers leave this script.
@@ -269,6 +273,75 @@ def make_gridbatched(rf, rk, outdir):
     print("reference_gridbatched.npz:", len(out), "arrays")
 
 
+# ------------------------------------------------------------------------------------------------
+# coastlines the fixture mask never draws: reference_coastlines.npz -- case builder shared with the tests
+# ------------------------------------------------------------------------------------------------
+COAST_LAND_GRIDS = ["REGULAR_WITH_LAND", "REGULAR_WITH_LAND_AREA_WEIGHTED", "IRREGULAR_WITH_LAND", "MOM5U", "MOM5T",
+                    "TRIPOLAR_REGULAR_WITH_LAND_AREA_WEIGHTED", "TRIPOLAR_POP_WITH_LAND"]
+COAST_FILES = {"gauss": "reference_coastlines.npz", "lap": "reference_coastlines_lap.npz"}
+
+
+def coast_case_names():
+    """`grid/coastline[/variant]`: every land kind x every coastline defined for it, IRREGULAR_WITH_LAND with kappa zeros, and the two
+    C-grid mask variants.  A case's position in this list seeds its coastline and picks its land treatment."""
+    sys.path.insert(0, REPO)
+    from gcm_filters_amd import testing as T
+
+    names = [f"{g}/{c}" for g in COAST_LAND_GRIDS for c in T.coastline_names(g.startswith("TRIPOLAR"))]
+    names += ["IRREGULAR_WITH_LAND/speckle/kappa", "IRREGULAR_WITH_LAND/one_land_cell/kappa"]
+    names += ["VECTOR_C_GRID/speckle/derived_q", "VECTOR_C_GRID/channels/independent_q"]
+    return names
+
+
+def build_coast_case(name: str, shape=SMALL):
+    """(grid, fields, grid_vars, filter kwargs) of a coastline case: the seeded field of scalar_case / vector_case, land treated as
+    NaN on all land / finite on all land / NaN on half the land and in three wet cells, cycling over the cases (the C-grid, whose
+    stencil does not mask its input, keeps finite values)."""
+    sys.path.insert(0, REPO)
+    from gcm_filters_amd import testing as T
+
+    k = coast_case_names().index(name)
+    parts = name.split("/")
+    grid, coast = parts[0], parts[1]
+    variant = parts[2] if len(parts) > 2 else ""
+    if grid == "VECTOR_C_GRID":
+        fields, _ = T.vector_case(grid, shape)
+        gv = T.cgrid_coast_vars(coast, shape, seed=k, independent_q=variant == "independent_q")
+    else:
+        f, gv = T.scalar_case(grid, shape)
+        gv["wet_mask"] = T.coastline(coast, shape, seed=k, tripolar=grid.startswith("TRIPOLAR"), cuts=(10,))
+        if variant == "kappa":
+            gv["kappa_w"], gv["kappa_s"] = T.kappa_with_zeros(shape)
+        fields = (T.treat_land(f, gv["wet_mask"], T.LAND_TREATMENTS[k % 3], seed=k),)
+    dimensional = grid in ("IRREGULAR_WITH_LAND", "MOM5U", "MOM5T", "TRIPOLAR_POP_WITH_LAND", "VECTOR_C_GRID")
+    dx_min = T.grid_dx_min(grid, gv) if dimensional else 1.0
+    return grid, fields, gv, dict(filter_scale=8.0 * dx_min, dx_min=dx_min, filter_shape="GAUSSIAN", n_steps=24)
+
+
+def make_coastlines(rf, rk, outdir):
+    """The reference's Laplacian and 24-step Gaussian filter on every coastline case.  One file per kind of array, 1.7 MB together:
+    this repository takes no new file above 1 MiB (the larger fixtures beside them are older than that rule), and 60 planes of either
+    kind compress to 0.96 / 0.74 MB."""
+    out = {"gauss": {}, "lap": {}}
+    for name in coast_case_names():
+        grid, fields, gv, fk = build_coast_case(name)
+        cls = rk.ALL_KERNELS[rk.GridType[grid]]
+        args = [gv[k] for k in cls.required_grid_args()]
+        with np.errstate(all="ignore"):
+            res = cls(**gv)(*fields)
+            out["lap"][name] = np.stack(res) if isinstance(res, tuple) else np.asarray(res)
+            spec = rf._compute_filter_spec(fk["filter_scale"], fk["dx_min"], rf.FilterShape[fk["filter_shape"]], np.pi, 2, fk["n_steps"])
+            if len(fields) == 2:
+                res = np.stack(rf._create_filter_func_vec(spec, cls)(*fields, *args))
+            else:
+                res = np.asarray(rf._create_filter_func(spec, cls)(*fields, *args))
+        out["gauss"][name] = res
+    for kind, fname in COAST_FILES.items():
+        np.savez_compressed(os.path.join(outdir, fname), **out[kind])
+        print(f"{fname}: {len(out[kind])} arrays, {sum(v.nbytes for v in out[kind].values()) // 1024} KiB raw, "
+              f"{os.path.getsize(os.path.join(outdir, fname)) // 1024} KiB on disk")
+
+
 # full-size cases: key -> (BASELINE config, filter scale in dx_min units (0 = the config's own), NaN on land?[, options])
 # options: level = the vertical level of config 5 (its fields are seeded per level); f32 = field AND grid variables cast to float32
 # before the reference sees them (its f32-input path: f32 recurrence, f64 running sum and result, SURVEY 8a A2)
@@ -342,6 +415,9 @@ def main():
         return 0
     if "--gridbatched" in sys.argv:
         make_gridbatched(rf, rk, HERE)
+        return 0
+    if "--coastlines" in sys.argv:
+        make_coastlines(rf, rk, HERE)
         return 0
 
     # 1. the reference's own goldens

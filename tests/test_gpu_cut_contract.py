@@ -46,8 +46,10 @@ PLANS = {
 }
 
 
-def _grid(grid, shape):
+def _grid(grid, shape, coast=""):
     f, gv = T.scalar_case(grid, shape)
+    if coast:       # gcm_filters_amd.testing.coastline instead of the fixture mask
+        gv["wet_mask"] = T.coastline(coast, shape, seed=33)
     return f, gv, ALL_KERNELS[GridType[grid]](**gv)
 
 
@@ -134,10 +136,10 @@ def _filter(grid, gv, n):
 
 
 @functools.lru_cache(maxsize=None)
-def _case(grid, shape, n):
+def _case(grid, shape, n, coast=""):
     """One field with NaN on land and in one wet cell, its filter, and the oracle's answer.  The fields of a batch are this one scaled by
     1 + 0.1 i: the oracle's answer scales with them, and a field that read another field's values would be off by far more than 1e-12."""
-    f, gv, _ = _grid(grid, shape)
+    f, gv, _ = _grid(grid, shape, coast)
     land = gv["wet_mask"] == 0
     f = np.where(land, np.nan, f)
     wet = np.argwhere(~land)
@@ -317,14 +319,18 @@ def test_refused_depths_leave_no_result():
 
 @pytest.mark.parametrize("n_steps", [63, 65])
 @pytest.mark.parametrize("grid,exchange,self_ring", [("TRIPOLAR_POP_WITH_LAND", "auto", False), ("TRIPOLAR_POP_WITH_LAND", "p2p", False),
-                                                     ("IRREGULAR_WITH_LAND", "p2p", True), ("IRREGULAR_WITH_LAND", "native", True)])
+                                                     ("IRREGULAR_WITH_LAND", "p2p", True), ("IRREGULAR_WITH_LAND", "native", True),
+                                                     ("IRREGULAR_WITH_LAND:open_south", "native", True)])
 def test_slab_filter_of_one_rank(grid, exchange, self_ring, n_steps):
     """SlabFilter(rank=0, world=1) cuts a whole grid as gcmf_apply does for the batch in hand (the tripolar grid's nines depend on it) and a
     ring of one rank as the slab drivers do (nines by option "slab_nines"); either way Filter.apply's bits.  (A tripolar grid is not periodic
-    in y: no ring of one there.)"""
+    in y: no ring of one there.)  With the fixture mask the face a ring of one exchanges across is closed (row 0 is land); the `open_south`
+    coastline (gcm_filters_amd.testing.coastline) keeps it live."""
     from gcm_filters_amd.distributed import SlabFilter
     shape = (200, 392)
-    f, gv, flt, p, c, want = _case(grid, shape, n_steps)
+    grid, _, coast = grid.partition(":")
+    f, gv, flt, p, c, want = _case(grid, shape, n_steps, coast)
+    assert not coast or (gv["wet_mask"][0] * gv["wet_mask"][-1]).any()
     dx = T.grid_dx_min(grid, gv)
     fk = dict(filter_scale=4.0 * dx, dx_min=dx, n_steps=n_steps, filter_shape=FilterShape.TAPER)
     with warnings.catch_warnings():

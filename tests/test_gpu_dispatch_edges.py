@@ -24,6 +24,7 @@ from __future__ import annotations
 import math
 import re
 import warnings
+import zlib
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -59,6 +60,9 @@ class Case:
     scheme: str = "forward"             # f32 error policy: forward | scalar_backward | cgrid_backward | bgrid_backward
     reaches: Tuple = ()                 # kernel names (without "gcmf::") this case is the inventory's witness for
     land: bool = True                   # False: an all-ocean wet_mask (no land fix-up, so no nx % 4 condition on the backward evaluation)
+    coast: str = ""                     # a coastline of testing.COASTLINES instead of the fixture mask ("name", "name:kappa": with
+                                        # testing.kappa_with_zeros, C-grid "name:indq": an independent wet_mask_q); tests/test_gpu_coastlines.py
+    land_values: str = "nan"            # the values on land of a `coast` case: testing.LAND_TREATMENTS
 
     def kernels(self):
         """The kernels this case reaches: `reaches`, else the one its regex names (a regex over several names names none)."""
@@ -286,7 +290,30 @@ _resident_family()
 # ------------------------------------------------------------------------------------------------------------------------------
 # running a case
 # ------------------------------------------------------------------------------------------------------------------------------
+def _coast_inputs(c: Case):
+    """Inputs of a case with a coastline: the mask (and kappa / the C-grid's second mask) from gcm_filters_amd.testing, seeded by the
+    case's id; strip cuts for `on_the_cuts` from the case's strip_rows."""
+    name, _, variant = c.coast.partition(":")
+    seed = zlib.crc32(c.id.encode()) % 10007
+    if c.grid == "VECTOR_C_GRID":
+        gv = T.cgrid_coast_vars(name, c.shape, seed, independent_q=variant == "indq")
+        fields = [np.stack([T.random_field(c.shape, s + 2 * l) for l in range(c.nb)]) if c.nb else T.random_field(c.shape, s)
+                  for s in (42, 43)]
+    else:
+        gv = T.scalar_grid_vars(c.grid, c.shape)
+        cuts = tuple(v for k, v in c.tuning if k == "strip_rows") + tuple(v for k, v in c.geom if k == "H")
+        gv["wet_mask"] = T.coastline(name, c.shape, seed, tripolar=c.grid.startswith("TRIPOLAR"), cuts=cuts)
+        if variant == "kappa":
+            gv["kappa_w"], gv["kappa_s"] = T.kappa_with_zeros(c.shape)
+        f = np.stack([T.random_field(c.shape, 100 + l) for l in range(c.nb)]) if c.nb else T.random_field(c.shape, 100)
+        fields = [T.treat_land(f, gv["wet_mask"], c.land_values, seed)]
+    gv = {k: v.astype(c.dt) for k, v in gv.items()}
+    return [x.astype(c.dt) for x in fields], gv
+
+
 def _inputs(c: Case):
+    if c.coast:
+        return _coast_inputs(c)
     rng_shape = ((c.nb,) if c.nb else ()) + c.shape
     if c.grid in T.VECTOR_GRIDS:
         gv = T.vector_grid_vars(c.grid, c.shape)

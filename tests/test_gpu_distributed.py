@@ -41,6 +41,9 @@ CASES = [
     # exactly 2 S rows below the seam (k_fold_band's input rows; found by tools/fuzz_slabs.py -- the row-range check was one row too strict)
     ("TRIPOLAR_POP_WITH_LAND", (28, 44), 16, 5, "f4b", 19),
     ("TRIPOLAR_POP_WITH_LAND", (40, 64), 16, 2, "f8", 24),
+    # a sixth slot that is a dict: extras by name.  coast = a coastline of gcm_filters_amd.testing.coastline: rows 0 and ny-1 wet, so the
+    # wrap between the last and the first rank carries flux (the fixture mask closes it: row 0 is land)
+    ("IRREGULAR_WITH_LAND", (50, 66), 4, 2, "f8", dict(coast="open_south")),
 ]
 
 
@@ -56,6 +59,7 @@ CASES_WIDE = [
     ("REGULAR_WITH_LAND", (83, 64), 5, 2, "f4b"),
     ("VECTOR_C_GRID", (80, 64), 4, 4, "f4"),
     ("IRREGULAR_WITH_LAND", (350, 64), 10, 2, "f8", 27),    # nine levels per launch on slabs of 70 rows
+    ("IRREGULAR_WITH_LAND", (90, 64), 8, 2, "f8", dict(coast="open_south")),
 ]
 
 
@@ -81,14 +85,20 @@ def _worker(rank, world, port, q, exchange="auto"):
     res = {}
     try:
         for grid, shape, halo, nbatch, dt, *rest in (CASES_WIDE if world == WIDE else CASES):
+            extra = rest[0] if rest and isinstance(rest[0], dict) else {}     # (a plain sixth slot is n_steps)
+            coast = extra.get("coast", "")
+            rest = [extra["n_steps"]] if "n_steps" in extra else [n for n in rest if not isinstance(n, dict)]
+            name, back32 = f"{grid}-{shape}-h{halo}-b{nbatch}-{dt}" + (f"-{coast}" if coast else ""), dt == "f4b"
             if rest and world not in (2, WIDE):
-                res[f"{grid}-{shape}-h{halo}-b{nbatch}-{dt}"] = (0.0, 0.0)   # (a two-rank geometry)
+                res[name] = (0.0, 0.0)   # (a two-rank geometry)
                 continue
-            name, back32 = f"{grid}-{shape}-h{halo}-b{nbatch}-{dt}", dt == "f4b"
             dt = "f4" if back32 else dt
             ev = "backward" if back32 else "auto"     # (f32 scalar fields: backward only when asked for, round 5)
             vec = grid in T.VECTOR_GRIDS
             gv = T.vector_grid_vars(grid, shape) if vec else T.scalar_grid_vars(grid, shape)
+            if coast:
+                gv["wet_mask"] = T.coastline(coast, shape, seed=55)
+                assert (gv["wet_mask"][0] * gv["wet_mask"][-1]).any()
             fields = [np.stack([T.random_field(shape, 7 + 10 * c + b) for b in range(nbatch)]) for c in range(2 if vec else 1)]
             nanland = (not vec) and "wet_mask" in gv and nbatch >= 2   # ocean-like input in the last batch entry
             if nanland:

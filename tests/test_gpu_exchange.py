@@ -44,14 +44,33 @@ CASES = [
     ("VECTOR_C_GRID", (128, 64), 4, 8, "f4"),                   # 16 blocks per state: the packed message path
     ("VECTOR_B_GRID", (120, 64), 3, 2, "f8"),
 ]
+# Coastlines ("GRID:coastline", gcm_filters_amd.testing.coastline): with the fixture mask row 0 is land, so the only boundary a ring of one
+# rank exchanges across is a closed face and garbage ghost rows would go unnoticed on every land kind.  `open_south` and a speckle whose
+# row 0 is opened keep that face live; halo 8 and a halo (5) that does not divide n_steps - 1 = 6.
+CASES += [(f"{grid}:{coast}", shape, halo, nbatch, dt)
+          for grid, shape, nbatch, dt in (("REGULAR_WITH_LAND", (120, 128), 2, "f8"), ("IRREGULAR_WITH_LAND", (130, 132), 1, "f8"),
+                                          ("MOM5U", (96, 64), 3, "f4"))
+          for coast in ("open_south", "speckle_open") for halo in (8, 5)]
+
+
+def coast_mask(coast, shape):
+    """`speckle_open`: the speckle with its southernmost row opened."""
+    m = T.coastline(coast.replace("_open", ""), shape, seed=21)
+    if coast.endswith("_open"):
+        m[0, :] = 1
+    return m
 
 
 @pytest.mark.parametrize("exchange", ["native", "p2p"])
 @pytest.mark.parametrize("grid,shape,halo,nbatch,dt", CASES)
 def test_self_ring_native_exchange_equals_single_domain(grid, shape, halo, nbatch, dt, exchange):
     """exchange="p2p": the same ring of one rank through the mailbox / flag kernels of csrc/gcmf_p2p.hip (its neighbours' blocks are its own)."""
+    grid, _, coast = grid.partition(":")
     vec = grid in T.VECTOR_GRIDS
     gv = T.vector_grid_vars(grid, shape) if vec else T.scalar_grid_vars(grid, shape)
+    if coast:
+        gv["wet_mask"] = coast_mask(coast, shape)
+        assert (gv["wet_mask"][0] * gv["wet_mask"][-1]).any()        # a live face across the y seam
     fields = [np.stack([T.random_field(shape, 7 + 10 * c + b) for b in range(nbatch)]) for c in range(2 if vec else 1)]
     if (not vec) and "wet_mask" in gv and nbatch >= 2:
         fields[0][-1] = np.where(gv["wet_mask"] == 0, np.nan, fields[0][-1])
@@ -92,3 +111,19 @@ def test_self_ring_native_exchange_equals_single_domain(grid, shape, halo, nbatc
         assert np.array_equal(np.isnan(g), np.isnan(o))
         ok = ~np.isnan(o)
         assert np.abs(g[ok] - o[ok]).max() <= (1e-5 if dt == "f4" else 1e-13) * np.abs(o[ok]).max()
+    if coast:
+        # and the oracle: 1e-12 in f64; f32 state (the forward scheme) within 1.5 x the error of the oracle's own f32 path + 1e-6
+        # (tests/test_gpu_dispatch_edges.py errors())
+        spec = O.make_spec(fk["filter_scale"], dx, "GAUSSIAN")
+        assert spec.n_steps == sf.n_steps and (sf.n_steps - 1) % 5 != 0
+        gv64 = {k: v.astype("f8") for k, v in gv.items()}
+        with np.errstate(all="ignore"):
+            truth = O.filter_func(spec, grid, fields[0].astype("f8"), gv64)
+            ref32 = O.filter_func(spec, grid, fields[0], gv) if dt == "f4" else None
+        assert np.array_equal(np.isnan(got[0]), np.isnan(truth))
+        ok = ~np.isnan(truth)
+        scale = np.abs(truth[ok]).max()
+        e = np.abs(got[0][ok] - truth[ok]).max() / scale
+        bound = 1e-12 if dt == "f8" else 1.5 * np.abs(ref32[ok] - truth[ok]).max() / scale + 1e-6
+        print(f"{grid}:{coast} halo {halo} {exchange}: error against the oracle {e:.3e} (bound {bound:.3e})")
+        assert e <= bound, (grid, coast, halo, exchange, e, bound)

@@ -134,13 +134,18 @@ def test_default_policy_leaves_tripolar_and_larger_grids_on_the_strip_marching_l
 
 @pytest.mark.parametrize("grid,shape,halo,exchange", [("IRREGULAR_WITH_LAND", (300, 360), 32, "native"), ("IRREGULAR_WITH_LAND", (130, 132), 8, "p2p"),
                                                       ("REGULAR_WITH_LAND", (120, 128), 16, "p2p"), ("REGULAR", (96, 128), 12, "native"),
-                                                      ("MOM5U", (96, 64), 10, "p2p")])
+                                                      ("MOM5U", (96, 64), 10, "p2p"),
+                                                      ("IRREGULAR_WITH_LAND:open_south", (130, 132), 8, "native")])
 def test_slab_driver_runs_resident_between_exchanges(grid, shape, halo, exchange, monkeypatch):
     monkeypatch.setenv("GCMF_RESIDENT", "1")
     """A ring of one rank (ghost rows exchanged with itself: the 8-GPU choreography on one GPU): gcmf_slab_apply_backward runs every
     stretch between two exchanges as ONE resident launch; same bits as its strip-marching launches and as the single-domain filter."""
     from gcm_filters_amd.distributed import SlabFilter
+    grid, _, coast = grid.partition(":")
     f, gv = T.scalar_case(grid, shape)
+    if coast:       # (the fixture mask closes the only face a ring of one exchanges across: row 0 is land)
+        gv["wet_mask"] = T.coastline(coast, shape, seed=44)
+        assert (gv["wet_mask"][0] * gv["wet_mask"][-1]).any()
     if "wet_mask" in gv:
         f = np.where(gv["wet_mask"] == 0, np.nan, f)
     dx = T.grid_dx_min(grid, gv) if O.DIMENSIONAL[grid] else 1.0

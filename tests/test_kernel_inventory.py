@@ -13,7 +13,8 @@ ALLOWLIST = {
     "k_ringc6": "never instantiated (DESIGN_HISTORY.md); its note_kernel call site is unreachable",
     # plan-time precompute: run by every plan creation; covered by tests/test_gpu_parity.py::test_kernel_vs_reference_zarr
     "k_pre_mask": "plan precompute; tests/test_gpu_parity.py::test_kernel_vs_reference_zarr",
-    "k_pre_isolated": "plan precompute; tests/test_gpu_parity.py::test_kernel_vs_reference_zarr",
+    "k_pre_isolated": "plan precompute; tests/test_gpu_parity.py::test_kernel_vs_reference_zarr; cells cut off from the sea (lakes, a checkerboard, "
+                      "kappa zeros, land on the tripole seam): tests/test_gpu_coastlines.py",
     "k_count_land": "plan precompute; tests/test_gpu_parity.py::test_kernel_vs_reference_zarr",
     "k_pre_irregular": "plan precompute; tests/test_gpu_parity.py::test_kernel_vs_reference_zarr",
     "k_pre_pop": "plan precompute; tests/test_gpu_parity.py::test_kernel_vs_reference_zarr",
@@ -24,9 +25,12 @@ ALLOWLIST = {
     # helpers that run beside the recurrence kernels; Plan.last_kernel() names only the recurrence kernel
     "k_prepare": "area-weighted prepare step, not named by last_kernel; tests/test_gpu_parity.py::test_kernel_vs_reference_zarr",
     "k_fold_band": "tripole seam band beside / after the blocked launch, not named by last_kernel; "
-                   "tests/test_gpu_zip.py::test_the_seam_band_after_or_beside_the_launch",
-    "k_land_fix": "land fix-up after the backward evaluation, not named by last_kernel; tests/test_gpu_parity.py::test_land_kept_out_of_the_state",
-    "k_zero_land": "zeroes land in the state, not named by last_kernel; tests/test_gpu_parity.py::test_land_kept_out_of_the_state",
+                   "tests/test_gpu_zip.py::test_the_seam_band_after_or_beside_the_launch; with land on the seam: "
+                   "tests/test_gpu_coastlines.py (tripolar-band-*)",
+    "k_land_fix": "land fix-up after the backward evaluation, not named by last_kernel; tests/test_gpu_parity.py::test_land_kept_out_of_the_state; "
+                  "words of mixed land and water, finite and NaN values on land: tests/test_gpu_coastlines.py",
+    "k_zero_land": "zeroes land in the state, not named by last_kernel; tests/test_gpu_parity.py::test_land_kept_out_of_the_state; "
+                   "words of mixed land and water: tests/test_gpu_coastlines.py",
     # multi-rank halo exchange
     "k_pack_rows": "halo exchange packing; tests/test_gpu_exchange.py::test_raw_exchange_fills_ghost_rows_direct_and_packed",
     "k_p2p_post": "peer-to-peer halo exchange; tests/test_gpu_distributed.py::test_slabs_on_one_gpu_match_single_domain",

@@ -152,3 +152,30 @@ def test_oracle_grid_variables_with_leading_dims(grid):
         else:
             got = O.filter_func(spec, grid, fields[0], gv)
     assert np.array_equal(got, want_f)
+
+
+@pytest.mark.parametrize("name", MG.coast_case_names())
+def test_oracle_on_coastlines_the_fixture_never_draws(name):
+    """Speckled, checkerboard, channel, lake, open-south, one-cell, all-land, on-the-cuts and land-on-the-fold masks (testing.COASTLINES)
+    on every land kind, kappa zeros, and a C-grid whose wet_mask_q differs from wet_mask_t: L(f) and the 24-step Gaussian filter,
+    bit-equal to the imported reference (make_golden.py --coastlines).  This is what licenses the oracle as the truth of
+    tests/test_gpu_coastlines.py."""
+    import os
+    want = {}
+    for kind, fname in MG.COAST_FILES.items():
+        with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", fname)) as z:
+            want[kind] = z[name]
+    grid, fields, gv, fk = MG.build_coast_case(name)
+    with np.errstate(all="ignore"):
+        lap = _stack(O.make_laplacian(grid, gv)(*fields))
+        spec = O.make_spec(fk["filter_scale"], fk["dx_min"], fk["filter_shape"], n_steps=fk["n_steps"])
+        assert spec.n_steps == 24
+        if len(fields) == 2:
+            got = np.stack(O.filter_func_vec(spec, grid, *fields, gv))
+        else:
+            got = O.filter_func(spec, grid, fields[0], gv)
+    assert lap.dtype == want["lap"].dtype and got.dtype == want["gauss"].dtype
+    assert np.array_equal(lap, want["lap"], equal_nan=True)
+    assert np.array_equal(got, want["gauss"], equal_nan=True)
+    if "all_land" not in name:
+        assert np.isfinite(got).any(), "a case must not reduce to a NaN pattern"

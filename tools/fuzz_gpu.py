@@ -8,6 +8,7 @@ from gcm_filters_amd import Filter, FilterShape, GridType, testing as T
 from gcm_filters_amd.kernels import clear_plan_cache
 from oracle import gcmf_oracle as O
 
+# --coast: draw the wet mask from gcm_filters_amd.testing.COASTLINES (grids of 24 x 24 and more) instead of the fixture mask; off by default
 # --eval auto|reference|backward: the Filter's evaluation order (default auto; "backward" = the all-f32 backward kernels for f32 scalar / B-grid fields)
 EVAL = sys.argv[sys.argv.index("--eval") + 1] if "--eval" in sys.argv else "auto"
 rng = np.random.default_rng(int(sys.argv[1]) if len(sys.argv) > 1 else 0)
@@ -41,6 +42,15 @@ for it in range(ncase):
     if "--cgrid" in sys.argv or "--bgrid" in sys.argv:
         nb = (int(rng.choice([1, 3, 4, 8, 12, 41])),)
     gv = T.vector_grid_vars(grid, shape) if vec else T.scalar_grid_vars(grid, shape)
+    if "--coast" in sys.argv and min(shape) >= 24:
+        # the wet mask from testing.COASTLINES (seeded by the case) instead of the fixture's: a live y seam, mixed words, lakes, land on the fold
+        tri = grid.startswith("TRIPOLAR")
+        names = T.coastline_names(tri)
+        coast, cseed = names[int(rng.integers(len(names)))], int(rng.integers(1 << 30))
+        if "wet_mask" in gv:
+            gv["wet_mask"] = T.coastline(coast, shape, cseed, tripolar=tri, cuts=(int(rng.integers(5, 40)),))
+        elif grid == "VECTOR_C_GRID":
+            gv = T.cgrid_coast_vars(coast, shape, cseed, independent_q=bool(rng.integers(2)))
     ncomp = 2 if vec else 1
     fields = [rng.random(nb + shape) for _ in range(ncomp)]
     if not vec and "wet_mask" in gv and rng.random() < 0.5:
