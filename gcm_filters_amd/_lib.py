@@ -459,6 +459,11 @@ class Plan:
             out[k] = v if "x" in v else int(v)
         return out
 
+    def last_wet_units(self) -> int:
+        """Pairs of strips of the kernel last_kernel() named if k_ringcz cut them from the wet rows of each window (option "wet_rows"; 0: a grid
+        that is all land), -1 if it took the even cut or another kernel ran."""
+        return int(self.last_kernel_geometry().get("units", -1))
+
     def set_tuning(self, rows_per_wave: int = 0, xcd_remap: int = -1, multi_s: int = 0, strip_rows: int = 0,
                    prefetch_rows: int = 0, clenshaw: int = -1, zigzag: int = -1):
         """`clenshaw` (needs multi_s > 0): backward evaluation 0 = off, 1 = flux kinds, 2 = all scalar kinds; -1 keeps it.
@@ -474,7 +479,7 @@ class Plan:
 
     def set_option(self, name: str, value: int):
         """Named per-plan switch (gcmf_set_option, include/gcmf.h): "cgrid_ring", "cgrid_ring_smax", "cgrid_ring_hmax", "cgrid_ring_ncarry", "pack_batch",
-        "single_launch", "ringc9", "ringc_zip", "ringc_smax", "band_seq_cells", "zip_fold", "slab_nines", "clenshaw_f32", "ring_flux_f32"."""
+        "single_launch", "ringc9", "ringc_zip", "ringc_smax", "band_seq_cells", "zip_fold", "slab_nines", "clenshaw_f32", "ring_flux_f32", "wet_rows"."""
         check(load().gcmf_set_option(self._h, name.encode(), int(value)))
 
 

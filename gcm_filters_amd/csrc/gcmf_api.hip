@@ -52,6 +52,7 @@ static int ensure_work(gcmf_plan *pl, size_t bytes) {
   }
   GCMF_HIP(hipMalloc(&pl->work, bytes));
   pl->work_bytes = bytes;
+  pl->pool_clean = false;   // (new planes hold anything)
   return GCMF_OK;
 }
 
@@ -546,10 +547,21 @@ static bool sched_single_launch(ApplyCtx &x) {
 // Backward (Clenshaw) evaluation, gcmf_ringc_impl.hpp: state (b_{k+1}, b_{k+2}) in a pool of four planes, the constant input read by
 // every launch, no fbar planes.  The first launch forms b_n = p[n] f as it loads f; level l = 1..n uses p[n - l]; the last launch
 // writes the result.  depths: clenshaw_cut's launches.
-static int sched_backward_scalar(ApplyCtx &x, const int *depths, int n_clen) {
+// was_clean: the pool's planes are finite wherever k_ringcz's wet-row tables leave them unwritten (gcmf_plan::pool_clean); launches of
+// a whole grid and a lone field may take such a table (wet_table, gcmf_ringc_zip.hip) and keep the planes that way -- the flux kinds'
+// backward kernels take f as zero on isolated cells, whose state is then +-0 at every level -- every other caller owns its planes.
+static int sched_backward_scalar(ApplyCtx &x, const int *depths, int n_clen, bool was_clean) {
   void *pool[4] = {x.A[0], x.B[0], x.Cb[0], x.Db[0]};
   const void *u = nullptr, *v = nullptr;
   int rc;
+  gcmf_plan *pl = x.pl;
+  struct WetNow {   // (cleared however the schedule leaves)
+    gcmf_plan *pl;
+    ~WetNow() { pl->wet_now = false; }
+  } wet_guard{pl};
+  pl->wet_now = pl->wet_rows > 0 && x.nbatch == 1 && !pl->mask_per_field && pl->full && !pl->g.fold && pl->kind == K_FLUX &&
+                pl->d.dtype == GCMF_F64 && pl->n_land > 0 && pl->pool_bytes > 0;
+  pl->pool_clean = pl->wet_now && was_clean;
   for (int q = 0, lvl = 1; q < n_clen; lvl += depths[q++]) {
     void *fr[2];
     free_planes(pool, 1, u, v, fr);
@@ -750,6 +762,8 @@ static int run_schedule(ApplyCtx &x, uint32_t flags, bool use_multi, bool use_vm
       return GCMF_ERR_HIP;
     }
   }
+  const bool was_clean = pl->pool_clean;   // (only sched_backward_scalar keeps the work planes finite on land)
+  pl->pool_clean = false;
   bool resident = false;
   int path = GCMF_PATH_STRIPS;
   if (n_clen > 0 && x.nbatch == 1 && !(flags & GCMF_NO_RESIDENT) && !pl->mask_per_field) {   // (the on-chip kernel reads the plan's own mask)
@@ -766,7 +780,7 @@ static int run_schedule(ApplyCtx &x, uint32_t flags, bool use_multi, bool use_vm
     if (resident)
       rc = sched_resident(x);
     else if ((flags & GCMF_NO_RESIDENT) || pl->mask_per_field || ringc_one_depth(pl, x.n_steps, x.nbatch) <= 0 || !sched_single_launch(x))
-      rc = sched_backward_scalar(x, depths, n_clen);
+      rc = sched_backward_scalar(x, depths, n_clen, was_clean);
     if (rc || pl->n_land == 0) return rc;
     // the isolated cells' own polynomial (forward recurrence, as the reference computes it)
     return land_fix_tail(pl, x.p, x.n_steps, x.c, x.din[0], x.dout[0], x.fb32, x.nbatch, x.s);
@@ -876,6 +890,12 @@ static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double 
   int rc = ensure_work(pl, per * pl->ncomp);
   if (rc || (rc = wait_for_work(pl, x.s))) return rc;
   char *w = (char *)pl->work;
+  // the four state planes of a scalar blocked schedule, one after the other: what a wet-row table launch zero-fills once (pool_clean)
+  void *pool_base = w + oA;
+  const size_t pool_bytes = (pl->ncomp == 1 && use_multi) ? 4 * szT : 0;
+  if (pool_base != pl->pool_base || pool_bytes != pl->pool_bytes) pl->pool_clean = false;
+  pl->pool_base = pool_base;
+  pl->pool_bytes = pool_bytes;
   x.F2 = w + oF2;
   for (int k = 0; k < pl->ncomp; ++k) {
     char *base = w + per * k;

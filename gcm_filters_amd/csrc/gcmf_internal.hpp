@@ -104,6 +104,20 @@ struct VecMultiArgs {
                          // the input f, p0 = p_n, pk[t] = coefficient of level t + 1, fb_out = the result (last launch)
 };
 
+// Strips cut from the wet rows of each window (k_ringcz, round 7; gcmf_ringc_zip.hip).  need[wx * rows + r]: row r of window wx holds a
+// cell that exchanges with a neighbour somewhere in the window's 128 columns (one profile per window width WI).
+struct WetProfile {
+  int WI = 0;
+  std::vector<uint8_t> need;
+};
+// The pairs of one launch geometry: units = (window, lo, mid, hi) on the device; dev == nullptr: this geometry keeps the even cut.
+struct WetTable {
+  int S = 0, row_lo = 0, row_hi = 0;
+  int64_t nbatch = 0;
+  void *dev = nullptr;
+  int nunits = 0, H = 0, nstrips = 0, march = 0;
+};
+
 }  // namespace gcmf
 
 struct gcmf_plan {
@@ -186,6 +200,22 @@ struct gcmf_plan {
   long long band_seq_cells = 3000000;   // tripolar plans: blocked launches over at most this many cells run k_fold_band AFTER themselves (its 1024-thread form), not beside (env GCMF_BAND_SEQ_CELLS; 0 = never)
   bool alone_now = true;  // (set by advance_multi for the blocked launch it issues: no k_fold_band waves will share its SIMDs)
   int zip_fold = 1;       // tripolar f64 flux plans, backward evaluation: k_ringcz advances the seam's rows itself (no k_fold_band); gcmf_set_option "zip_fold", env GCMF_ZIP_FOLD
+  // Whole f64 flux grids with land, a lone field (round 7): k_ringcz's strips are cut from the rows of each window that hold anything wet
+  // (wet_table, gcmf_ringc_zip.hip).  0 off, 1 where that marches at least 10 % fewer rows than the even cut, 2 whenever eligible;
+  // gcmf_set_option "wet_rows".  Cells no strip owns are never written, but they are read as ghost cells (against zero coefficients:
+  // harmless while finite), so the four state planes must be finite there: pool_clean says they are (zero-filled once, and the flux
+  // kinds' backward launches only ever write +-0 into isolated cells).  What can put a NaN / inf there: a new or regrown work buffer
+  // (anything), the one-launch-per-step schedule (k_scalar_step carries a NaN on land through every T_k), and calls whose work layout
+  // puts other planes where the pool lies (without the blocked schedules: fbar and the staged host input, NaN on land and all).  The
+  // blocked forward schedule zeroes land in its state too, but no schedule is trusted: every one other than sched_backward_scalar on
+  // an eligible call clears the flag, and so does a work buffer or layout other than the last call's.
+  int wet_rows = 1;
+  bool wet_now = false;         // this launch belongs to a gcmf_apply schedule that may take the table (sched_backward_scalar)
+  bool pool_clean = false;
+  void *pool_base = nullptr;    // the four state planes of the call that runs now (contiguous) ...
+  size_t pool_bytes = 0;        // ... 0: the call has no such pool
+  std::vector<gcmf::WetProfile> wet_prof;
+  std::vector<gcmf::WetTable> wet_tabs;
   int slab_nines = 0;     // row slabs of f64 flux grids without a tripole seam: nine levels per launch where that saves one (gcmf_set_option "slab_nines"; every rank or none)
   int ringc_smax = 0;     // backward scalar launches: at most this many levels each (5..8; 0 = the default cut: nine where offered, else eight); gcmf_set_option "ringc_smax"
   int ringc9 = 1;         // whole f64 flux-form grids without a tripole seam: up to NINE levels per k_ringc launch (env GCMF_RINGC9, gcmf_set_option "ringc9")
@@ -314,6 +344,9 @@ int launch_ringc_flux9(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);   // n
 int launch_ringc_flux_slab(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);
 int launch_ringc_zip(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);   // f64 flux plans without a tripole seam, short strips: pairs of strips zipped at a shared seam (k_ringcz, gcmf_ringc_zip.hip)
 int ringc_zip_march(const gcmf_plan *pl, const MultiArgs &a, int *pairs);
+// k_ringcz's pairs cut from the wet rows of each window (round 7): the table of this launch geometry (built once, cached on the plan), or
+// nullptr where the launch keeps the even cut (not eligible, the policy of option "wet_rows", or an error -- then *rc says which)
+const WetTable *wet_table(gcmf_plan *pl, const MultiArgs &a, hipStream_t s, int *rc);
 bool ringc_zip_fold_ok(const gcmf_plan *pl, const MultiArgs &a);   // can k_ringcz advance the tripole seam's rows of this launch itself?  // rows a k_ringcz launch would march (all rounds), 0 = not offered
 int launch_ringc_flux_slab_f32(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);   // flux plans without a tripole seam, short strips: early exits (k_ringcs)
 int launch_flux_multi2(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);

@@ -532,21 +532,30 @@ __global__ __launch_bounds__(256, 1) void k_ringcs(const MultiP<T, T> P) {
 // pairs of (almost) equal height; a pair is cut in the middle: the lower strip marches down the grid from the cut, the upper one up.  A
 // workgroup = the two pairs of two neighbouring windows (pair (2 bx + w / 2), member w % 2); a pair past the end idles through the barriers.
 // A non-finite value met by ANY wave of the workgroup sends all four through the nan_to_num march (they meet at its barriers).
-template <typename T, int S, bool FIRST, bool XE>
-__global__ __launch_bounds__(256, 1) void k_ringcz(const MultiP<T, T> P) {
+// TAB (round 7): the pairs come from the launch's table (MultiP::utab: strips cut from the rows of each window that hold anything wet,
+// wet_table in gcmf_ringc_zip.hip) -- a kernel of its own, k_ringcz<T, S, FIRST, XE, true>: as a wave-uniform branch inside the one kernel
+// the table cost the ordinary launch 3-4 % (these marches are paced by their instruction stream, see PF above and DESIGN.md 6).
+template <typename T, int S, bool FIRST, bool XE, bool TAB>
+__device__ __forceinline__ void ringcz_body(const MultiP<T, T> &P, T (*zl)[S * 64 * (16 / sizeof(T))]) {
   constexpr int VEC = 16 / sizeof(T), W = 64 * VEC, M = (S + VEC - 1) / VEC * VEC, WI = W - 2 * M;
-  __shared__ __attribute__((aligned(16))) T zl[4][S * W];   // (row S - 1: the fold strips' exchange of the input state)
   int bx = blockIdx.x;
   if (P.xcd_per > 0 && bx < 8 * P.xcd_per) bx = (bx & 7) * P.xcd_per + (bx >> 3);
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int np = P.nstrips >> 1, nnorm = P.nwx * np;
   const int unit = bx * 2 + (w >> 1);   // a pair of waves: a pair of strips, or (after the pairs) a window of the top rows and its mirror image
-  const bool fold = unit >= nnorm;
+  const bool fold = !TAB && unit >= nnorm;
   const long long boff = (long long)blockIdx.y * P.bstride;
   const bool upper = (w & 1) != 0;
   bool active, odd;
   int wx = 0, a, b, pos_at = 0, klo = -(1 << 30), khi = 1 << 30;
-  if (!fold) {
+  if (TAB) {
+    active = unit < P.nunits;
+    const int4 e = P.utab[active ? unit : 0];   // (wave-uniform: scalar loads)
+    wx = e.x;
+    a = upper ? e.z : e.y;
+    b = upper ? e.w : e.z;
+    odd = !upper;
+  } else if (!fold) {
     const int pid = unit;
     active = true;
     wx = pid % P.nwx;
@@ -580,6 +589,17 @@ __global__ __launch_bounds__(256, 1) void k_ringcz(const MultiP<T, T> P) {
       for (int k = 0; k < nbar; ++k) __syncthreads();
     }
   }
+}
+template <typename T, int S, bool FIRST, bool XE>
+__global__ __launch_bounds__(256, 1) void k_ringcz(const MultiP<T, T> P) {
+  __shared__ __attribute__((aligned(16))) T zl[4][S * 64 * (16 / sizeof(T))];   // (row S - 1: the fold strips' exchange of the input state)
+  ringcz_body<T, S, FIRST, XE, false>(P, zl);
+}
+template <typename T, int S, bool FIRST, bool XE, bool TAB>
+__global__ __launch_bounds__(256, 1) void k_ringcz(const MultiP<T, T> P) {
+  static_assert(TAB, "the even cut is k_ringcz<T, S, FIRST, XE>");
+  __shared__ __attribute__((aligned(16))) T zl[4][S * 64 * (16 / sizeof(T))];
+  ringcz_body<T, S, FIRST, XE, true>(P, zl);
 }
 
 template <typename T, int S, bool FIRST>
@@ -636,6 +656,33 @@ static int launch_ringc_zip_sf(gcmf_plan *pl, const MultiArgs &a, hipStream_t s)
   }
   P.nstrips = 2 * np;
   P.H = (nrows - P.fold_rows + 2 * np - 1) / (2 * np);
+  // (round 7) whole grids with land, a lone field: the pairs cut from the rows of each window that hold anything wet -- the wave slots
+  // of all-land tiles go to the wet part, and every strip gets shorter (wet_table, gcmf_ringc_zip.hip)
+  const WetTable *tab = nullptr;
+  if (sizeof(T) == 8 && pl->wet_now && !a.zip_fold) {
+    int rc = GCMF_OK;
+    tab = wet_table(pl, a, s, &rc);
+    if (rc) return rc;
+    if (tab && !pl->pool_clean) {   // cells no pair owns are read as ghost cells: they must be finite (gcmf_plan::pool_clean)
+      if (FIRST) {                  // (a first launch reads no state: nothing the fill could destroy)
+        GCMF_HIP(hipMemsetAsync(pl->pool_base, 0, pl->pool_bytes, s));
+        pl->pool_clean = true;
+      } else {
+        // A later launch of an application whose FIRST launch took no table (the policy refused that depth, or another kernel ran it):
+        // the planes hold live state, so no fill, and this launch keeps the even cut -- as will the later launches of every such
+        // application, silently (option 2 never gets here: every launch of an eligible call takes its table, the first one too).
+        // clenshaw_cut puts the deepest launches first; where the policy of option 1 refuses those and would take a shallower
+        // later one, that one is lost.
+        tab = nullptr;
+      }
+    }
+  }
+  if (tab) {
+    P.utab = (const int4 *)tab->dev;
+    P.nunits = tab->nunits;
+    P.nstrips = tab->nstrips;
+    P.H = tab->H;
+  }
   P.npack = 0;
   P.nwaves = P.nwx * P.nstrips;
   P.wrap = g.south_wrap && g.north_wrap;
@@ -646,18 +693,28 @@ static int launch_ringc_zip_sf(gcmf_plan *pl, const MultiArgs &a, hipStream_t s)
   for (int t = 0; t < MAX_PK; ++t) P.pk[t] = t < S ? a.pk[t] : 0.0;
   P.p0 = a.p0;
   P.c = a.c;
-  dim3 block(256), grid((P.nwx * np + P.nfw + 1) / 2, (unsigned)a.nbatch);
+  dim3 block(256), grid(tab ? (tab->nunits + 1) / 2 : (P.nwx * np + P.nfw + 1) / 2, (unsigned)a.nbatch);
   P.xcd_per = pl->xcd_remap ? (int)(grid.x / 8) : 0;
   P.zigzag = 1;
   bool xe = true;
   ringc_zip_rows(std::max(P.H, P.fold_rows) + S + 1, S, &xe);
   if (pl->ringc_zip == 2) xe = true;    // (tuning: 2 = always the early-exit form, 3 = always whole periods)
   if (pl->ringc_zip == 3) xe = false;
-  if (xe) hipLaunchKernelGGL((k_ringcz<T, S, FIRST, true>), grid, block, 0, s, P);
-  else hipLaunchKernelGGL((k_ringcz<T, S, FIRST, false>), grid, block, 0, s, P);
+  if (tab) {
+    if constexpr (sizeof(T) == 8) {   // (f64 only: wet_table)
+      if (grid.x > 0) {   // (a grid that is all land has no pair: k_land_fix writes the whole result)
+        if (xe) hipLaunchKernelGGL((k_ringcz<T, S, FIRST, true, true>), grid, block, 0, s, P);
+        else hipLaunchKernelGGL((k_ringcz<T, S, FIRST, false, true>), grid, block, 0, s, P);
+      }
+    }
+  } else if (xe) {
+    hipLaunchKernelGGL((k_ringcz<T, S, FIRST, true>), grid, block, 0, s, P);
+  } else {
+    hipLaunchKernelGGL((k_ringcz<T, S, FIRST, false>), grid, block, 0, s, P);
+  }
   GCMF_HIP(hipGetLastError());
-  note_kernel(pl, std::string("gcmf::k_ringcz<") + tyname<T>() + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ", " + (xe ? "true" : "false") + ">", S,
-              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows));
+  note_kernel(pl, std::string("gcmf::k_ringcz<") + tyname<T>() + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ", " + (xe ? "true" : "false") + (tab ? ", true>" : ">"), S,
+              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + (tab ? " units=" + std::to_string(tab->nunits) : std::string()));
   return GCMF_OK;
 }
 

@@ -18,6 +18,144 @@ int ringc_zip_march(const gcmf_plan *pl, const MultiArgs &a, int *pairs) {
   if (pairs) *pairs = np;
   return np >= 1 ? march : 0;
 }
+// Strips cut from the wet rows of each window (round 7).  A quarter to a third of an ocean grid is land in continents many windows wide:
+// a (window, strip) tile whose 128 columns hold nothing but isolated cells marches its rows for nothing -- the state there is +-0 at every
+// level and k_land_fix writes the result.  Leaving such waves out alone would not shorten the launch (it lasts as long as its tallest
+// strip): their wave slots go to the wet part instead.  Per window the rows that hold anything wet (WetProfile, once per plan and window
+// width) are widened by S + 1 rows on both ends (across the y wrap where the grid wraps) and merged into runs; every run is cut into
+// pairs (lo, mid, hi) of equal height, the height being the smallest at which all pairs of the launch fit ONE round of the 512 pair
+// slots.  Same march, same operands for every cell a pair owns; cells no pair owns are isolated, hold +-0 in the state planes
+// (gcmf_plan::pool_clean) and get their result from k_land_fix.
+static const WetProfile *wet_profile(gcmf_plan *pl, int WI, hipStream_t s, int *rc) {
+  for (const WetProfile &p : pl->wet_prof)
+    if (p.WI == WI) return &p;
+  // once per plan and window width, on the host: the plan's land bytes come back once (rows x nx bytes), a row's windows are ranges of
+  // its running count of cells that exchange with a neighbour (the window's 128 columns: WI owned ones and the ghost columns, across
+  // the x wrap)
+  const int rows = pl->g.rows, nx = pl->g.nx, nwx = (nx + WI - 1) / WI, M = (128 - WI) / 2;
+  std::vector<uint8_t> bits((size_t)rows * nx);
+  if (hipMemcpyAsync(bits.data(), pl->lbits, bits.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+    set_error("wet_profile: reading the plan's land bytes back failed: %s", hipGetErrorString(hipGetLastError()));
+    *rc = GCMF_ERR_HIP;
+    return nullptr;
+  }
+  WetProfile p;
+  p.WI = WI;
+  p.need.assign((size_t)nwx * rows, 0);
+  std::vector<int> run((size_t)nx + 1);
+  for (int r = 0; r < rows; ++r) {
+    const uint8_t *row = bits.data() + (size_t)r * nx;
+    run[0] = 0;
+    for (int i = 0; i < nx; ++i) run[i + 1] = run[i] + (row[i] & 1);
+    for (int wx = 0; wx < nwx; ++wx) {
+      int any = 0;
+      if (nx <= 128) {
+        any = run[nx];
+      } else {
+        int c0 = (wx * WI - M) % nx;
+        if (c0 < 0) c0 += nx;
+        const int c1 = c0 + 128;
+        any = c1 <= nx ? run[c1] - run[c0] : (run[nx] - run[c0]) + run[c1 - nx];
+      }
+      p.need[(size_t)wx * rows + r] = any ? 1 : 0;
+    }
+  }
+  pl->wet_prof.push_back(std::move(p));
+  return &pl->wet_prof.back();
+}
+
+const WetTable *wet_table(gcmf_plan *pl, const MultiArgs &a, hipStream_t s, int *rc) {
+  *rc = GCMF_OK;
+  const Geom &g = pl->g;
+  const int S = a.S, rows = g.rows, nrows = a.row_hi - a.row_lo;
+  if (!pl->wet_rows || !pl->wet_now || pl->mask_per_field || pl->n_land <= 0 || !pl->lbits || pl->d.dtype != GCMF_F64 || pl->kind != K_FLUX ||
+      g.fold || a.zip_fold || a.nbatch != 1 || !pl->pool_base || !pl->pool_bytes || S < 5 || S > 9 || nrows < 4)
+    return nullptr;
+  const WetTable *t = nullptr;
+  for (const WetTable &c : pl->wet_tabs)
+    if (c.S == S && c.row_lo == a.row_lo && c.row_hi == a.row_hi && c.nbatch == a.nbatch) t = &c;
+  if (!t) {
+    const int M = (S + 1) / 2 * 2, WI = 128 - 2 * M, nwx = (g.nx + WI - 1) / WI, reach = S + 1;
+    const WetProfile *prof = wet_profile(pl, WI, s, rc);
+    if (!prof) return nullptr;
+    const bool wrap = g.south_wrap && g.north_wrap;
+    WetTable nt;
+    nt.S = S; nt.row_lo = a.row_lo; nt.row_hi = a.row_hi; nt.nbatch = a.nbatch;
+    struct Run { int wx, lo, len; };
+    std::vector<Run> runs;
+    std::vector<uint8_t> own(nrows);
+    bool ok = true;
+    for (int wx = 0; wx < nwx && ok; ++wx) {
+      const uint8_t *need = prof->need.data() + (size_t)wx * rows;
+      std::fill(own.begin(), own.end(), 0);
+      for (int r = 0; r < rows; ++r) {
+        if (!need[r]) continue;
+        for (int d = -reach; d <= reach; ++d) {
+          int q = r + d;
+          if (wrap) q = ((q % rows) + rows) % rows;
+          if (q >= a.row_lo && q < a.row_hi) own[q - a.row_lo] = 1;
+        }
+      }
+      for (int r = 0; r < nrows;) {
+        if (!own[r]) { ++r; continue; }
+        int e = r;
+        while (e < nrows && own[e]) ++e;
+        if (e - r < 4) ok = false;   // (a grid shorter than a run)
+        runs.push_back({wx, a.row_lo + r, e - r});
+        r = e;
+      }
+    }
+    if (ok && runs.size() <= 512) {
+      // the smallest strip height at which the pairs of all runs fit one round of the 512 pair slots
+      auto pairs_of = [](int len, int H) { return std::max(1, std::min(len / 4, (len + 2 * H - 1) / (2 * H))); };
+      int H = 2;
+      for (;; ++H) {
+        long long tot = 0;
+        for (const Run &r : runs) tot += pairs_of(r.len, H);
+        if (tot <= 512) break;
+      }
+      std::vector<int4> units;
+      std::vector<int> per_window(nwx, 0);
+      for (const Run &r : runs) {
+        const int n = pairs_of(r.len, H);
+        per_window[r.wx] += n;
+        for (int p = 0; p < n; ++p) {
+          const int lo = r.lo + (int)((long long)p * r.len / n), hi = r.lo + (int)((long long)(p + 1) * r.len / n), mid = lo + (hi - lo) / 2;
+          units.push_back(make_int4(r.wx, lo, mid, hi));
+          nt.H = std::max(nt.H, std::max(mid - lo, hi - mid));
+        }
+      }
+      // neighbours in x side by side, then up the grid: the order in which the even cut numbers its pairs (they share an XCD's L2)
+      std::stable_sort(units.begin(), units.end(), [](const int4 &p, const int4 &q) { return p.z != q.z ? p.z < q.z : p.x < q.x; });
+      nt.nunits = (int)units.size();
+      nt.nstrips = 2 * (nwx ? *std::max_element(per_window.begin(), per_window.end()) : 0);
+      nt.march = (int)ringc_zip_rows(nt.H + S + 1, S, nullptr);
+      const size_t bytes = std::max<size_t>(1, units.size()) * sizeof(int4);
+      if (hipMalloc(&nt.dev, bytes) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("wet_table: no memory for %zu pairs", units.size());
+        *rc = GCMF_ERR_HIP;
+        return nullptr;
+      }
+      pl->owned.push_back(nt.dev);
+      if (!units.empty() && hipMemcpy(nt.dev, units.data(), units.size() * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess) {
+        set_error("wet_table: uploading %zu pairs failed: %s", units.size(), hipGetErrorString(hipGetLastError()));
+        *rc = GCMF_ERR_HIP;
+        return nullptr;
+      }
+    }
+    pl->wet_tabs.push_back(nt);
+    t = &pl->wet_tabs.back();
+  }
+  if (!t->dev) return nullptr;
+  if (pl->wet_rows == 1) {   // the policy of the zipped strips themselves: only where it marches at least 10 % fewer rows
+    int march = 0;
+    const int M = (S + 1) / 2 * 2, WI = 128 - 2 * M;
+    if (ringc_zip_pairs((g.nx + WI - 1) / WI, a.nbatch, nrows, S, &march) < 1 || (long long)t->march * 100 > (long long)march * 90) return nullptr;
+  }
+  return t;
+}
+
 // The tripole seam inside the launch (round 6): whole-launch conditions for k_ringcz's fold strips (gcmf_ringc_impl.hpp) -- the f64 flux
 // kind evaluated backwards, rows up to the seam, a lane's two cells on one side of the row's centre, no packed batch.
 bool ringc_zip_fold_ok(const gcmf_plan *pl, const MultiArgs &a) {
