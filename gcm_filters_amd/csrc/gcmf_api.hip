@@ -93,41 +93,17 @@ static void host_unregister(const void *p) {
 //
 // Tripolar grids: the fold couples column i of the top row with column nx-1-i, i.e. with a DIFFERENT wave of the
 // strip-marching kernel, which therefore stops S rows below the seam; the top S rows ("band") are advanced by k_fold_band.
-static int launch_ringc(gcmf_plan *pl, const MultiArgs &m, hipStream_t s) {
+// backward: the launcher of the form ringc_cut chose for this launch (gcmf_ringc_cut.hpp has the policy and its measurements)
+static int launch_ringc(gcmf_plan *pl, const MultiArgs &m, const RingcCut &cut, hipStream_t s) {
+  if (cut.form == RINGC_NONE) return GCMF_OK;
+  if (cut.form == RINGC_ZIP || cut.form == RINGC_ZIP_FOLD) return launch_ringc_zip(pl, m, cut, s);
   switch (pl->kind) {
-    case K_REG: return launch_ringc_reg(pl, m, s);
-    case K_MASK: return launch_ringc_maskz(pl, m, s);
+    case K_REG: return launch_ringc_reg(pl, m, cut, s);
+    case K_MASK: return launch_ringc_maskz(pl, m, cut, s);
     case K_FLUX:
-      // Nothing has to fit beside the waves where there is no tripole seam -> the early-exit form (k_ringcs) wherever it shortens the march:
-      // the plain form marches whole 12-row ring periods, the early-exit form leaves after every fourth row (and costs ~60 registers:
-      // 1.4 % per launch in f64, ~8 % in f32).  1024 lone waves on 1080 x 1440 f64 cells own 14-row strips: 32 rows marched instead of 36,
-      // and every SIMD has a wave (330 -> 364 G cell-steps/s, tools/measure_midsize.py); an 8-way slab 28 instead of 36; BASELINE-size
-      // f64 grids 96 either way (-> k_ringc), BASELINE-size f32 grids 52 instead of 60 (+4 %), 1080 x 1440 f32 24 either way (-> k_ringc,
-      // the early-exit form measured 9 % slower there).
-      if (!pl->g.fold || pl->alone_now) {   // (nothing has to fit beside these waves: no seam in this launch, or its band runs afterwards)
-        const bool f64 = pl->d.dtype == GCMF_F64;
-        const int wi = f64 ? (m.S == 9 ? 108 : 112) : 240;   // useful columns of a window (f32: four cells per lane)
-        const long long nrows = m.row_hi - m.row_lo, per = ((pl->g.nx + wi - 1) / wi) * std::max<long long>(1, m.nbatch);
-        const long long want = strips_per_column(per, nrows, m.S, 12);
-        const long long H0 = std::min(nrows, std::max(4LL, pl->strip_rows > 0 ? (long long)pl->strip_rows : (nrows + want - 1) / want));
-        const long long need = H0 + 2 * m.S;
-        const long long rows_xe = std::max(12LL, (need + 3) / 4 * 4), rows_pad = (need + 11) / 12 * 12;
-        const bool xe = m.S <= 8 && H0 < pl->ringc_xe_rows && rows_xe * 100 <= rows_pad * (f64 ? 95 : 90);
-        // Round 6: strips zipped in pairs at a shared seam (k_ringcz) march H + S + 1 rows instead of H + 2 S: where strips are as short as
-        // their ghost zones (1/4-degree grids: 15 rows behind 2 x 9; the 300-row slab of one of eight ranks: 11 behind 2 x 8) -- and, for
-        // less, at BASELINE size (2400 x 3600: 30 strips of 80 rows marching 92 instead of 27 of 90 marching 108: 890.5 against 906 us,
-        // same box, alternating; the launch is bound by HBM there)
-        const long long rounds = (per * ((nrows + H0 - 1) / H0) + 1023) / 1024;
-        const int mz = ringc_zip_march(pl, m, nullptr);
-        if (mz > 0 && m.nbatch <= 1 && (long long)mz * 100 <= rounds * (xe ? rows_xe : rows_pad) * 90) return launch_ringc_zip(pl, m, s);
-        // batches: against the better of whole strips per field and the packed column (1/4-degree grids, 2 .. 8 fields: + 3 .. 20 %)
-        if (mz > 0 && m.nbatch > 1 && f64 &&
-            mz * 100.0 <= ringc_batch_cost((pl->g.nx + wi - 1) / wi, m.nbatch, nrows, m.S, xe ? 4 : 12, pl->pack_batch != 0) * 90.0)
-          return launch_ringc_zip(pl, m, s);
-        if (xe) return launch_ringc_flux_slab(pl, m, s);
-      }
-      if (m.S == 9) return launch_ringc_flux9(pl, m, s);
-      return launch_ringc_flux(pl, m, s);
+      if (cut.xe) return launch_ringc_flux_slab(pl, m, cut, s);   // (k_ringcs, or k_ringcp's early-exit form)
+      if (m.S == 9) return launch_ringc_flux9(pl, m, cut, s);
+      return launch_ringc_flux(pl, m, cut, s);
     default: break;
   }
   set_error("k_ringc: plan is not a scalar kind");
@@ -139,9 +115,10 @@ int advance_multi(gcmf_plan *pl, const MultiArgs &m, hipStream_t s, int *launche
   const int rows = g.rows, S = m.S;
   const bool band = g.fold && m.row_hi == rows;
   int rc;
+  RingcCut cut{};
   auto blocked = [&](const MultiArgs &a) -> int {   // (between the dominant kernel's timing events)
     int r;
-    if ((r = dom_begin(pl, s)) || (r = backward ? launch_ringc(pl, a, s) : launch_scalar_multi(pl, a, s)) || (r = dom_end(pl, s))) return r;
+    if ((r = dom_begin(pl, s)) || (r = backward ? launch_ringc(pl, a, cut, s) : launch_scalar_multi(pl, a, s)) || (r = dom_end(pl, s))) return r;
     if (launches) ++*launches;
     return GCMF_OK;
   };
@@ -149,18 +126,10 @@ int advance_multi(gcmf_plan *pl, const MultiArgs &m, hipStream_t s, int *launche
   // that lasts no longer than itself the band is the slower of the two (its waves share the SIMDs with the marching waves) and the fork /
   // join costs ~5 us on top: a 1080 x 1440 tripolar grid took 294 us against 215 us for the same grid without a seam.
   const bool seq = band && pl->band_seq_cells > 0 && (long long)m.nbatch * (m.row_hi - m.row_lo) * g.nx <= pl->band_seq_cells;
-  pl->alone_now = !band || seq;
-  if (!band) return blocked(m);
-  if (backward && ringc_zip_fold_ok(pl, m)) {   // (round 6) the seam's rows inside the launch: strips that start at the seam, zipped with their mirror windows
-    MultiArgs mz = m;
-    mz.zip_fold = 1;
-    pl->alone_now = true;
-    if ((rc = dom_begin(pl, s))) return rc;
-    if ((rc = launch_ringc_zip(pl, mz, s))) return rc;
-    if ((rc = dom_end(pl, s))) return rc;
-    if (launches) ++*launches;
-    return GCMF_OK;
-  }
+  // how the strips of a backward launch are cut: decided once, here (on the seam's plan: of the rows k_fold_band leaves, or -- round 6 --
+  // the seam's rows inside the launch: strips that start at the seam, zipped with their mirror windows)
+  if (backward) cut = ringc_cut(ringc_cut_in(pl, m.row_hi - m.row_lo, band, m.nbatch, S, band && !seq));
+  if (!band || cut.form == RINGC_ZIP_FOLD) return blocked(m);
   const int blo = rows - S;  // first band row
   // k_fold_band reads rows [rows - 2S, rows) of the input planes (valid: the caller's ghost zone covers [row_lo - S, ...)) and owns
   // [rows - S, rows); the blocked launch gets [row_lo, rows - S), possibly nothing

@@ -32,12 +32,7 @@ bool ringc9_ok(const gcmf_plan *pl) {
 // short of the seam keep the band.
 static bool ringc9_fold_ok(const gcmf_plan *pl, int64_t nbatch, int64_t row_lo, int64_t row_hi) {
   if (!(pl && pl->ringc9 && pl->kind == K_FLUX && pl->d.dtype == GCMF_F64 && pl->full && pl->g.fold && pl->g.rows >= 64)) return false;
-  MultiArgs a{};
-  a.S = 9;
-  a.nbatch = nbatch;
-  a.row_lo = (int)row_lo;
-  a.row_hi = (int)row_hi;
-  return ringc_zip_fold_ok(pl, a);
+  return ringc_cut(ringc_cut_in(pl, (int)(row_hi - row_lo), row_hi == pl->g.rows, nbatch, 9, false)).form == RINGC_ZIP_FOLD;
 }
 
 // ... and ROW SLABS of f64 flux grids without a tripole seam, when the slab's owner says so (option "slab_nines": SlabFilter sets it on every
@@ -92,9 +87,12 @@ int clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, 
     // ~4 + rows x (0.6 + 0.045 S); 1080 x 1440 n 63: 7 x 9 levels 225, 8 launches of <= 8 215, 9 x 7 217; 720 x 1440: 158 / 170 / 169.
     double best = 0.0;
     for (int S = 9; S >= 7; --S) {
-      const int M = (S + 1) / 2 * 2, WI = 128 - 2 * M, L = (n_steps + S - 1) / S;
-      int march = 0;
-      if (ringc_zip_pairs((pl->g.nx + WI - 1) / WI, 1, pl->g.rows, S, &march) < 1) continue;
+      // (the even zipped cut of a lone field over all the plan's rows, whatever the plan's strip_rows and seam)
+      RingcCutIn in = ringc_cut_in(pl, pl->g.rows, false, 1, S, false);
+      in.strip_rows = 0;
+      const long long march = ringc_cut(in).zip_march;
+      const int L = (n_steps + S - 1) / S;
+      if (march < 1) continue;
       const double t = L * (4.0 + march * (0.6 + 0.045 * S));
       if (best == 0.0 || t < 0.98 * best) { best = t; smax = S; }
     }

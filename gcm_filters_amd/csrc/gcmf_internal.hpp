@@ -12,17 +12,9 @@
 #include <vector>
 
 #include "gcmf.h"
+#include "gcmf_ringc_cut.hpp"   // enum Kind, strips_per_column; ringc_cut(): how a backward scalar launch is cut
 
 namespace gcmf {
-
-// Stencil families.  Every reference Laplacian maps onto one of them after plan-time folding.
-enum Kind : int {
-  K_REG = 0,   // REGULAR, REGULAR_AREA_WEIGHTED: 5-point, no coefficients              (40 B/cell.step f64)
-  K_MASK = 1,  // *_WITH_LAND regular grids + tripolar regular: 1 byte of neighbour bits (41 B)
-  K_FLUX = 2,  // IRREGULAR / POP / MOM5U / MOM5T: east-face, north-face, 1/area planes  (64 B)
-  K_CGRID = 3, // VECTOR_C_GRID: 14 folded planes
-  K_BGRID = 4  // VECTOR_B_GRID: 8 folded planes
-};
 
 // internal mode bit on top of GCMF_STEP_FIRST / GCMF_STEP_LAST
 constexpr unsigned STEP_LAPL = 0x100u;  // t0 = L(t1) only (gcmf_laplacian)
@@ -84,7 +76,6 @@ struct MultiArgs {
   int land_zero;  // the caller guarantees that isolated (land) cells of u0 and v0 are zero: GCMF_STEP_LAND_ZERO
   int ring_first; // first launch: the caller will overwrite the result of the isolated (land) cells (k_land_fix) or there are
                   // none, so the launch may take them as zero while it loads the field (k_ring<..., FIRST>)
-  int zip_fold = 0;  // k_ringcz: [row_lo, row_hi) ends at the tripole seam and the launch advances the seam rows itself (no k_fold_band)
 };
 
 // Arguments of one S-step vector launch (gcmf_cgrid_stream2.hip / gcmf_bgrid_stream2.hip): T_{k-1}, T_{k-2} -> T_{k+S-2}, T_{k+S-1}.
@@ -198,7 +189,6 @@ struct gcmf_plan {
   int pack_batch = 1;     // k_ringc / k_ringcs: the fields of a batch as one column per window (ringc_walk, round 6); gcmf_set_option "pack_batch"
   int ringc_zip = 1;      // f64 flux plans without a tripole seam: k_ringcz where it marches fewer rows (env GCMF_RINGC_ZIP, gcmf_set_option "ringc_zip")
   long long band_seq_cells = 3000000;   // tripolar plans: blocked launches over at most this many cells run k_fold_band AFTER themselves (its 1024-thread form), not beside (env GCMF_BAND_SEQ_CELLS; 0 = never)
-  bool alone_now = true;  // (set by advance_multi for the blocked launch it issues: no k_fold_band waves will share its SIMDs)
   int zip_fold = 1;       // tripolar f64 flux plans, backward evaluation: k_ringcz advances the seam's rows itself (no k_fold_band); gcmf_set_option "zip_fold", env GCMF_ZIP_FOLD
   // Whole f64 flux grids with land, a lone field (round 7): k_ringcz's strips are cut from the rows of each window that hold anything wet
   // (wet_table, gcmf_ringc_zip.hip).  0 off, 1 where that marches at least 10 % fewer rows than the even cut, 2 whenever eligible;
@@ -255,79 +245,6 @@ inline std::string launch_geom(int H, int nstrips, int nwx, int xcd, unsigned gx
   return b;
 }
 size_t dtype_size(int dtype);
-// How many strips a (window, batch entry) column of the one-wave-per-SIMD strip-marching kernels is cut into: ideally as many as fill ONE
-// resident round of 1024 waves (all strips march in lock-step) -- a single field at BASELINE size: 33 windows x 31 strips.  Batches do
-// not divide that well (33 windows x 16 fields = 528 columns: one strip each left half the SIMDs without a wave -- a batch of 16 ran at
-// 515 G against 811 G for a batch of 4 before round 5): the number of rounds k <= 8 is chosen that minimises k x (rows a wave marches:
-// H + 2 S, rounded up to the exit period), one round being preferred by 4 % per extra round.
-inline long long strips_per_column(long long per_strip, long long nrows, int S, int period) {
-  if (per_strip < 1) per_strip = 1;
-  long long best = 1;
-  double best_cost = -1.0;
-  for (int k = 1; k <= 8; ++k) {
-    long long w = (1024LL * k) / per_strip;
-    if (w < 1) w = 1;
-    if (w > nrows) w = nrows;
-    const long long H = (nrows + w - 1) / w;
-    long long march = H + 2 * S;
-    if (period > 1) march = (march + period - 1) / period * period;
-    const long long rounds = (w * per_strip + 1023) / 1024;
-    const double cost = (double)(rounds * march) * (1.0 + 0.04 * (rounds - 1));
-    if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = w; }
-    if (w >= nrows) break;
-  }
-  return best;
-}
-// k_ringcz (gcmf_ringc_impl.hpp): strips zipped in pairs
-// rows a ZIP march of `need` rows runs -- with early exits: one every second row up to eight levels, every fourth at nine; without: whole
-// ring periods (taken when it is no longer: 80 fewer registers, the same time per row -- 1080 x 1440 at eight levels, 24 rows either way:
-// 215.2 against 214.7 us)
-inline long long ringc_zip_rows(long long need, int S, bool *xe) {
-  const long long ex = S <= 8 ? 2 : 4;
-  const long long mx = std::max(12LL, (need + ex - 1) / ex * ex), mp = (need + 11) / 12 * 12;
-  if (xe) *xe = mx < mp;
-  return std::min(mx, mp);
-}
-// pairs per window: whole rounds of the 1024 wave slots, strips of at least two rows; *march = rows the launch marches (all rounds)
-inline int ringc_zip_pairs(long long nwx, long long nbatch, long long nrows, int S, int *march) {
-  long long best = 0, best_cost = 0;
-  for (int k = 1; k <= 8; ++k) {
-    long long np = (512LL * k) / std::max(1LL, nwx * nbatch);
-    np = std::min(np, nrows / 4);
-    if (np < 1) continue;
-    const long long H = (nrows + 2 * np - 1) / (2 * np);                 // the taller strips
-    const long long m = ringc_zip_rows(H + S + 1, S, nullptr);
-    const long long rounds = (2 * np * nwx * nbatch + 1023) / 1024;
-    const long long cost = rounds * m * (100 + 4 * (rounds - 1));
-    if (!best || cost < best_cost) { best = np; best_cost = cost; if (march) *march = (int)(rounds * m); }
-    if (np >= nrows / 4) break;
-  }
-  return (int)best;
-}
-
-// What a batch costs WITHOUT k_ringcz, in rows marched (x 1.04 per extra round of the wave slots): the better of whole strips per field and
-// the packed column of launch_ringc_sf (gcmf_ringc_impl.hpp: the same formulas) -- for the policies that weigh the zipped strips against it
-inline double ringc_batch_cost(long long nwx, long long nbatch, long long nrows, int S, int exitp, bool pack) {
-  auto padded = [&](long long m) { return (m + exitp - 1) / exitp * exitp; };
-  const long long want = strips_per_column(nwx * nbatch, nrows, S, exitp);
-  long long H = std::max(4LL, (nrows + want - 1) / want);
-  if (exitp == 12) H += (12 - (H + 2 * S) % 12) % 12;
-  H = std::min(H, nrows);
-  const long long nstrips = (nrows + H - 1) / H, rounds_u = (nwx * nbatch * nstrips + 1023) / 1024;
-  double best = (double)(rounds_u * padded(H + 2 * S)) * (1.0 + 0.04 * (rounds_u - 1));
-  if (!pack || nbatch <= 1) return best;
-  const long long total = nbatch * nrows, slots = std::max(1LL, 1024LL / nwx);
-  for (long long k = 1; k <= 16; ++k) {
-    const long long w = std::min(total, slots * k), q = (total + w - 1) / w;
-    if (q > nrows || q > 320) continue;
-    const long long rounds = (w * nwx + 1023) / 1024;
-    const bool crosses = (nrows % q) != 0;
-    const double cost = (double)(rounds * (padded(q + 2 * S) + (crosses ? padded(2 * S + exitp / 2) : 0))) * (1.0 + 0.04 * (rounds - 1));
-    if (cost < 0.97 * best) best = cost;
-    if (w >= total) break;
-  }
-  return best;
-}
 // kernel launchers (defined in gcmf_scalar.hip / gcmf_vector.hip)
 int launch_scalar_step(gcmf_plan *pl, const StepArgs &a, hipStream_t s);
 int launch_vector_step(gcmf_plan *pl, const StepArgs &a, hipStream_t s);
@@ -335,20 +252,24 @@ int launch_scalar_multi(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);
 bool flux_multi2_supported(const gcmf_plan *pl, int S);
 bool ring_supported(const gcmf_plan *pl, const MultiArgs &a);
 int launch_ring_flux_f32(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);   // gcmf_ring_flux_f32.hip
-// backward (Clenshaw) evaluation, gcmf_ringc_impl.hpp: one launch of S = 5..8 levels; a.fb_in = the constant input f, a.fb_out =
-// the result (last launch), a.pk[t] = the coefficient of level t + 1 of this launch
-int launch_ringc_reg(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);
-int launch_ringc_maskz(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);
-int launch_ringc_flux(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);
-int launch_ringc_flux9(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);   // nine levels: whole f64 flux grids without a seam (gcmf_ringc_flux9.hip)
-int launch_ringc_flux_slab(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);
-int launch_ringc_zip(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);   // f64 flux plans without a tripole seam, short strips: pairs of strips zipped at a shared seam (k_ringcz, gcmf_ringc_zip.hip)
-int ringc_zip_march(const gcmf_plan *pl, const MultiArgs &a, int *pairs);
+// backward (Clenshaw) evaluation, gcmf_ringc_impl.hpp: one launch of S = 5..9 levels; a.fb_in = the constant input f, a.fb_out =
+// the result (last launch), a.pk[t] = the coefficient of level t + 1 of this launch; cut = ringc_cut()'s answer for the launch
+// (gcmf_ringc_cut.hpp), which the launchers apply: advance_multi asks once and picks the launcher by cut.form
+inline RingcCutIn ringc_cut_in(const gcmf_plan *pl, int rows, bool seam, int64_t nbatch, int S, bool band_beside) {
+  return RingcCutIn{pl->g.nx, rows, seam, (long long)nbatch, S, pl->d.dtype == GCMF_F64, pl->kind, band_beside, pl->mask_per_field != 0,
+                    pl->strip_rows, pl->ringc_xe_rows, pl->ringc_zip, pl->zip_fold, pl->pack_batch};
+}
+int launch_ringc_reg(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
+int launch_ringc_maskz(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
+int launch_ringc_flux(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
+int launch_ringc_flux9(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // nine levels: whole f64 flux grids without a seam (gcmf_ringc_flux9.hip)
+int launch_ringc_flux_slab(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // no seam's band beside, short strips: early exits (k_ringcs)
+int launch_ringc_flux_slab_f32(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
+int launch_ringc_zip(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // f64 flux plans: pairs of strips zipped at a shared seam, fold strips at the tripole seam (k_ringcz, gcmf_ringc_zip.hip)
 // k_ringcz's pairs cut from the wet rows of each window (round 7): the table of this launch geometry (built once, cached on the plan), or
-// nullptr where the launch keeps the even cut (not eligible, the policy of option "wet_rows", or an error -- then *rc says which)
-const WetTable *wet_table(gcmf_plan *pl, const MultiArgs &a, hipStream_t s, int *rc);
-bool ringc_zip_fold_ok(const gcmf_plan *pl, const MultiArgs &a);   // can k_ringcz advance the tripole seam's rows of this launch itself?  // rows a k_ringcz launch would march (all rounds), 0 = not offered
-int launch_ringc_flux_slab_f32(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);   // flux plans without a tripole seam, short strips: early exits (k_ringcs)
+// nullptr where the launch keeps the even cut (not eligible, the policy of option "wet_rows" against the even cut's march, or an error --
+// then *rc says which)
+const WetTable *wet_table(gcmf_plan *pl, const MultiArgs &a, long long even_march, hipStream_t s, int *rc);
 int launch_flux_multi2(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);
 // the on-chip kernel (gcmf_resident.hip): L <= 64 levels of the backward evaluation in ONE launch on a field that fits the register
 // files + LDS of the chip (short slabs, small grids); pk = the L coefficients (a.S / a.pk are ignored)

@@ -37,8 +37,6 @@ template <int VEC> __device__ __forceinline__ unsigned cell_bytes(const uint8_t 
 
 // one march of a strip; returns whether this wave met a non-finite value in its last level (wave-uniform)
 // XE: early exits also for the flux kinds (k_ringcs: slabs that do not own a tripole seam, see below)
-// XE6: ONE early exit, in the middle of the ring period (whole f64 flux grids at nine levels, round 6: a strip marches a multiple of six
-// rows instead of twelve)
 // ZIP: two strips of one window that share a boundary ("seam") march AWAY from it, side by side in one workgroup (k_ringcz, round 6): neither
 // warms its levels up over S ghost rows on that side -- at its first row every level takes the flux across the seam from the row the partner
 // has just produced (one row per level through LDS, a workgroup barrier per level: S - 1 of them in the first ring period), so a strip
@@ -59,7 +57,7 @@ template <bool ZIP> constexpr bool ringc_ramp_on(int t, int ph) { return ZIP ? (
 // time).  pos_at: the window's first column instead of wx * WI - M; [klo, khi): the columns this window keeps.
 // PF: the launch carries one plane of mask bytes per batch entry (MultiP::mper, GCMF_MASK_FROM_NAN) -- an instantiation of k_ringc of its
 // own (see k_ring, gcmf_ring_impl.hpp: the kernel of an ordinary launch is the code it was before).
-template <typename T, int KIND, int S, bool FIRST, bool SANI, bool XE = false, bool XE6 = false, bool ZIP = false, bool PF = false>
+template <typename T, int KIND, int S, bool FIRST, bool SANI, bool XE = false, bool ZIP = false, bool PF = false>
 __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx, const int a, const int b, const long long boff, const bool odd,
                                             T *zmine = nullptr, const T *zpart = nullptr, const bool fold = false, const int pos_at = 0,
                                             const int klo = -(1 << 30), const int khi = 1 << 30) {
@@ -441,7 +439,7 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
       if (EARLY && r0 + 3 >= r_last) break;     // (the last period is left after the strip's last row, see k_ring)
       phase(ic<4>{}, r0 + 4, run);
       phase(ic<5>{}, r0 + 5, run);
-      if ((XE6 || XE2) && r0 + 5 >= r_last) break;
+      if (XE2 && r0 + 5 >= r_last) break;
       phase(ic<6>{}, r0 + 6, run);
       phase(ic<7>{}, r0 + 7, run);
       if (EARLY && r0 + 7 >= r_last) break;
@@ -463,17 +461,17 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
 // its run, which crosses at most one field boundary (H <= nrows): up to two (field, row range) segments, each a march of its own with its
 // 2 S warm-up rows.  16 fields x 33 windows of a 300-row slab tile 1024 wave slots at ~70 % as whole strips (a strip cannot cross from one
 // field into the next) and at ~95 % this way.
-template <typename T, int KIND, int S, bool FIRST, bool XE, bool XE6, bool PACK, bool PF = false>   // (PF: never packed, launch_ringc_sf)
+template <typename T, int KIND, int S, bool FIRST, bool XE, bool PACK, bool PF = false>   // (PF: never packed, ringc_cut)
 __device__ __forceinline__ void ringc_walk(const MultiP<T, T> &P, const int wid) {
   const int wx = wid % P.nwx, st = wid / P.nwx;
   if constexpr (!PACK) {   // one strip of one field (the instruction stream of rounds 2-5: the walk below costs the land-mask kernel 5 %)
     const int a = P.out_lo + st * P.H;
     const int b = min(a + P.H, P.out_hi);
     const long long boff = (long long)blockIdx.y * P.bstride;
-    if (ringc_march<T, KIND, S, FIRST, false, XE, XE6, false, PF>(P, wx, a, b, boff, (st & 1) != 0)) {
+    if (ringc_march<T, KIND, S, FIRST, false, XE, false, PF>(P, wx, a, b, boff, (st & 1) != 0)) {
       if constexpr (KIND != K_REG) {
         if (P.nfb && (threadIdx.x & 63) == 0) atomicAdd(P.nfb, 1u);                      // instrumentation: gcmf_ring_fallbacks
-        ringc_march<T, KIND, S, FIRST, true, XE, XE6, false, PF>(P, wx, a, b, boff, (st & 1) != 0);   // the same strip again, operands through nan_to_num
+        ringc_march<T, KIND, S, FIRST, true, XE, false, PF>(P, wx, a, b, boff, (st & 1) != 0);   // the same strip again, operands through nan_to_num
       }
     }
     return;
@@ -486,10 +484,10 @@ __device__ __forceinline__ void ringc_walk(const MultiP<T, T> &P, const int wid)
     const int len = min(v1 - v0, nrows - r);
     const int a = P.out_lo + r, b = a + len;
     const long long boff = (long long)fld * P.bstride;
-    if (ringc_march<T, KIND, S, FIRST, false, XE, XE6>(P, wx, a, b, boff, (st & 1) != 0)) {
+    if (ringc_march<T, KIND, S, FIRST, false, XE>(P, wx, a, b, boff, (st & 1) != 0)) {
       if constexpr (KIND != K_REG) {
         if (P.nfb && (threadIdx.x & 63) == 0) atomicAdd(P.nfb, 1u);
-        ringc_march<T, KIND, S, FIRST, true, XE, XE6>(P, wx, a, b, boff, (st & 1) != 0);
+        ringc_march<T, KIND, S, FIRST, true, XE>(P, wx, a, b, boff, (st & 1) != 0);
       }
     }
     v0 += len;
@@ -502,7 +500,7 @@ __global__ __launch_bounds__(256, 1) void k_ringc(const MultiP<T, T> P) {
   if (P.xcd_per > 0 && bx < 8 * P.xcd_per) bx = (bx & 7) * P.xcd_per + (bx >> 3);
   const int wid = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (wid >= P.nwaves) return;
-  ringc_walk<T, KIND, S, FIRST, false, false, false, PF>(P, wid);
+  ringc_walk<T, KIND, S, FIRST, false, false, PF>(P, wid);
 }
 
 // ... and for packed batches (ringc_walk<PACK>): XE = the early-exit form of the flux kinds (k_ringcs)
@@ -512,7 +510,7 @@ __global__ __launch_bounds__(256, 1) void k_ringcp(const MultiP<T, T> P) {
   if (P.xcd_per > 0 && bx < 8 * P.xcd_per) bx = (bx & 7) * P.xcd_per + (bx >> 3);
   const int wid = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (wid >= P.nwaves) return;
-  ringc_walk<T, KIND, S, FIRST, XE, false, true>(P, wid);
+  ringc_walk<T, KIND, S, FIRST, XE, true>(P, wid);
 }
 
 // The flux kinds with early exits: for ROW SLABS that own no tripole seam (the ranks of a multi-GPU run, the row blocks of the host
@@ -524,7 +522,7 @@ __global__ __launch_bounds__(256, 1) void k_ringcs(const MultiP<T, T> P) {
   if (P.xcd_per > 0 && bx < 8 * P.xcd_per) bx = (bx & 7) * P.xcd_per + (bx >> 3);
   const int wid = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (wid >= P.nwaves) return;
-  ringc_walk<T, K_FLUX, S, FIRST, true, false, false>(P, wid);
+  ringc_walk<T, K_FLUX, S, FIRST, true, false>(P, wid);
 }
 
 // k_ringcz: strips ZIPPED in pairs at a shared seam (ringc_march<ZIP>), early exits: mid-size whole grids and row slabs of the f64 flux kinds
@@ -578,13 +576,13 @@ __device__ __forceinline__ void ringcz_body(const MultiP<T, T> &P, T (*zl)[S * 6
   }
   const int nbar = P.fold_rows > 0 ? S : S - 1;   // (barriers of a march: one more in a launch with fold strips)
   bool bad = false;
-  if (active) bad = ringc_march<T, K_FLUX, S, FIRST, false, XE, false, true>(P, wx, a, b, boff, odd, zl[w], zl[w ^ 1], fold, pos_at, klo, khi);
+  if (active) bad = ringc_march<T, K_FLUX, S, FIRST, false, XE, true>(P, wx, a, b, boff, odd, zl[w], zl[w ^ 1], fold, pos_at, klo, khi);
   else
     for (int k = 0; k < nbar; ++k) __syncthreads();
   if (__syncthreads_or(bad ? 1 : 0)) {
     if (active) {
       if (P.nfb && (threadIdx.x & 63) == 0) atomicAdd(P.nfb, 1u);
-      ringc_march<T, K_FLUX, S, FIRST, true, XE, false, true>(P, wx, a, b, boff, odd, zl[w], zl[w ^ 1], fold, pos_at, klo, khi);
+      ringc_march<T, K_FLUX, S, FIRST, true, XE, true>(P, wx, a, b, boff, odd, zl[w], zl[w ^ 1], fold, pos_at, klo, khi);
     } else {
       for (int k = 0; k < nbar; ++k) __syncthreads();
     }
@@ -602,141 +600,10 @@ __global__ __launch_bounds__(256, 1) void k_ringcz(const MultiP<T, T> P) {
   ringcz_body<T, S, FIRST, XE, true>(P, zl);
 }
 
-template <typename T, int S, bool FIRST>
-static int launch_ringc_zip_sf(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
-  constexpr int VEC = 16 / sizeof(T), W = 64 * VEC, M = (S + VEC - 1) / VEC * VEC, WI = W - 2 * M;
+// What every backward scalar launch passes to its kernel: the caller's planes, the plan's coefficient planes, and the cut (ringc_cut,
+// gcmf_ringc_cut.hpp) -- nothing about the geometry is worked out here
+template <typename T> static void ringc_params(MultiP<T, T> &P, const gcmf_plan *pl, const MultiArgs &a, const RingcCut &c) {
   const Geom &g = pl->g;
-  MultiP<T, T> P;
-  P.u0 = (const T *)a.u0;
-  P.v0 = (const T *)a.v0;
-  P.uo = (T *)a.uo;
-  P.vo = (T *)a.vo;
-  P.fb_in = (const T *)a.fb_in;
-  P.fb_out = (T *)a.fb_out;
-  P.d_out = nullptr;
-  if (sizeof(T) == 4 && !a.fb_is_f32) {
-    P.d_out = (double *)a.fb_out;
-    P.fb_out = nullptr;
-  }
-  P.cE = (const T *)g.coef[0];
-  P.cN = (const T *)g.coef[1];
-  P.ra = (const T *)g.coef[2];
-  P.zrow = (const T *)pl->zero_row;
-  P.nfb = pl->ring_nfb;
-  P.mbits = g.mbits;
-  P.lbits = (pl->n_land > 0) ? pl->lbits : nullptr;
-  P.area = (const T *)g.area;
-  P.nx = g.nx;
-  P.rows = g.rows;
-  P.out_lo = a.row_lo;
-  P.out_hi = a.row_hi;
-  const int nrows = a.row_hi - a.row_lo;
-  if (nrows <= 0 || a.nbatch <= 0) return GCMF_OK;
-  P.nwx = (g.nx + WI - 1) / WI;
-  int np = ringc_zip_pairs(P.nwx, a.nbatch, nrows, S, nullptr);
-  P.fold_rows = 0;
-  P.nfw = 0;
-  if (a.zip_fold) {   // the top rows: strips that start at the tripole seam, zipped with their mirror windows (one more "half pair" per window)
-    P.nfw = (g.nx / 2 + WI - 1) / WI;
-    // as many pairs as fill whole rounds of the 256 CUs together with the fold strips (two units per workgroup, pairs and fold strips mixed:
-    // 257 workgroups would be two rounds -- config 4 measured 1.32 ms that way against 0.90)
-    long long npmax = 0;
-    for (long long k = 1; k <= 8 && npmax < 1; ++k) {
-      const long long cap = 256 * k / std::max<long long>(1, std::min<long long>(a.nbatch, 256 * k));   // workgroups per field
-      npmax = 2 * cap > P.nfw ? (2 * cap - P.nfw) / P.nwx : 0;                                        // (two units per workgroup)
-    }
-    np = (int)std::max(1LL, std::min<long long>(npmax, (nrows - S) / 4));
-    // (at least S rows: the ghost rows the pairs below march beyond their last row must stay on this side of the seam)
-    P.fold_rows = std::max(S, (int)((nrows + 2 * np) / (2 * np + 1)));
-    np = (int)std::max(1LL, std::min<long long>(np, (nrows - P.fold_rows) / 4));
-  }
-  if (np < 1 || nrows - P.fold_rows < 2 * np) {
-    set_error("k_ringcz: %d rows cannot be cut into pairs of strips", nrows);
-    return GCMF_ERR_INVALID_ARG;
-  }
-  P.nstrips = 2 * np;
-  P.H = (nrows - P.fold_rows + 2 * np - 1) / (2 * np);
-  // (round 7) whole grids with land, a lone field: the pairs cut from the rows of each window that hold anything wet -- the wave slots
-  // of all-land tiles go to the wet part, and every strip gets shorter (wet_table, gcmf_ringc_zip.hip)
-  const WetTable *tab = nullptr;
-  if (sizeof(T) == 8 && pl->wet_now && !a.zip_fold) {
-    int rc = GCMF_OK;
-    tab = wet_table(pl, a, s, &rc);
-    if (rc) return rc;
-    if (tab && !pl->pool_clean) {   // cells no pair owns are read as ghost cells: they must be finite (gcmf_plan::pool_clean)
-      if (FIRST) {                  // (a first launch reads no state: nothing the fill could destroy)
-        GCMF_HIP(hipMemsetAsync(pl->pool_base, 0, pl->pool_bytes, s));
-        pl->pool_clean = true;
-      } else {
-        // A later launch of an application whose FIRST launch took no table (the policy refused that depth, or another kernel ran it):
-        // the planes hold live state, so no fill, and this launch keeps the even cut -- as will the later launches of every such
-        // application, silently (option 2 never gets here: every launch of an eligible call takes its table, the first one too).
-        // clenshaw_cut puts the deepest launches first; where the policy of option 1 refuses those and would take a shallower
-        // later one, that one is lost.
-        tab = nullptr;
-      }
-    }
-  }
-  if (tab) {
-    P.utab = (const int4 *)tab->dev;
-    P.nunits = tab->nunits;
-    P.nstrips = tab->nstrips;
-    P.H = tab->H;
-  }
-  P.npack = 0;
-  P.nwaves = P.nwx * P.nstrips;
-  P.wrap = g.south_wrap && g.north_wrap;
-  P.first = FIRST ? 1 : 0;
-  P.last = a.last;
-  P.area_weighted = 0;
-  P.bstride = (long long)g.rows * g.nx;
-  for (int t = 0; t < MAX_PK; ++t) P.pk[t] = t < S ? a.pk[t] : 0.0;
-  P.p0 = a.p0;
-  P.c = a.c;
-  dim3 block(256), grid(tab ? (tab->nunits + 1) / 2 : (P.nwx * np + P.nfw + 1) / 2, (unsigned)a.nbatch);
-  P.xcd_per = pl->xcd_remap ? (int)(grid.x / 8) : 0;
-  P.zigzag = 1;
-  bool xe = true;
-  ringc_zip_rows(std::max(P.H, P.fold_rows) + S + 1, S, &xe);
-  if (pl->ringc_zip == 2) xe = true;    // (tuning: 2 = always the early-exit form, 3 = always whole periods)
-  if (pl->ringc_zip == 3) xe = false;
-  if (tab) {
-    if constexpr (sizeof(T) == 8) {   // (f64 only: wet_table)
-      if (grid.x > 0) {   // (a grid that is all land has no pair: k_land_fix writes the whole result)
-        if (xe) hipLaunchKernelGGL((k_ringcz<T, S, FIRST, true, true>), grid, block, 0, s, P);
-        else hipLaunchKernelGGL((k_ringcz<T, S, FIRST, false, true>), grid, block, 0, s, P);
-      }
-    }
-  } else if (xe) {
-    hipLaunchKernelGGL((k_ringcz<T, S, FIRST, true>), grid, block, 0, s, P);
-  } else {
-    hipLaunchKernelGGL((k_ringcz<T, S, FIRST, false>), grid, block, 0, s, P);
-  }
-  GCMF_HIP(hipGetLastError());
-  note_kernel(pl, std::string("gcmf::k_ringcz<") + tyname<T>() + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ", " + (xe ? "true" : "false") + (tab ? ", true>" : ">"), S,
-              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + (tab ? " units=" + std::to_string(tab->nunits) : std::string()));
-  return GCMF_OK;
-}
-
-// k_ringc with the one mid-period exit (see ringc_march)
-template <typename T, int KIND, int S, bool FIRST>
-__global__ __launch_bounds__(256, 1) void k_ringc6(const MultiP<T, T> P) {
-  int bx = blockIdx.x;
-  if (P.xcd_per > 0 && bx < 8 * P.xcd_per) bx = (bx & 7) * P.xcd_per + (bx >> 3);
-  const int wid = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  if (wid >= P.nwaves) return;
-  ringc_walk<T, KIND, S, FIRST, false, true, false>(P, wid);
-}
-
-template <typename T, int KIND, int S, bool FIRST, bool XE = false, bool XE6 = false>
-static int launch_ringc_sf(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
-  constexpr int VEC = 16 / sizeof(T);
-  constexpr int W = 64 * VEC;
-  constexpr int M = (S + VEC - 1) / VEC * VEC;
-  constexpr int WI = W - 2 * M;
-  constexpr int R = RingGeom::R;
-  const Geom &g = pl->g;
-  MultiP<T, T> P;
   P.u0 = (const T *)a.u0;
   P.v0 = (const T *)a.v0;
   P.uo = (T *)a.uo;
@@ -761,83 +628,107 @@ static int launch_ringc_sf(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
   P.rows = g.rows;
   P.out_lo = a.row_lo;
   P.out_hi = a.row_hi;
-  const int nrows = a.row_hi - a.row_lo;
-  if (nrows <= 0 || a.nbatch <= 0) return GCMF_OK;
-  P.nwx = (g.nx + WI - 1) / WI;
-  int H = pl->strip_rows;
-  if (H <= 0) {
-    constexpr int EXITP = (KIND == K_FLUX && !XE) ? (XE6 ? R / 2 : R) : 4;   // rows between two exits of the march
-    const long long want = strips_per_column((long long)P.nwx * a.nbatch, nrows, S, EXITP);
-    H = (int)((nrows + want - 1) / want);
-    if (H < 4) H = 4;   // (short strips for small grids: see k_ring)
-    if (KIND == K_FLUX && !XE) H += (EXITP - (H + 2 * S) % EXITP) % EXITP;   // whole (half) periods (no early exit here): let the padding carry real rows
-  }
-  if (H > nrows) H = nrows;
-  P.H = H;
-  P.nstrips = (nrows + H - 1) / H;
-  P.npack = 0;
-  // (GCMF_MASK_FROM_NAN: whole strips per field -- the packed walk has not been run with one plane of mask bytes per entry)
-  if (!XE6 && a.nbatch > 1 && pl->strip_rows <= 0 && pl->pack_batch && !pl->mask_per_field && (long long)a.nbatch * nrows < (1LL << 30)) {
-    // Packed batch (see ringc_walk): as many runs per window as fill whole rounds of the 1024 wave slots, never longer than a field.
-    // Taken when its rounds x (run + warm-up rows, one field boundary in most runs) beat the whole strips chosen above -- short grids
-    // (the 300-row slab of one of 8 ranks, 16 fields: 626-651 -> 708-710 G; tools/measure_batched_scaling.py).
-    constexpr int EXITP = (KIND == K_FLUX && !XE) ? (XE6 ? R / 2 : R) : 4;
-    auto padded = [&](long long m) { return (m + EXITP - 1) / EXITP * EXITP; };
-    const long long total = (long long)a.nbatch * nrows, slots = std::max(1LL, 1024LL / P.nwx);
-    const long long rounds_u = ((long long)P.nwx * a.nbatch * P.nstrips + 1023) / 1024;
-    const double cost_u = (double)(rounds_u * padded(H + 2 * S)) * (1.0 + 0.04 * (rounds_u - 1));
-    double best = cost_u;
-    long long best_q = 0, best_w = 0;
-    for (long long k = 1; k <= 16; ++k) {
-      const long long w = std::min(total, slots * k);                 // runs per window
-      const long long q = (total + w - 1) / w;                       // rows per run
-      if (q > nrows || q > 320) continue;   // (tall runs lose: 2400 x 3600 x 8 fields as 30 runs of 640 rows per window 768 G against 805 G as whole strips)
-      const long long rounds = (w * P.nwx + 1023) / 1024;
-      const bool crosses = (nrows % q) != 0;                          // (runs aligned with the fields cross nothing)
-      const double cost = (double)(rounds * (padded(q + 2 * S) + (crosses ? padded(2 * S + EXITP / 2) : 0))) * (1.0 + 0.04 * (rounds - 1));
-      if (cost < 0.97 * best) { best = cost; best_q = q; best_w = (total + q - 1) / q; }
-      if (w >= total) break;
-    }
-    if (best_q > 0) {
-      P.H = (int)best_q;
-      P.nstrips = (int)best_w;
-      P.npack = (int)a.nbatch;
-    }
-  }
-  P.nwaves = P.nwx * P.nstrips;
+  P.nwx = c.nwx;
+  P.H = c.H;
+  P.nstrips = c.nstrips;
+  P.npack = c.npack;
+  P.fold_rows = c.fold_rows;
+  P.nfw = c.nfw;
+  P.nwaves = c.nwx * c.nstrips;
   P.wrap = g.south_wrap && g.north_wrap;
-  P.first = FIRST ? 1 : 0;
+  P.first = a.first ? 1 : 0;
   P.last = a.last;
-  P.area_weighted = (KIND == K_FLUX) ? 0 : g.area_weighted;
+  P.area_weighted = (pl->kind == K_FLUX) ? 0 : g.area_weighted;
   P.bstride = (long long)g.rows * g.nx;
-  for (int t = 0; t < MAX_PK; ++t) P.pk[t] = t < S ? a.pk[t] : 0.0;
+  for (int t = 0; t < MAX_PK; ++t) P.pk[t] = t < a.S ? a.pk[t] : 0.0;
   P.p0 = a.p0;
   P.c = a.c;
-  dim3 block(256), grid((P.nwaves + 3) / 4, P.npack > 0 ? 1u : (unsigned)a.nbatch);
-  P.xcd_per = pl->xcd_remap ? (int)(grid.x / 8) : 0;
-  P.zigzag = pl->zigzag;
-  if constexpr (!XE6) {
-    if (P.npack > 0) {
-      hipLaunchKernelGGL((k_ringcp<T, KIND, S, FIRST, XE>), grid, block, 0, s, P);
-      GCMF_HIP(hipGetLastError());
-      note_kernel(pl, std::string("gcmf::k_ringcp<") + tyname<T>() + ", " + std::to_string(KIND) + ", " + std::to_string(S) + ", " +
-                          (FIRST ? "true" : "false") + ", " + (XE ? "true" : "false") + ">", S,
-                  launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows));
-      return GCMF_OK;
+  P.xcd_per = pl->xcd_remap ? (int)(c.grid_x / 8) : 0;
+  P.zigzag = pl->zigzag;   // (k_ringcz's pairs always march away from each other)
+}
+
+template <typename T, int S, bool FIRST>
+static int launch_ringc_zip_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+  const int nrows = a.row_hi - a.row_lo;
+  const bool folds = cut.form == RINGC_ZIP_FOLD;
+  if (cut.pairs < 1 || nrows - cut.fold_rows < 2 * cut.pairs) {
+    set_error("k_ringcz: %d rows cannot be cut into pairs of strips", nrows);
+    return GCMF_ERR_INVALID_ARG;
+  }
+  // (round 7) whole grids with land, a lone field: the pairs cut from the rows of each window that hold anything wet -- the wave slots
+  // of all-land tiles go to the wet part, and every strip gets shorter (wet_table, gcmf_ringc_zip.hip)
+  const WetTable *tab = nullptr;
+  if (sizeof(T) == 8 && pl->wet_now && !folds) {
+    int rc = GCMF_OK;
+    tab = wet_table(pl, a, cut.march, s, &rc);
+    if (rc) return rc;
+    if (tab && !pl->pool_clean) {   // cells no pair owns are read as ghost cells: they must be finite (gcmf_plan::pool_clean)
+      if (FIRST) {                  // (a first launch reads no state: nothing the fill could destroy)
+        GCMF_HIP(hipMemsetAsync(pl->pool_base, 0, pl->pool_bytes, s));
+        pl->pool_clean = true;
+      } else {
+        // A later launch of an application whose FIRST launch took no table (the policy refused that depth, or another kernel ran it):
+        // the planes hold live state, so no fill, and this launch keeps the even cut -- as will the later launches of every such
+        // application, silently (option 2 never gets here: every launch of an eligible call takes its table, the first one too).
+        // clenshaw_cut puts the deepest launches first; where the policy of option 1 refuses those and would take a shallower
+        // later one, that one is lost.
+        tab = nullptr;
+      }
     }
+  }
+  RingcCut c = cut;
+  if (tab) {   // the table's strips instead of the even cut's
+    c.nstrips = tab->nstrips;
+    c.H = tab->H;
+    c.grid_x = (unsigned)((tab->nunits + 1) / 2);
+    c.xe = ringc_zip_exits(tab->H, S, pl->ringc_zip);
+  }
+  MultiP<T, T> P;
+  ringc_params(P, pl, a, c);
+  if (tab) {
+    P.utab = (const int4 *)tab->dev;
+    P.nunits = tab->nunits;
+  }
+  const bool xe = c.xe;
+  dim3 block(256), grid(c.grid_x, c.grid_y);
+  if (tab) {
+    if constexpr (sizeof(T) == 8) {   // (f64 only: wet_table)
+      if (grid.x > 0) {   // (a grid that is all land has no pair: k_land_fix writes the whole result)
+        if (xe) hipLaunchKernelGGL((k_ringcz<T, S, FIRST, true, true>), grid, block, 0, s, P);
+        else hipLaunchKernelGGL((k_ringcz<T, S, FIRST, false, true>), grid, block, 0, s, P);
+      }
+    }
+  } else if (xe) {
+    hipLaunchKernelGGL((k_ringcz<T, S, FIRST, true>), grid, block, 0, s, P);
+  } else {
+    hipLaunchKernelGGL((k_ringcz<T, S, FIRST, false>), grid, block, 0, s, P);
+  }
+  GCMF_HIP(hipGetLastError());
+  note_kernel(pl, std::string("gcmf::k_ringcz<") + tyname<T>() + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ", " + (xe ? "true" : "false") + (tab ? ", true>" : ">"), S,
+              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + (tab ? " units=" + std::to_string(tab->nunits) : std::string()));
+  return GCMF_OK;
+}
+
+// k_ringc / k_ringcs (XE) on whole strips, k_ringcp on a packed batch: as the cut says
+template <typename T, int KIND, int S, bool FIRST, bool XE = false>
+static int launch_ringc_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+  MultiP<T, T> P;
+  ringc_params(P, pl, a, cut);
+  const int nrows = a.row_hi - a.row_lo;
+  dim3 block(256), grid(cut.grid_x, cut.grid_y);
+  if (cut.form == RINGC_PACKED) {
+    hipLaunchKernelGGL((k_ringcp<T, KIND, S, FIRST, XE>), grid, block, 0, s, P);
+    GCMF_HIP(hipGetLastError());
+    note_kernel(pl, std::string("gcmf::k_ringcp<") + tyname<T>() + ", " + std::to_string(KIND) + ", " + std::to_string(S) + ", " +
+                        (FIRST ? "true" : "false") + ", " + (XE ? "true" : "false") + ">", S,
+                launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows));
+    return GCMF_OK;
   }
   if constexpr (XE) {
     hipLaunchKernelGGL((k_ringcs<T, S, FIRST>), grid, block, 0, s, P);
     GCMF_HIP(hipGetLastError());
     note_kernel(pl, std::string("gcmf::k_ringcs<") + tyname<T>() + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
                 launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows));
-    return GCMF_OK;
-  }
-  if constexpr (XE6) {
-    hipLaunchKernelGGL((k_ringc6<T, KIND, S, FIRST>), grid, block, 0, s, P);
-    GCMF_HIP(hipGetLastError());
-    note_kernel(pl, std::string("gcmf::k_ringc6<") + tyname<T>() + ", " + std::to_string(KIND) + ", " + std::to_string(S) + ", " +
-                        (FIRST ? "true" : "false") + ">", S, launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows));
     return GCMF_OK;
   }
   bool own = false;   // (GCMF_MASK_FROM_NAN: the instantiation that adds the entry's offset to its mask row pointers)
@@ -854,27 +745,27 @@ static int launch_ringc_sf(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
 
 // one stencil kind, one state type (their own translation units: gcmf_ringc_<kind>.hip = f64, gcmf_ringc_<kind>_f32.hip = f32 -- the
 // instantiations of a kind compile for four to five minutes in one unit)
-template <int KIND> static int launch_ringc_kind_f32(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
+template <int KIND> static int launch_ringc_kind_f32(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
   // f32 state, four cells per lane, the whole polynomial carried in f32 (f64 result unless GCMF_OUT_F32): the flux kinds since round 3,
   // the REGULAR / land-mask kinds since round 4
   switch (a.S) {
-    case 5: return a.first ? launch_ringc_sf<float, KIND, 5, true>(pl, a, s) : launch_ringc_sf<float, KIND, 5, false>(pl, a, s);
-    case 6: return a.first ? launch_ringc_sf<float, KIND, 6, true>(pl, a, s) : launch_ringc_sf<float, KIND, 6, false>(pl, a, s);
-    case 7: return a.first ? launch_ringc_sf<float, KIND, 7, true>(pl, a, s) : launch_ringc_sf<float, KIND, 7, false>(pl, a, s);
+    case 5: return a.first ? launch_ringc_sf<float, KIND, 5, true>(pl, a, cut, s) : launch_ringc_sf<float, KIND, 5, false>(pl, a, cut, s);
+    case 6: return a.first ? launch_ringc_sf<float, KIND, 6, true>(pl, a, cut, s) : launch_ringc_sf<float, KIND, 6, false>(pl, a, cut, s);
+    case 7: return a.first ? launch_ringc_sf<float, KIND, 7, true>(pl, a, cut, s) : launch_ringc_sf<float, KIND, 7, false>(pl, a, cut, s);
     case 8:   // (never a first launch: clenshaw_cut starts an f32 filter with at most seven levels -- eight spill there)
       if (a.first) break;
-      return launch_ringc_sf<float, KIND, 8, false>(pl, a, s);
+      return launch_ringc_sf<float, KIND, 8, false>(pl, a, cut, s);
   }
   set_error("k_ringc<float>: depth %d%s is not offered", a.S, a.first ? " as a first launch" : "");
   return GCMF_ERR_INVALID_ARG;
 }
 
-template <int KIND> static int launch_ringc_kind_f64(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
+template <int KIND> static int launch_ringc_kind_f64(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
   switch (a.S) {
-    case 5: return a.first ? launch_ringc_sf<double, KIND, 5, true>(pl, a, s) : launch_ringc_sf<double, KIND, 5, false>(pl, a, s);
-    case 6: return a.first ? launch_ringc_sf<double, KIND, 6, true>(pl, a, s) : launch_ringc_sf<double, KIND, 6, false>(pl, a, s);
-    case 7: return a.first ? launch_ringc_sf<double, KIND, 7, true>(pl, a, s) : launch_ringc_sf<double, KIND, 7, false>(pl, a, s);
-    case 8: return a.first ? launch_ringc_sf<double, KIND, 8, true>(pl, a, s) : launch_ringc_sf<double, KIND, 8, false>(pl, a, s);
+    case 5: return a.first ? launch_ringc_sf<double, KIND, 5, true>(pl, a, cut, s) : launch_ringc_sf<double, KIND, 5, false>(pl, a, cut, s);
+    case 6: return a.first ? launch_ringc_sf<double, KIND, 6, true>(pl, a, cut, s) : launch_ringc_sf<double, KIND, 6, false>(pl, a, cut, s);
+    case 7: return a.first ? launch_ringc_sf<double, KIND, 7, true>(pl, a, cut, s) : launch_ringc_sf<double, KIND, 7, false>(pl, a, cut, s);
+    case 8: return a.first ? launch_ringc_sf<double, KIND, 8, true>(pl, a, cut, s) : launch_ringc_sf<double, KIND, 8, false>(pl, a, cut, s);
   }
   return GCMF_ERR_INVALID_ARG;
 }

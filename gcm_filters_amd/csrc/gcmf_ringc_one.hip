@@ -81,8 +81,8 @@ __global__ __launch_bounds__(256, 1) void k_ringc_one(const OneP<S> P) {
       for (int t = 0; t < S; ++t) Q.pk[t] = P.pk[q][t];
       Q.first = (q == 0) ? 1 : 0;
       Q.last = (q == P.npass - 1) ? 1 : 0;
-      if (q == 0) ringc_walk<double, K_FLUX, S, true, false, false, false>(Q, wid);
-      else ringc_walk<double, K_FLUX, S, false, false, false, false>(Q, wid);
+      if (q == 0) ringc_walk<double, K_FLUX, S, true, false, false>(Q, wid);
+      else ringc_walk<double, K_FLUX, S, false, false, false>(Q, wid);
     }
     if (q + 1 < P.npass) ok = one_barrier<S>(P, q) && ok;
   }
@@ -108,44 +108,23 @@ int ringc_one_depth(const gcmf_plan *pl, int n_steps, int64_t nbatch) {
 }
 
 template <int S> static int launch_one(gcmf_plan *pl, const double *p, int n_steps, double c, const void *f, void *out, void *const *pool, hipStream_t s) {
-  constexpr int M = (S + 1) / 2 * 2, WI = 128 - 2 * M, R = RingGeom::R;
   const Geom &g = pl->g;
+  // the strips of k_ringc<double, K_FLUX, S> on a lone field: whole ring periods, no zipped pairs (the passes share one geometry)
+  RingcCutIn in = ringc_cut_in(pl, g.rows, false, 1, S, false);
+  in.ringc_zip = in.ringc_xe_rows = 0;
+  const RingcCut cut = ringc_cut(in);
+  MultiArgs a{};   // (the state planes, the coefficients and first / last are the passes' own: OneP, k_ringc_one)
+  a.fb_in = f;
+  a.fb_out = out;
+  a.row_lo = 0;
+  a.row_hi = g.rows;
+  a.p0 = p[n_steps];
+  a.c = c;
   OneP<S> P{};
   MultiP<double, double> &B = P.base;
-  B.fb_in = (const double *)f;
-  B.fb_out = (double *)out;
-  B.d_out = nullptr;
-  B.cE = (const double *)g.coef[0];
-  B.cN = (const double *)g.coef[1];
-  B.ra = (const double *)g.coef[2];
-  B.zrow = (const double *)pl->zero_row;
-  B.nfb = pl->ring_nfb;
-  B.mbits = g.mbits;
-  B.lbits = (pl->n_land > 0) ? pl->lbits : nullptr;
-  B.area = (const double *)g.area;
-  B.nx = g.nx;
-  B.rows = g.rows;
-  B.out_lo = 0;
-  B.out_hi = g.rows;
-  B.nwx = (g.nx + WI - 1) / WI;
-  const long long want = strips_per_column(B.nwx, g.rows, S, R);   // (as launch_ringc_sf: whole ring periods)
-  int H = (int)((g.rows + want - 1) / want);
-  if (H < 4) H = 4;
-  H += (R - (H + 2 * S) % R) % R;
-  if (H > g.rows) H = g.rows;
-  B.H = H;
-  B.nstrips = (g.rows + H - 1) / H;
-  B.nwaves = B.nwx * B.nstrips;
-  B.npack = 0;
-  B.wrap = g.south_wrap && g.north_wrap;
-  B.area_weighted = 0;
-  B.bstride = (long long)g.rows * g.nx;
-  B.p0 = p[n_steps];
-  B.c = c;
-  B.zigzag = pl->zigzag;
+  ringc_params(B, pl, a, cut);
   P.npass = n_steps / S;
-  P.nwg = (B.nwaves + 3) / 4;
-  B.xcd_per = pl->xcd_remap ? P.nwg / 8 : 0;
+  P.nwg = (int)cut.grid_x;
   int dev = 0, ncu = 0;
   GCMF_HIP(hipGetDevice(&dev));
   GCMF_HIP(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev));

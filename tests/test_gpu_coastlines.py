@@ -104,7 +104,7 @@ FAMILIES = [
        options=_t(ringc_smax=8, ringc_zip=0), env=_t(GCMF_RINGC_XE_ROWS="0", GCMF_ZIGZAG="0")),
     # the early-exit form where it shortens the march (launch_ringc): strips of 22 rows march 40 rows instead of 48
     _f("ringcs", FLUX_KINDS, "f8", WIDE, r"k_ringcs<double, 8, ", kappa=True, tuning=_t(multi_s=8, strip_rows=22), options=_t(ringc_smax=8, ringc_zip=0)),
-    # zipped strips choose their own height (ringc_zip_march refuses a plan with strip_rows set)
+    # zipped strips choose their own height (ringc_cut offers no zipped strips to a plan with strip_rows set)
     _f("ringcz", FLUX_KINDS, "f8", WIDE, r"k_ringcz<double, 8, ", kappa=True, options=_t(ringc_smax=8, ringc_zip=1)),
     _f("ringc9", FLUX_KINDS, "f8", WIDE, r"k_ringc<double, {K}, 9, ", kappa=True, n_steps=36, tuning=_t(multi_s=8, strip_rows=H), options=_t(ringc_zip=0),
        env=_t(GCMF_RINGC_XE_ROWS="0")),

@@ -2,7 +2,7 @@
 for a plan, a polynomial length and a batch, and a caller that runs those depths through gcmf_cheb_multi(GCMF_STEP_CLENSHAW) or
 gcmf_slab_apply_backward gets gcmf_apply's bits.  SlabFilter (distributed.py), the row-block pipeline (host_blocks.py) and C callers rely on
 it.  The plans below sit on both sides of every branch of clenshaw_cut (csrc/gcmf_api_blocks.hip): nine levels per launch on whole flux
-grids (ringc9_ok), on whole tripolar grids whose launches advance the seam themselves (ringc_zip_fold_ok: nx >= 256, nx % 4 == 0, 64 rows,
+grids (ringc9_ok), on whole tripolar grids whose launches advance the seam themselves (ringc_cut's fold strips: nx >= 256, nx % 4 == 0, 64 rows,
 a batch of at most 64 fields that is not packed), on row slabs (option "slab_nines"), the cut search of cache-resident grids, the scalar
 kinds behind plan->clenshaw = 2 and f32 state.  Results are held to gcmf_apply bit for bit and to the oracle (oracle/gcmf_oracle.py)."""
 import ctypes as C

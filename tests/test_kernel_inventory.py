@@ -10,7 +10,6 @@ CSRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 # kernel -> why the sweep does not name it, and where it is covered
 ALLOWLIST = {
-    "k_ringc6": "never instantiated (DESIGN_HISTORY.md); its note_kernel call site is unreachable",
     # plan-time precompute: run by every plan creation; covered by tests/test_gpu_parity.py::test_kernel_vs_reference_zarr
     "k_pre_mask": "plan precompute; tests/test_gpu_parity.py::test_kernel_vs_reference_zarr",
     "k_pre_isolated": "plan precompute; tests/test_gpu_parity.py::test_kernel_vs_reference_zarr; cells cut off from the sea (lakes, a checkerboard, "
