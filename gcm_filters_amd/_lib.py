@@ -36,6 +36,8 @@ EXPORTS = [
     "gcmf_slab_apply_backward", "gcmf_slab_backward_vec_supported", "gcmf_slab_apply_backward_vec", "gcmf_resident_supported", "gcmf_resident_levels", "gcmf_p2p_create", "gcmf_p2p_export", "gcmf_p2p_connect", "gcmf_p2p_start", "gcmf_p2p_finish", "gcmf_p2p_status", "gcmf_p2p_destroy", "gcmf_p2p_guard", "gcmf_p2p_seq", "gcmf_p2p_set_timeout_ms", "gcmf_p2p_debug_skip_post",
     "gcmf_plan_last_path", "gcmf_resident_status",
 ]
+# the entry points of stacked plans (include/gcmf.h: gcmf_plan_create_levels), a list of their own; load() binds both lists
+EXPORTS_LEVELS = ["gcmf_plan_create_levels", "gcmf_plan_levels"]
 PATH_NAMES = {0: None, 1: "resident", 2: "strips", 3: "resident-lock-busy", 4: "resident-disabled"}
 RESIDENT_STATES = {0: "ok", 1: "lock-busy", 2: "disabled", 3: "off"}
 PLAN_SELF_RING, PLAN_SKIP_KAPPA_ONE = 0x1, 0x2
@@ -100,6 +102,10 @@ def load() -> C.CDLL:
         vp, vpp = C.c_void_p, C.POINTER(C.c_void_p)
         lib.gcmf_plan_create.argtypes = [C.POINTER(PlanDesc), vpp, C.c_int, vpp]
         lib.gcmf_plan_create.restype = C.c_int
+        lib.gcmf_plan_create_levels.argtypes = [C.POINTER(PlanDesc), vpp, C.POINTER(C.c_int64), C.c_int, C.c_int64, vpp]
+        lib.gcmf_plan_create_levels.restype = C.c_int
+        lib.gcmf_plan_levels.argtypes = [vp]
+        lib.gcmf_plan_levels.restype = C.c_int64
         lib.gcmf_plan_destroy.argtypes = [vp]
         lib.gcmf_plan_destroy.restype = None
         for name in ("gcmf_grid_nplanes", "gcmf_grid_ncomp", "gcmf_grid_is_dimensional", "gcmf_grid_is_tripolar"):
@@ -277,10 +283,53 @@ class Plan:
         st = lib.gcmf_plan_create(C.byref(desc), _ptr_array(ptrs), len(ptrs), C.byref(out))
         del keep
         check(st)
-        self._h = out
+        self._adopt(out)
+
+    def _adopt(self, handle):
+        self._h = handle
         ra, fo, ro = C.c_int64(), C.c_int64(), C.c_int64()
-        check(lib.gcmf_plan_rows(self._h, C.byref(ra), C.byref(fo), C.byref(ro)))
+        check(load().gcmf_plan_rows(self._h, C.byref(ra), C.byref(fo), C.byref(ro)))
         self.rows_alloc, self.first_owned, self.rows_owned = ra.value, fo.value, ro.value
+
+    @classmethod
+    def create_levels(cls, grid_type: int, dtype: int, ny: int, nx: int, planes: Sequence, plane_levels: Sequence[int], nlev: int, *,
+                      device: int = 0, planes_on_device: bool = False, skip_kappa_one: bool = False) -> "Plan":
+        """A STACKED plan (gcmf_plan_create_levels): grid planes with a level axis, planes[i] of shape (plane_levels[i], ny, nx) --
+        (ny, nx) will do where plane_levels[i] is 1 -- with plane_levels[i] = 1 (shared by all levels) or nlev.  apply() then filters
+        batch entry b with the grid of level b % nlev.  float64 IRREGULAR_WITH_LAND / MOM5U / MOM5T whole grids; anything else raises
+        GcmfError(ERR_UNSUPPORTED)."""
+        lib = load()
+        self = cls.__new__(cls)
+        self._h = None
+        self.grid_type, self.dtype, self.ny, self.nx, self.device = int(grid_type), int(dtype), int(ny), int(nx), int(device)
+        self.ncomp = lib.gcmf_grid_ncomp(self.grid_type)
+        nlev = int(nlev)
+        plane_levels = [int(n) for n in plane_levels]
+        if len(plane_levels) != len(planes):
+            raise ValueError("create_levels: one entry of plane_levels per grid plane")
+        desc = PlanDesc(self.grid_type, self.dtype, self.ny, self.nx, 0, self.ny, 0, self.device, 1 if planes_on_device else 0,
+                        PLAN_SKIP_KAPPA_ONE if skip_kappa_one else 0)
+        if planes_on_device:
+            ptrs = [int(p) for p in planes]
+            keep = None
+        else:
+            keep = [np.ascontiguousarray(p, dtype=np_dtype(self.dtype)) for p in planes]
+            for a, n in zip(keep, plane_levels):
+                if a.shape != (n, self.ny, self.nx) and not (n == 1 and a.shape == (self.ny, self.nx)):
+                    raise ValueError(f"grid plane has shape {a.shape}, expected {(n, self.ny, self.nx)}")
+            ptrs = [a.ctypes.data for a in keep]
+        out = C.c_void_p()
+        st = lib.gcmf_plan_create_levels(C.byref(desc), _ptr_array(ptrs), (C.c_int64 * max(len(plane_levels), 1))(*plane_levels),
+                                         len(ptrs), nlev, C.byref(out))
+        del keep
+        check(st)
+        self._adopt(out)
+        return self
+
+    @property
+    def levels(self) -> int:
+        """Levels of a stacked plan (create_levels); 1 for an ordinary plan."""
+        return int(load().gcmf_plan_levels(self._h))
 
     # -- lifetime ------------------------------------------------------------------------------
     def close(self):
@@ -457,7 +506,7 @@ class Plan:
         for tok in buf.value.decode().split():
             k, _, v = tok.partition("=")
             out[k] = v if "x" in v else int(v)
-        return out
+        return out   # (+ "units": a wet-row table's pairs; "levels": a stacked plan's)
 
     def last_wet_units(self) -> int:
         """Pairs of strips of the kernel last_kernel() named if k_ringcz cut them from the wet rows of each window (option "wet_rows"; 0: a grid

@@ -101,6 +101,7 @@ static int launch_ringc(gcmf_plan *pl, const MultiArgs &m, const RingcCut &cut, 
     case K_REG: return launch_ringc_reg(pl, m, cut, s);
     case K_MASK: return launch_ringc_maskz(pl, m, cut, s);
     case K_FLUX:
+      if (pl->stacked) return launch_ringc_levels(pl, m, cut, s);   // (always the plain strips: ringc_cut)
       if (cut.xe) return launch_ringc_flux_slab(pl, m, cut, s);   // (k_ringcs, or k_ringcp's early-exit form)
       if (m.S == 9) return launch_ringc_flux9(pl, m, cut, s);
       return launch_ringc_flux(pl, m, cut, s);
@@ -204,9 +205,10 @@ int land_fix_tail(gcmf_plan *pl, const double *p, int n_steps, double c, const v
 }
 // Stages the raw grid planes on the device (temporaries, unless they are there already), folds them into the plan (precompute), frees
 // the temporaries; scalar plans also get a row of zeros for k_ring.
-static int stage_grid(gcmf_plan *pl, const void *const *planes, int nplanes) {
+// plane_levels (stacked plans, gcmf_plan_create_levels): plane k is plane_levels[k] planes long
+static int stage_grid(gcmf_plan *pl, const void *const *planes, int nplanes, const int64_t *plane_levels = nullptr) {
   const gcmf_plan_desc &d = pl->d;
-  const size_t plane_bytes = (size_t)d.ny * d.nx * dtype_size(d.dtype);
+  const size_t one_plane = (size_t)d.ny * d.nx * dtype_size(d.dtype);
   std::vector<const void *> dplanes(nplanes, nullptr);
   std::vector<void *> staged;
   int rc = GCMF_OK;
@@ -215,9 +217,10 @@ static int stage_grid(gcmf_plan *pl, const void *const *planes, int nplanes) {
       dplanes[k] = planes[k];
       continue;
     }
+    const size_t plane_bytes = one_plane * (size_t)(plane_levels ? plane_levels[k] : 1);
     int dup = -1;  // the same host array passed twice (e.g. wet_mask_t is wet_mask_q) is uploaded once
     for (int q = 0; q < k; ++q)
-      if (planes[q] == planes[k]) dup = q;
+      if (planes[q] == planes[k] && (!plane_levels || plane_levels[q] == plane_levels[k])) dup = q;
     if (dup >= 0) {
       dplanes[k] = dplanes[dup];
       continue;
@@ -234,7 +237,8 @@ static int stage_grid(gcmf_plan *pl, const void *const *planes, int nplanes) {
     }
     dplanes[k] = p;
   }
-  if (rc == GCMF_OK) rc = precompute(pl, dplanes.data(), d.planes_on_device ? nullptr : planes);
+  if (rc == GCMF_OK)
+    rc = pl->stacked ? precompute_levels(pl, dplanes.data(), plane_levels) : precompute(pl, dplanes.data(), d.planes_on_device ? nullptr : planes);
   if (rc == GCMF_OK && pl->ncomp == 1) {  // a row of zeros for k_ring
     void *z = nullptr;
     const size_t zb = ((size_t)d.nx + 64) * 8 + 256;
@@ -304,7 +308,9 @@ void gcmf_plan_destroy(gcmf_plan *pl) {
   delete pl;
 }
 
-int gcmf_plan_create(const gcmf_plan_desc *desc, const void *const *planes, int nplanes, gcmf_plan **out) {
+// gcmf_plan_create (plane_levels == nullptr) and gcmf_plan_create_levels
+static int plan_create(const gcmf_plan_desc *desc, const void *const *planes, const int64_t *plane_levels, int nplanes, int64_t nlev,
+                       gcmf_plan **out) {
   if (!desc || !out) {
     set_error("gcmf_plan_create: null argument");
     return GCMF_ERR_INVALID_ARG;
@@ -348,6 +354,8 @@ int gcmf_plan_create(const gcmf_plan_desc *desc, const void *const *planes, int 
 
   gcmf_plan *pl = new gcmf_plan();
   pl->d = *desc;
+  pl->stacked = plane_levels != nullptr;
+  pl->nlev = nlev;
   pl->kind = gi.kind;
   pl->ncomp = gi.ncomp;
   pl->tripolar = gi.tripolar;
@@ -415,11 +423,55 @@ int gcmf_plan_create(const gcmf_plan_desc *desc, const void *const *planes, int 
   PLAN_HIP(hipEventCreate(&pl->ev1));
   PLAN_HIP(hipEventCreateWithFlags(&pl->ev_busy, hipEventDisableTiming));
 
-  if (int rc = stage_grid(pl, planes, nplanes)) return fail(rc);
+  if (int rc = stage_grid(pl, planes, nplanes, plane_levels)) return fail(rc);
   *out = pl;
   return GCMF_OK;
 #undef PLAN_HIP
 }
+
+int gcmf_plan_create(const gcmf_plan_desc *desc, const void *const *planes, int nplanes, gcmf_plan **out) {
+  return plan_create(desc, planes, nullptr, nplanes, 1, out);
+}
+
+int gcmf_plan_create_levels(const gcmf_plan_desc *desc, const void *const *planes, const int64_t *plane_levels, int nplanes, int64_t nlev,
+                            gcmf_plan **out) {
+  if (!desc || !out || !plane_levels || nplanes < 1) {
+    set_error("gcmf_plan_create_levels: null argument");
+    return GCMF_ERR_INVALID_ARG;
+  }
+  *out = nullptr;
+  GridInfo gi;
+  if (!grid_info(desc->grid_type, gi)) {
+    set_error("gcmf_plan_create_levels: unknown grid_type %d", desc->grid_type);
+    return GCMF_ERR_INVALID_ARG;
+  }
+  if (gi.kind != K_FLUX || gi.tripolar) {
+    set_error("gcmf_plan_create_levels: stacked plans exist for IRREGULAR_WITH_LAND, MOM5U and MOM5T (flux form, no tripole seam), not "
+              "for grid type %d: build one plan per level", desc->grid_type);
+    return GCMF_ERR_UNSUPPORTED;
+  }
+  if (desc->dtype != GCMF_F64) {
+    set_error("gcmf_plan_create_levels: stacked plans compute in f64 (dtype %d given): build one plan per level", desc->dtype);
+    return GCMF_ERR_UNSUPPORTED;
+  }
+  if (desc->row_begin != 0 || desc->row_end != desc->ny || (desc->flags & GCMF_PLAN_SELF_RING)) {
+    set_error("gcmf_plan_create_levels: stacked plans cover the whole grid (rows [%lld, %lld) of %lld%s given)", (long long)desc->row_begin,
+              (long long)desc->row_end, (long long)desc->ny, (desc->flags & GCMF_PLAN_SELF_RING) ? ", GCMF_PLAN_SELF_RING" : "");
+    return GCMF_ERR_UNSUPPORTED;
+  }
+  if (nlev < 1 || nlev > 32768) {
+    set_error("gcmf_plan_create_levels: %lld levels (1 .. 32768)", (long long)nlev);
+    return GCMF_ERR_INVALID_ARG;
+  }
+  for (int k = 0; k < nplanes; ++k)
+    if (plane_levels[k] != 1 && plane_levels[k] != nlev) {
+      set_error("gcmf_plan_create_levels: grid plane %d has %lld levels, neither 1 nor %lld", k, (long long)plane_levels[k], (long long)nlev);
+      return GCMF_ERR_INVALID_ARG;
+    }
+  return plan_create(desc, planes, plane_levels, nplanes, nlev, out);
+}
+
+int64_t gcmf_plan_levels(const gcmf_plan *pl) { return pl ? pl->nlev : 0; }
 
 int gcmf_plan_rows(const gcmf_plan *pl, int64_t *rows_alloc, int64_t *first_owned, int64_t *rows_owned) {
   if (!pl) return GCMF_ERR_INVALID_ARG;
@@ -528,7 +580,7 @@ static int sched_backward_scalar(ApplyCtx &x, const int *depths, int n_clen, boo
     gcmf_plan *pl;
     ~WetNow() { pl->wet_now = false; }
   } wet_guard{pl};
-  pl->wet_now = pl->wet_rows > 0 && x.nbatch == 1 && !pl->mask_per_field && pl->full && !pl->g.fold && pl->kind == K_FLUX &&
+  pl->wet_now = pl->wet_rows > 0 && x.nbatch == 1 && !pl->mask_per_field && !pl->stacked && pl->full && !pl->g.fold && pl->kind == K_FLUX &&
                 pl->d.dtype == GCMF_F64 && pl->n_land > 0 && pl->pool_bytes > 0;
   pl->pool_clean = pl->wet_now && was_clean;
   for (int q = 0, lvl = 1; q < n_clen; lvl += depths[q++]) {
@@ -735,7 +787,13 @@ static int run_schedule(ApplyCtx &x, uint32_t flags, bool use_multi, bool use_vm
   pl->pool_clean = false;
   bool resident = false;
   int path = GCMF_PATH_STRIPS;
-  if (n_clen > 0 && x.nbatch == 1 && !(flags & GCMF_NO_RESIDENT) && !pl->mask_per_field) {   // (the on-chip kernel reads the plan's own mask)
+  if (pl->stacked && n_clen <= 0) {   // (run_whole has refused GCMF_FORWARD_RECURRENCE)
+    set_error("gcmf_apply: a stacked plan (gcmf_plan_create_levels) runs the backward evaluation only, which is not on offer for this plan "
+              "and a polynomial of %d steps (gcmf_clenshaw_cut_batch returns 0): build one plan per level", x.n_steps);
+    return GCMF_ERR_UNSUPPORTED;
+  }
+  // (the on-chip kernel reads the plan's own mask, and one level's planes)
+  if (n_clen > 0 && x.nbatch == 1 && !(flags & GCMF_NO_RESIDENT) && !pl->mask_per_field && !pl->stacked) {
     int why = GCMF_RESIDENT_OFF;
     resident = resident_supported(pl, 0, x.rows, std::min(x.n_steps, 64), x.n_steps, &why);   // (small whole grids; GCMF_RESIDENT=1: whatever fits)
     if (!resident && why == GCMF_RESIDENT_LOCK_BUSY) path = GCMF_PATH_STRIPS_LOCK_BUSY;
@@ -748,7 +806,7 @@ static int run_schedule(ApplyCtx &x, uint32_t flags, bool use_multi, bool use_vm
     int rc = GCMF_OK;
     if (resident)
       rc = sched_resident(x);
-    else if ((flags & GCMF_NO_RESIDENT) || pl->mask_per_field || ringc_one_depth(pl, x.n_steps, x.nbatch) <= 0 || !sched_single_launch(x))
+    else if ((flags & GCMF_NO_RESIDENT) || pl->mask_per_field || pl->stacked || ringc_one_depth(pl, x.n_steps, x.nbatch) <= 0 || !sched_single_launch(x))
       rc = sched_backward_scalar(x, depths, n_clen, was_clean);
     if (rc || pl->n_land == 0) return rc;
     // the isolated cells' own polynomial (forward recurrence, as the reference computes it)
@@ -945,6 +1003,7 @@ static int run_host_pipelined(gcmf_plan *pl, const double *p, int n_steps, doubl
     if (ch == 0 && pl->timing) GCMF_HIP(hipEventRecord(pl->ev0, s_cmp));
     const void *din[2] = {In(slot, 0), nc > 1 ? In(slot, 1) : nullptr};
     void *dout[2] = {Out(slot, 0), nc > 1 ? Out(slot, 1) : nullptr};
+    pl->entry0 = ch * chunk_nb;   // (stacked plans: the chunk's entry b is entry ch * chunk_nb + b of the call)
     int r = run_whole_locked(pl, p, n_steps, c, din, dout, nb, dflags, (void *)s_cmp, lapl_only, false);
     if (r) return r;
     if (ch == nchunks - 1 && pl->timing) GCMF_HIP(hipEventRecord(pl->ev1, s_cmp));
@@ -1022,9 +1081,26 @@ static int run_whole(gcmf_plan *pl, const double *p, int n_steps, double c, cons
     set_error("gcmf_apply / gcmf_laplacian need a plan covering the whole grid; use gcmf_cheb_step on row slabs");
     return GCMF_ERR_INVALID_ARG;
   }
+  if (pl->stacked) {   // (GCMF_MASK_FROM_NAN: refused above, the flux kinds have no mask bytes)
+    if (lapl_only) {
+      set_error("gcmf_laplacian: not available on a stacked plan (gcmf_plan_create_levels): build one plan per level");
+      return GCMF_ERR_UNSUPPORTED;
+    }
+    if (flags & GCMF_FORWARD_RECURRENCE) {
+      set_error("gcmf_apply: GCMF_FORWARD_RECURRENCE is not available on a stacked plan (gcmf_plan_create_levels), whose levels only the "
+                "backward evaluation's strips address: build one plan per level");
+      return GCMF_ERR_UNSUPPORTED;
+    }
+    if (nbatch % pl->nlev) {
+      set_error("gcmf_apply: a stacked plan of %lld levels takes batches that are multiples of it (entry b runs on level b %% nlev), not %lld",
+                (long long)pl->nlev, (long long)nbatch);
+      return GCMF_ERR_INVALID_ARG;
+    }
+  }
   if (nbatch == 0) return GCMF_OK;
   std::lock_guard<std::mutex> lk(pl->mu);
   GCMF_HIP(hipSetDevice(pl->d.device));
+  pl->entry0 = 0;
   if (!(flags & GCMF_DEVICE_PTRS) && nbatch > 1 && pl->host_chunk_bytes > 0) {
     const size_t entry = (size_t)pl->d.ny * pl->d.nx * dtype_size(pl->d.dtype);
     int64_t chunk_nb = (int64_t)(pl->host_chunk_bytes / entry);
@@ -1047,6 +1123,7 @@ static int run_whole(gcmf_plan *pl, const double *p, int n_steps, double c, cons
       in2[k] = (const char *)in[k] + (size_t)b0 * cell * ts;
       out2[k] = (char *)out[k] + (size_t)b0 * cell * fbs;
     }
+    pl->entry0 = b0;
     int rc = run_whole_locked(pl, p, n_steps, c, in2, out2, nb, flags, stream, lapl_only, true);
     if (rc) return rc;
     ms_total += pl->last_ms;

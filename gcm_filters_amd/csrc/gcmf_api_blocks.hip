@@ -21,6 +21,14 @@ static bool refuse_mask_from_nan(uint32_t flags, const char *who) {
   return true;
 }
 
+// ... and a stacked plan (gcmf_plan_create_levels): only gcmf_apply's backward strips address its levels
+static bool refuse_stacked(const gcmf_plan *pl, const char *who) {
+  if (!pl || !pl->stacked) return false;
+  set_error("%s: not available on a stacked plan (gcmf_plan_create_levels), whose coefficient planes have a level axis that only "
+            "gcmf_apply's backward strip launches address: build one plan per level", who);
+  return true;
+}
+
 // Nine levels per launch (k_ringc<double, K_FLUX, 9>): whole f64 flux-form grids without a tripole seam (the seam's k_fold_band and the
 // slabs' early-exit form stop at eight), tall enough for the deeper ghost zone.
 bool ringc9_ok(const gcmf_plan *pl) {
@@ -80,7 +88,7 @@ int clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, 
   const bool nines_full = ringc9_ok(pl) || ringc9_fold_ok(pl, nbatch, 0, pl->g.rows), nines = nines_full || ringc9_slab_ok(pl);
   if (!(n_steps >= 10 || (n_steps >= 5 && n_steps <= 8) || (n_steps == 9 && nines))) return 0;
   int smax = pl->ringc_smax;
-  if (!smax && nbatch == 1 && nines_full && pl->ringc_zip && (long long)pl->g.rows * pl->g.nx <= 2500000LL && n_steps >= 10) {
+  if (!smax && nbatch == 1 && !pl->stacked && nines_full && pl->ringc_zip && (long long)pl->g.rows * pl->g.nx <= 2500000LL && n_steps >= 10) {
     // Whole grids that live in the caches and run k_ringcz (1/4-degree grids): a launch is paced by the rows its strips march, not by the
     // bytes it moves, so fewer launches are not always faster -- a strip marches H + S + 1 rows whose cost grows with S, and fewer
     // levels mean narrower ghost columns (sometimes a window less).  Measured (experiments/scripts/zip_ab.py, us per launch):
@@ -157,6 +165,7 @@ int gcmf_cheb_step(gcmf_plan *pl, const void *const *t1, const void *const *t2, 
                    void *const *t0, void *const *fbar_out, double coef0, double coef1, double c, uint32_t mode,
                    uint32_t flags, int64_t nbatch, int64_t row_lo, int64_t row_hi, void *stream) {
   if (refuse_mask_from_nan(flags, "gcmf_cheb_step")) return GCMF_ERR_UNSUPPORTED;
+  if (refuse_stacked(pl, "gcmf_cheb_step")) return GCMF_ERR_UNSUPPORTED;
   if (!pl || !t1 || !fbar_out) {
     set_error("gcmf_cheb_step: null argument");
     return GCMF_ERR_INVALID_ARG;
@@ -204,6 +213,7 @@ int gcmf_cheb_multi(gcmf_plan *pl, const void *u, const void *v, void *uo, void 
                     void *fbar_out, const double *pk, int S, double p0, double c, uint32_t mode, uint32_t flags,
                     int64_t nbatch, int64_t row_lo, int64_t row_hi, void *stream) {
   if (refuse_mask_from_nan(flags, "gcmf_cheb_multi")) return GCMF_ERR_UNSUPPORTED;
+  if (refuse_stacked(pl, "gcmf_cheb_multi")) return GCMF_ERR_UNSUPPORTED;
   if (pl && pk && (mode & GCMF_STEP_CLENSHAW)) {
     // S levels of the backward evaluation on rows [row_lo, row_hi): (u, v) = (b_{k+1}, b_{k+2}) (FIRST: unused, the launch forms
     // b_n = p0 * f itself), fbar_in = the constant input f, pk[t] = coefficient of level t + 1, LAST: fbar_out = the result
@@ -265,7 +275,7 @@ int gcmf_cheb_multi(gcmf_plan *pl, const void *u, const void *v, void *uo, void 
 }
 
 int gcmf_resident_supported(const gcmf_plan *pl, int64_t row_lo, int64_t row_hi, int L) {
-  if (!pl) return 0;
+  if (!pl || pl->stacked) return 0;
   (void)hipSetDevice(pl->d.device);
   return resident_fits(pl, (int)row_lo, (int)row_hi, L) ? 1 : 0;
 }
@@ -276,6 +286,7 @@ int gcmf_resident_supported(const gcmf_plan *pl, int64_t row_lo, int64_t row_hi,
 // same levels run through gcmf_cheb_multi(GCMF_STEP_CLENSHAW) in launches of 5..8.
 int gcmf_resident_levels(gcmf_plan *pl, const void *u, const void *v, void *uo, void *vo, const void *f, void *out, const double *pk, int L,
                          double p0, double c, uint32_t mode, int64_t row_lo, int64_t row_hi, void *stream) {
+  if (refuse_stacked(pl, "gcmf_resident_levels")) return GCMF_ERR_UNSUPPORTED;
   if (!pl || !pk || !f || L < 1) {
     set_error("gcmf_resident_levels: null argument");
     return GCMF_ERR_INVALID_ARG;
@@ -303,6 +314,7 @@ int gcmf_cheb_multi_vec(gcmf_plan *pl, const void *const *u, const void *const *
                         const void *const *fbar_in, void *const *fbar_out, const double *pk, int S, double p0, double c,
                         uint32_t mode, uint32_t flags, int64_t nbatch, int64_t row_lo, int64_t row_hi, void *stream) {
   if (refuse_mask_from_nan(flags, "gcmf_cheb_multi_vec")) return GCMF_ERR_UNSUPPORTED;
+  if (refuse_stacked(pl, "gcmf_cheb_multi_vec")) return GCMF_ERR_UNSUPPORTED;
   if (!pl || !u || !fbar_out || !pk) {
     set_error("gcmf_cheb_multi_vec: null argument");
     return GCMF_ERR_INVALID_ARG;
@@ -345,6 +357,7 @@ int gcmf_cheb_multi_vec(gcmf_plan *pl, const void *const *u, const void *const *
 int gcmf_has_land(const gcmf_plan *pl) { return land_ok(pl, 0) ? 1 : 0; }
 
 int gcmf_zero_land(gcmf_plan *pl, void *const *a, void *const *b, int64_t nbatch, void *stream) {
+  if (refuse_stacked(pl, "gcmf_zero_land")) return GCMF_ERR_UNSUPPORTED;
   if (!pl || !a || !b || !a[0] || !b[0] || nbatch < 1) return GCMF_ERR_INVALID_ARG;
   if (!land_ok(pl, 0)) return GCMF_ERR_UNSUPPORTED;
   std::lock_guard<std::mutex> lk(pl->mu);
@@ -355,6 +368,7 @@ int gcmf_zero_land(gcmf_plan *pl, void *const *a, void *const *b, int64_t nbatch
 int gcmf_land_fix(gcmf_plan *pl, const double *p, int n_steps, double c, const void *const *in, void *const *out,
                   int64_t nbatch, uint32_t flags, void *stream) {
   if (refuse_mask_from_nan(flags, "gcmf_land_fix")) return GCMF_ERR_UNSUPPORTED;
+  if (refuse_stacked(pl, "gcmf_land_fix")) return GCMF_ERR_UNSUPPORTED;
   if (!pl || !p || !in || !out || !in[0] || !out[0] || n_steps < 1 || nbatch < 1) return GCMF_ERR_INVALID_ARG;
   if (!land_ok(pl, n_steps)) return GCMF_ERR_UNSUPPORTED;
   std::lock_guard<std::mutex> lk(pl->mu);
@@ -376,6 +390,7 @@ int gcmf_slab_apply_backward(gcmf_plan *pl, gcmf_comm *comm, gcmf_p2p *p2p, int 
                              const int *cut, int ncut, void *X, void *const *pool, void *out, int64_t nbatch, int halo, int overlap,
                              uint32_t flags, void *stream) {
   if (refuse_mask_from_nan(flags, "gcmf_slab_apply_backward")) return GCMF_ERR_UNSUPPORTED;
+  if (refuse_stacked(pl, "gcmf_slab_apply_backward")) return GCMF_ERR_UNSUPPORTED;
   if (!pl || !p || !cut || ncut < 1 || !X || !pool || !out || nbatch < 1 || pl->ncomp != 1) {
     set_error("gcmf_slab_apply_backward: bad argument");
     return GCMF_ERR_INVALID_ARG;
@@ -556,6 +571,7 @@ int gcmf_slab_backward_vec_supported(const gcmf_plan *pl, int64_t nbatch, int ha
 int gcmf_slab_apply_backward_vec(gcmf_plan *pl, gcmf_comm *comm, gcmf_p2p *p2p, int south, int north, const double *p, int n_steps, double c,
                                  void *const *X, void *const *pool, void *const *out, int64_t nbatch, int halo, uint32_t flags, void *stream) {
   if (refuse_mask_from_nan(flags, "gcmf_slab_apply_backward_vec")) return GCMF_ERR_UNSUPPORTED;
+  if (refuse_stacked(pl, "gcmf_slab_apply_backward_vec")) return GCMF_ERR_UNSUPPORTED;
   if (!pl || !p || !X || !pool || !out || !X[0] || !X[1] || !out[0] || !out[1] || nbatch < 1 || n_steps < 2) {
     set_error("gcmf_slab_apply_backward_vec: bad argument");
     return GCMF_ERR_INVALID_ARG;
@@ -627,6 +643,7 @@ int gcmf_slab_apply_backward_vec(gcmf_plan *pl, gcmf_comm *comm, gcmf_p2p *p2p, 
 
 int gcmf_prepare(gcmf_plan *pl, const void *const *in, void *const *out, int64_t nbatch, int64_t row_lo,
                  int64_t row_hi, void *stream) {
+  if (refuse_stacked(pl, "gcmf_prepare")) return GCMF_ERR_UNSUPPORTED;
   if (!pl || !in || !out) return GCMF_ERR_INVALID_ARG;
   if (row_lo < 0 || row_hi > pl->rows_alloc || row_lo > row_hi) return GCMF_ERR_INVALID_ARG;
   std::lock_guard<std::mutex> lk(pl->mu);

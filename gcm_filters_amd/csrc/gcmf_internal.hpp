@@ -181,6 +181,14 @@ struct gcmf_plan {
   // Everything that launches holds the mutex; the lock-free queries (land_ok in gcmf_has_land, clenshaw_cut, resident_fits) may see the
   // call's values from another thread -- include/gcmf.h tells callers not to race them with a flagged call.
   int mask_per_field = 0;
+  // A STACKED plan (gcmf_plan_create_levels): g.coef[0..2] and lbits hold nlev planes of the whole grid, one after the other, and batch
+  // entry b of a gcmf_apply call is filtered with level b % nlev.  Only the plain strips of the backward evaluation know the level axis
+  // (k_ringc<..., LV>, k_land_fix): every other schedule, the building blocks and gcmf_laplacian refuse such a plan.  entry0: the index,
+  // within the caller's batch, of the first entry of the chunk that runs now (the host pipeline and very long batches cut a call into
+  // chunks whose boundaries need not be multiples of nlev); written and read under the plan's mutex.
+  bool stacked = false;
+  int64_t nlev = 1;
+  int64_t entry0 = 0;
   int zero_land = 1;      // env GCMF_ZERO_LAND=0 turns it off
   int ring = 1;           // env GCMF_RING=0: deep launches stay with k_flux_multi2 / k_scalar_multi
   unsigned *ring_nfb = nullptr;    // device counter behind gcmf_ring_fallbacks (lives behind zero_row)
@@ -257,12 +265,13 @@ int launch_ring_flux_f32(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);   //
 // (gcmf_ringc_cut.hpp), which the launchers apply: advance_multi asks once and picks the launcher by cut.form
 inline RingcCutIn ringc_cut_in(const gcmf_plan *pl, int rows, bool seam, int64_t nbatch, int S, bool band_beside) {
   return RingcCutIn{pl->g.nx, rows, seam, (long long)nbatch, S, pl->d.dtype == GCMF_F64, pl->kind, band_beside, pl->mask_per_field != 0,
-                    pl->strip_rows, pl->ringc_xe_rows, pl->ringc_zip, pl->zip_fold, pl->pack_batch};
+                    pl->strip_rows, pl->ringc_xe_rows, pl->ringc_zip, pl->zip_fold, pl->pack_batch, pl->stacked};
 }
 int launch_ringc_reg(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
 int launch_ringc_maskz(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
 int launch_ringc_flux(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
 int launch_ringc_flux9(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // nine levels: whole f64 flux grids without a seam (gcmf_ringc_flux9.hip)
+int launch_ringc_levels(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // a stacked plan's plain strips (gcmf_ringc_levels.hip)
 int launch_ringc_flux_slab(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // no seam's band beside, short strips: early exits (k_ringcs)
 int launch_ringc_flux_slab_f32(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
 int launch_ringc_zip(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // f64 flux plans: pairs of strips zipped at a shared seam, fold strips at the tripole seam (k_ringcz, gcmf_ringc_zip.hip)
@@ -322,6 +331,8 @@ int launch_land_fix(gcmf_plan *pl, const void *in, void *out, const double *dp, 
                     int64_t nbatch, hipStream_t s);
 // plan-time precompute (gcmf_precompute.hip): fills pl->g from the raw global planes (device pointers)
 int precompute(gcmf_plan *pl, const void *const *dplanes, const void *const *hplanes_or_null);
+// ... of a stacked plan (f64 flux kinds without a seam, whole grid): plane k holds plane_levels[k] (1 or pl->nlev) planes
+int precompute_levels(gcmf_plan *pl, const void *const *dplanes, const int64_t *plane_levels);
 // GCMF_MASK_FROM_NAN: the mask bytes of every entry of a batch, from the plan's own bytes `wet` and the entries' NaNs (k_pre_mask)
 int launch_field_masks(gcmf_plan *pl, const uint8_t *wet, const void *fields, uint8_t *bits, int64_t nbatch, hipStream_t s);
 }  // namespace gcmf

@@ -9,7 +9,10 @@
 
 namespace gcmf {
 
-template <typename T, typename FB, bool FUSED>
+// LV: a stacked plan (gcmf_plan_create_levels) -- lbits holds nlev planes, one per level, and entry b reads plane (lev0 + b) % nlev;
+// per_field = nlev | lev0 << 16 (nlev <= 32768).  An instantiation of its own: as a runtime branch in the one kernel (with its second
+// 64-bit division) BASELINE config 3 measured 0.7 % slower, 0.747 against 0.741 ms per application, three alternating runs each
+template <typename T, typename FB, bool FUSED, bool LV = false>
 __global__ __launch_bounds__(256) void k_land_fix(const T *in, FB *out, const uint8_t *lbits, const T *area,
                                                   const double *p, int n_steps, double c_, long long ncell,
                                                   long long ntotal, int per_field) {
@@ -21,7 +24,9 @@ __global__ __launch_bounds__(256) void k_land_fix(const T *in, FB *out, const ui
   // dependency chains per lane; cells that do exchange with neighbours are computed along and not stored
   for (long long q4 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; q4 < ntotal; q4 += (long long)gridDim.x * blockDim.x * 4) {
     const long long cell = q4 % ncell;
-    const unsigned m = *reinterpret_cast<const unsigned *>(lbits + (per_field ? q4 : cell));   // (per_field: every entry its own plane of bytes)
+    unsigned m;
+    if constexpr (LV) m = *reinterpret_cast<const unsigned *>(lbits + (((per_field >> 16) + q4 / ncell) % (per_field & 0xFFFF)) * ncell + cell);
+    else m = *reinterpret_cast<const unsigned *>(lbits + (per_field ? q4 : cell));   // (per_field: every entry its own plane of bytes)
     if ((m & 0x01010101u) == 0x01010101u) continue;
     T xm2[4], xm1[4];
     FB fb[4];
@@ -89,6 +94,10 @@ __global__ __launch_bounds__(256) void k_zero_land(T *a, T *b, const uint8_t *lb
 
 // rows [row_lo, row_hi) of both planes (row_hi <= 0: all rows)
 int launch_zero_land(gcmf_plan *pl, void *a, void *b, int64_t nbatch, hipStream_t s, int row_lo, int row_hi) {
+  if (pl->stacked) {   // (only the forward schedule and gcmf_zero_land zero land in place: neither runs on a stacked plan)
+    set_error("k_zero_land: not available on a stacked plan (gcmf_plan_create_levels)");
+    return GCMF_ERR_UNSUPPORTED;
+  }
   if (row_hi <= 0) { row_lo = 0; row_hi = (int)pl->rows_alloc; }
   const long long ncell = (long long)pl->rows_alloc * pl->d.nx, cell0 = (long long)row_lo * pl->d.nx;
   const long long nsub = (long long)(row_hi - row_lo) * pl->d.nx, ntotal = nsub * nbatch;
@@ -113,6 +122,16 @@ static int launch_lf(gcmf_plan *pl, const void *in, void *out, const double *dp,
   if (nb > 32768) nb = 32768;
   dim3 block(256), grid((unsigned)nb);
   const size_t lds = ((size_t)n_steps + 1) * sizeof(double);
+  if constexpr (sizeof(T) == 8 && sizeof(FB) == 8) {
+    if (pl->stacked) {   // (f64 flux kinds; one level: the plan's one plane, the ordinary kernel)
+      if (pl->nlev >= 2) {
+        hipLaunchKernelGGL((k_land_fix<T, FB, true, true>), grid, block, lds, s, (const T *)in, (FB *)out, pl->lbits, area, dp, n_steps, c, ncell,
+                           ntotal, (int)pl->nlev | ((int)(pl->entry0 % pl->nlev) << 16));
+        GCMF_HIP(hipGetLastError());
+        return GCMF_OK;
+      }
+    }
+  }
   if (pl->kind == K_FLUX)
     hipLaunchKernelGGL((k_land_fix<T, FB, true>), grid, block, lds, s, (const T *)in, (FB *)out, pl->lbits, area, dp, n_steps, c,
                        ncell, ntotal, pl->mask_per_field);

@@ -122,6 +122,10 @@ template <typename T, typename FB> struct MultiP {
   double pk[MAX_PK];  // coefficient of level t (1-based) at pk[t-1]
   double p0;         // first only
   double c;
+  // stacked plans (gcmf_plan_create_levels): cE / cN / ra / lbits hold nlev planes lstride cells apart; batch entry b of the launch is
+  // filtered with the planes of level (lev0 + b) % nlev (k_ringc<..., LV = true> only: no other kernel reads these)
+  long long lstride = 0;
+  int nlev = 1, lev0 = 0;
 };
 
 

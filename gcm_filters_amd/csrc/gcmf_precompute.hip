@@ -499,6 +499,67 @@ template <typename T> static int precompute_t(gcmf_plan *pl, const void *const *
   return GCMF_OK;
 }
 
+// A stacked plan (gcmf_plan_create_levels; the caller has checked: an f64 flux kind without a seam, the whole grid): the fold kernels of
+// the ordinary plan run once per level into (nlev, ny, nx) coefficient planes and land bytes -- a whole grid's slab layout is the global
+// one, nothing is cut.  Plane k of the input has plane_levels[k] planes: 1 = shared by all levels.  Validation as the reference applies it
+// to grid variables with leading dims (kernels.py:262-281 on the whole arrays): a kappa > 1 on any level fails, and "no kappa equals 1"
+// fails only when no level has one -- the flag word is shared by the levels.
+int precompute_levels(gcmf_plan *pl, const void *const *dp, const int64_t *plane_levels) {
+  using T = double;
+  const int ny = (int)pl->d.ny, nx = (int)pl->d.nx, gt = pl->d.grid_type;
+  const size_t plane = (size_t)ny * nx;
+  const int64_t nlev = pl->nlev;
+  hipStream_t s = pl->stream;
+  const dim3 block(256), grid((unsigned)std::min<size_t>((plane + 255) / 256, 8192));
+  int *dflags = nullptr;   // [0] validation flags of all levels, [1] isolated cells of the level that runs now
+  GCMF_HIP(hipMalloc((void **)&dflags, 2 * sizeof(int)));
+  struct FlagGuard { int *p; ~FlagGuard() { (void)hipFree(p); } } guard{dflags};
+  GCMF_HIP(hipMemsetAsync(dflags, 0, 2 * sizeof(int), s));
+  int rc;
+  T *c[3];
+  for (auto &p : c)
+    if ((rc = dev_alloc(pl, (void **)&p, (size_t)nlev * plane * sizeof(T) + 256))) return rc;
+  uint8_t *isol = nullptr;
+  if ((rc = dev_alloc(pl, (void **)&isol, (size_t)nlev * plane + 256))) return rc;
+  int64_t n_land = 0;
+  for (int64_t l = 0; l < nlev; ++l) {
+    auto P = [&](int k) { return (const T *)dp[k] + (plane_levels[k] > 1 ? (size_t)l * plane : 0); };
+    T *cE = c[0] + (size_t)l * plane, *cN = c[1] + (size_t)l * plane, *ra = c[2] + (size_t)l * plane;
+    if (gt == GCMF_IRREGULAR_WITH_LAND)
+      hipLaunchKernelGGL(k_pre_irregular<T>, grid, block, 0, s, P(0), P(1), P(2), P(3), P(4), P(5), P(6), P(7), cE, cN, ra, ny, nx, dflags);
+    else
+      hipLaunchKernelGGL(k_pre_mom5<T>, grid, block, 0, s, P(0), P(1), P(2), P(3), P(4), P(5), cE, cN, ra, ny, nx, gt == GCMF_MOM5U ? 1 : 0);
+    hipLaunchKernelGGL(k_pre_isolated<T>, grid, block, 0, s, (const T *)cE, (const T *)cN, isol + (size_t)l * plane, ny, nx, 0, dflags + 1);
+    GCMF_HIP(hipGetLastError());
+    int got[2] = {0, 0};   // (per level: the count of a deep stack would not fit an int)
+    GCMF_HIP(hipMemcpyAsync(got, dflags, sizeof got, hipMemcpyDeviceToHost, s));
+    GCMF_HIP(hipMemsetAsync(dflags + 1, 0, sizeof(int), s));
+    GCMF_HIP(hipStreamSynchronize(s));
+    n_land += got[1];
+    if (l + 1 < nlev) continue;
+    const int flags = got[0];
+    if (gt == GCMF_IRREGULAR_WITH_LAND) {
+      if (flags & F_KW_GT1) {
+        set_error("There are kappa_w values > 1 and this can cause the filter to blow up.Please make sure all kappa_w are <=1.");
+        return GCMF_ERR_KAPPA_W_GT1;
+      }
+      if (flags & F_KS_GT1) {
+        set_error("There are kappa_s values > 1 and this can cause the filter to blow up.Please make sure all kappa_s are <=1.");
+        return GCMF_ERR_KAPPA_S_GT1;
+      }
+      if (!(flags & F_K_NEAR1) && !(pl->d.flags & GCMF_PLAN_SKIP_KAPPA_ONE)) {
+        set_error("At least one place in the domain must have either kappa_w = 1 or kappa_s = 1. Otherwise the filter's "
+                  "scale will not be equal to filter_scale anywhere in the domain.");
+        return GCMF_ERR_KAPPA_NONE_ONE;
+      }
+    }
+  }
+  for (int k = 0; k < 3; ++k) pl->g.coef[k] = c[k];
+  pl->lbits = isol;
+  pl->n_land = n_land;   // of all levels: a plan with land on any level has land
+  return GCMF_OK;
+}
+
 int precompute(gcmf_plan *pl, const void *const *dplanes, const void *const *hplanes) {
   return pl->d.dtype == GCMF_F64 ? precompute_t<double>(pl, dplanes, hplanes) : precompute_t<float>(pl, dplanes, hplanes);
 }

@@ -86,6 +86,7 @@ struct RingcCutIn {
   bool band_beside;      // k_fold_band runs BESIDE this launch (its waves must fit on the SIMDs next to these: no zip, no early exit)
   bool mask_per_field;   // GCMF_MASK_FROM_NAN: never packed
   int strip_rows, ringc_xe_rows, ringc_zip, zip_fold, pack_batch;   // the plan's options of these names
+  bool stacked = false;  // a stacked plan (gcmf_plan_create_levels): whole strips per entry in whole ring periods -- never zipped, packed or with early exits
 };
 
 struct RingcCut {
@@ -220,7 +221,7 @@ inline RingcCut ringc_cut(const RingcCutIn &in) {
     if (nrows <= 0) return c;
   }
   bool xe = false;
-  if (flux && !in.band_beside) {
+  if (flux && !in.band_beside && !in.stacked) {
     // Nothing has to fit beside the waves -> the early-exit form (k_ringcs) wherever it shortens the march: the plain form marches whole
     // 12-row ring periods, the early-exit form leaves after every fourth row (and costs ~60 registers: 1.4 % per launch in f64, ~8 % in
     // f32).  1024 lone waves on 1080 x 1440 f64 cells own 14-row strips: 32 rows marched instead of 36, and every SIMD has a wave (330 ->
@@ -254,8 +255,9 @@ inline RingcCut ringc_cut(const RingcCutIn &in) {
       }
     }
   }
-  // (GCMF_MASK_FROM_NAN: whole strips per field -- the packed walk has not been run with one plane of mask bytes per entry)
-  const bool pack = in.batch > 1 && in.strip_rows <= 0 && in.pack_batch && !in.mask_per_field && in.batch * nrows < (1LL << 30);
+  // (GCMF_MASK_FROM_NAN, stacked plans: whole strips per field -- the packed walk has not been run with one plane of mask bytes per
+  // entry, nor with coefficient planes per level)
+  const bool pack = in.batch > 1 && in.strip_rows <= 0 && in.pack_batch && !in.mask_per_field && !in.stacked && in.batch * nrows < (1LL << 30);
   const Strips st = strips(c.nwx, in.batch, nrows, S, (flux && !xe) ? CUT_PERIOD : 4, in.strip_rows, pack);
   c.form = st.npack > 0 ? RINGC_PACKED : xe ? RINGC_EARLY_EXIT : RINGC_PLAIN;
   c.xe = xe;

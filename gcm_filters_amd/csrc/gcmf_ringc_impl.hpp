@@ -57,7 +57,10 @@ template <bool ZIP> constexpr bool ringc_ramp_on(int t, int ph) { return ZIP ? (
 // time).  pos_at: the window's first column instead of wx * WI - M; [klo, khi): the columns this window keeps.
 // PF: the launch carries one plane of mask bytes per batch entry (MultiP::mper, GCMF_MASK_FROM_NAN) -- an instantiation of k_ringc of its
 // own (see k_ring, gcmf_ring_impl.hpp: the kernel of an ordinary launch is the code it was before).
-template <typename T, int KIND, int S, bool FIRST, bool SANI, bool XE = false, bool ZIP = false, bool PF = false>
+// LV: a stacked plan (gcmf_plan_create_levels; the f64 flux kinds' plain strips) -- the coefficient planes and the land bytes have a level
+// axis and batch entry b marches with the planes of level (P.lev0 + b) % P.nlev: one wave-uniform offset on row pointers that are scalar
+// already, and, like PF, an instantiation of its own.
+template <typename T, int KIND, int S, bool FIRST, bool SANI, bool XE = false, bool ZIP = false, bool PF = false, bool LV = false>
 __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx, const int a, const int b, const long long boff, const bool odd,
                                             T *zmine = nullptr, const T *zpart = nullptr, const bool fold = false, const int pos_at = 0,
                                             const int klo = -(1 << 30), const int khi = 1 << 30) {
@@ -69,6 +72,7 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
   static_assert(R >= S + D && R % 3 == 0 && R % RU == 0 && R % RV == 0 && RU >= 3 + D && RV >= 1 + D, "ring periods");
   constexpr bool FLUX = (KIND == K_FLUX), MASK = (KIND == K_MASKZ);
   static_assert(!ZIP || FLUX, "the seam exchange is the flux kinds' (a carried face flux per level)");
+  static_assert(!LV || (FLUX && !ZIP && !PF), "stacked plans: the flux kinds' plain strips");
   constexpr bool WATCH = (KIND != K_REG) && !SANI;  // K_REG has no nan_to_num in the reference: NaN spreads by plain arithmetic
   constexpr bool FUSED = true;   // nothing here is bit-identical with numpy anyway: every multiply-add pair is one fma
 
@@ -161,8 +165,13 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
   };
   const T *fplane = P.fb_in + boff;  // the constant input f (Clenshaw has no fbar: the pointer slot is reused)
   const long long moff = (MASK && PF) ? boff : 0;   // (wave-uniform) the entry's own plane of mask bytes
+  const long long loff = LV ? (long long)((P.lev0 + (int)blockIdx.y) % P.nlev) * P.lstride : 0;   // (wave-uniform) the entry's level
   const bool has_land = P.lbits != nullptr;
   const uint8_t *zbase = has_land ? P.lbits + moff : reinterpret_cast<const uint8_t *>(P.fb_in);  // (valid bytes, ignored)
+  // (LV adds its offset in branches of its own, here and in load_centre: with the offset folded into the ordinary expressions --
+  // "P.cE + loff" with loff = 0 -- the kernels of ordinary launches came out with another register allocation; this way they are the
+  // instruction stream they were, compared in the assembly)
+  if constexpr (LV) zbase = has_land ? P.lbits + loff : zbase;
   const bool weigh = !FLUX && P.area_weighted;
   const T *abase = weigh ? P.area : P.fb_in;  // (an unconditional load, ignored when there is no area)
 
@@ -187,6 +196,11 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
       // (an upward march: the face between the centre row and the row the cursor is on -- grid row j - 1's north face)
       const T *pN = !up ? (out_c ? P.zrow : P.cN + rc) : ((out_c || cout_) ? P.zrow : P.cN + (long long)(cj * nx));
       const T *pA = out_c ? P.zrow : P.ra + rc;
+      if constexpr (LV) {   // (zrow has no level axis)
+        pE = out_c ? pE : pE + loff;
+        pN = (!up ? out_c : (out_c || cout_)) ? pN : pN + loff;
+        pA = out_c ? pA : pA + loff;
+      }
       mload<T, VEC>(cE[sl], lane_ptr(pE, colT));
       mload<T, VEC>(cN[sl], lane_ptr(pN, colT));
       mload<T, VEC>(ra[sl], lane_ptr(pA, colT));
@@ -461,17 +475,17 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
 // its run, which crosses at most one field boundary (H <= nrows): up to two (field, row range) segments, each a march of its own with its
 // 2 S warm-up rows.  16 fields x 33 windows of a 300-row slab tile 1024 wave slots at ~70 % as whole strips (a strip cannot cross from one
 // field into the next) and at ~95 % this way.
-template <typename T, int KIND, int S, bool FIRST, bool XE, bool PACK, bool PF = false>   // (PF: never packed, ringc_cut)
+template <typename T, int KIND, int S, bool FIRST, bool XE, bool PACK, bool PF = false, bool LV = false>   // (PF, LV: never packed, ringc_cut)
 __device__ __forceinline__ void ringc_walk(const MultiP<T, T> &P, const int wid) {
   const int wx = wid % P.nwx, st = wid / P.nwx;
   if constexpr (!PACK) {   // one strip of one field (the instruction stream of rounds 2-5: the walk below costs the land-mask kernel 5 %)
     const int a = P.out_lo + st * P.H;
     const int b = min(a + P.H, P.out_hi);
     const long long boff = (long long)blockIdx.y * P.bstride;
-    if (ringc_march<T, KIND, S, FIRST, false, XE, false, PF>(P, wx, a, b, boff, (st & 1) != 0)) {
+    if (ringc_march<T, KIND, S, FIRST, false, XE, false, PF, LV>(P, wx, a, b, boff, (st & 1) != 0)) {
       if constexpr (KIND != K_REG) {
         if (P.nfb && (threadIdx.x & 63) == 0) atomicAdd(P.nfb, 1u);                      // instrumentation: gcmf_ring_fallbacks
-        ringc_march<T, KIND, S, FIRST, true, XE, false, PF>(P, wx, a, b, boff, (st & 1) != 0);   // the same strip again, operands through nan_to_num
+        ringc_march<T, KIND, S, FIRST, true, XE, false, PF, LV>(P, wx, a, b, boff, (st & 1) != 0);   // the same strip again, operands through nan_to_num
       }
     }
     return;
@@ -494,13 +508,13 @@ __device__ __forceinline__ void ringc_walk(const MultiP<T, T> &P, const int wid)
   }
 }
 
-template <typename T, int KIND, int S, bool FIRST, bool PF = false>
+template <typename T, int KIND, int S, bool FIRST, bool PF = false, bool LV = false>
 __global__ __launch_bounds__(256, 1) void k_ringc(const MultiP<T, T> P) {
   int bx = blockIdx.x;
   if (P.xcd_per > 0 && bx < 8 * P.xcd_per) bx = (bx & 7) * P.xcd_per + (bx >> 3);
   const int wid = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (wid >= P.nwaves) return;
-  ringc_walk<T, KIND, S, FIRST, false, false, PF>(P, wid);
+  ringc_walk<T, KIND, S, FIRST, false, false, PF, LV>(P, wid);
 }
 
 // ... and for packed batches (ringc_walk<PACK>): XE = the early-exit form of the flux kinds (k_ringcs)
@@ -623,6 +637,9 @@ template <typename T> static void ringc_params(MultiP<T, T> &P, const gcmf_plan 
   P.mbits = g.mbits;
   P.lbits = (pl->n_land > 0) ? pl->lbits : nullptr;
   P.mper = pl->mask_per_field;
+  P.lstride = pl->stacked ? (long long)g.rows * g.nx : 0;
+  P.nlev = (int)pl->nlev;
+  P.lev0 = (int)(pl->entry0 % pl->nlev);
   P.area = (const T *)g.area;
   P.nx = g.nx;
   P.rows = g.rows;
@@ -740,6 +757,25 @@ static int launch_ringc_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cu
   GCMF_HIP(hipGetLastError());
   note_kernel(pl, std::string("gcmf::k_ringc<") + tyname<T>() + ", " + std::to_string(KIND) + ", " + std::to_string(S) + ", " +
                       (FIRST ? "true" : "false") + ">", S, launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows));
+  return GCMF_OK;
+}
+
+// a stacked plan's launch (gcmf_plan_create_levels): k_ringc<double, K_FLUX, S, FIRST, false, true>; reported under the ordinary kernel's
+// name, as the per-entry-mask instantiation is, with " levels=<nlev>" behind the geometry
+template <int S, bool FIRST>
+static int launch_ringc_levels_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+  if (cut.form != RINGC_PLAIN || cut.xe || pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || !pl->stacked) {
+    set_error("k_ringc (stacked plan): the cut is not the plain strips of an f64 flux plan");
+    return GCMF_ERR_INVALID_ARG;
+  }
+  MultiP<double, double> P;
+  ringc_params(P, pl, a, cut);
+  const int nrows = a.row_hi - a.row_lo;
+  dim3 block(256), grid(cut.grid_x, cut.grid_y);
+  hipLaunchKernelGGL((k_ringc<double, K_FLUX, S, FIRST, false, true>), grid, block, 0, s, P);
+  GCMF_HIP(hipGetLastError());
+  note_kernel(pl, std::string("gcmf::k_ringc<double, ") + std::to_string((int)K_FLUX) + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
+              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " levels=" + std::to_string((long long)pl->nlev));
   return GCMF_OK;
 }
 

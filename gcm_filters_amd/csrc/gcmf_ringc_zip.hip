@@ -60,7 +60,7 @@ const WetTable *wet_table(gcmf_plan *pl, const MultiArgs &a, long long even_marc
   *rc = GCMF_OK;
   const Geom &g = pl->g;
   const int S = a.S, rows = g.rows, nrows = a.row_hi - a.row_lo;
-  if (!pl->wet_rows || !pl->wet_now || pl->mask_per_field || pl->n_land <= 0 || !pl->lbits || pl->d.dtype != GCMF_F64 || pl->kind != K_FLUX ||
+  if (!pl->wet_rows || !pl->wet_now || pl->mask_per_field || pl->stacked || pl->n_land <= 0 || !pl->lbits || pl->d.dtype != GCMF_F64 || pl->kind != K_FLUX ||
       g.fold || a.nbatch != 1 || !pl->pool_base || !pl->pool_bytes || S < 5 || S > 9 || nrows < 4)
     return nullptr;
   const WetTable *t = nullptr;

@@ -48,6 +48,15 @@ ALL_KERNELS: Dict[GridType, Any] = {}
 NAN_MASK_GRID_TYPES = (GridType.REGULAR_WITH_LAND, GridType.REGULAR_WITH_LAND_AREA_WEIGHTED,
                        GridType.TRIPOLAR_REGULAR_WITH_LAND_AREA_WEIGHTED)
 
+# the grid types whose per-level grid variables (wet_mask(z, y, x), kappa(z, y, x)) fold into ONE stacked plan (gcmf_plan_create_levels):
+# flux form, no tripole seam; float64 and the default (backward) evaluation only
+STACKED_GRID_TYPES = (GridType.IRREGULAR_WITH_LAND, GridType.MOM5U, GridType.MOM5T)
+# ... by default only for MORE levels than the plan cache holds plans (GCMF_PLAN_CACHE_SIZE, 64): there the per-level route rebuilds every
+# level's plan on every call (80 levels of 1080 x 1440: 600 ms against 26 ms per application); up to that many levels the cached
+# per-level plans run a lone field each on the zipped strips and measured the same as the stacked call's plain strips (16 levels of
+# 2400 x 3600: 12.86 against 12.84 ms, inside the spread)
+STACK_LEVELS_ABOVE = 64
+
 ArrayType = np.ndarray
 
 
@@ -427,6 +436,10 @@ class _DeviceLaplacian:
 
     def __init__(self, *args, **kwargs):
         self._skip_kappa_one = bool(kwargs.pop("_skip_kappa_one", False))
+        # grid variables with leading dims: one stacked plan and one call where the library has one -- None: for more than
+        # STACK_LEVELS_ABOVE levels; True / GCMF_STACK_LEVELS=1 in the environment: for any number; False / GCMF_STACK_LEVELS=0: never,
+        # a plan and a call per level (the keyword wins over the environment; both are for A/B runs and the tests)
+        self._stack_levels = kwargs.pop("_stack_levels", None)
         names = self._ARGS
         if len(args) > len(names):
             raise TypeError(f"{type(self).__name__}() takes {len(names)} grid arguments but {len(args)} were given")
@@ -447,6 +460,8 @@ class _DeviceLaplacian:
             if a.ndim < 2:
                 raise ValueError(f"grid variable {n!r} needs at least two (y, x) dimensions, got shape {tuple(a.shape)}")
         self._levels = None
+        self._glead = None
+        self._stacked = False
         if any(a.ndim > 2 for a in self._planes):
             self._init_levels()
             return
@@ -459,9 +474,22 @@ class _DeviceLaplacian:
         """Grid variables such as wet_mask(z, y, x) or kappa(z, y, x).  The reference's kernels roll along the last two
         axes only (kernels.py:113-121, 163-187, 297-315) and xarray.apply_ufunc broadcasts the remaining dims of field
         and grid variables against each other (filter.py:478-486), so every index of the grid variables' broadcast
-        leading shape is an independent 2-D problem: one device plan per index, each batch entry filtered with its own."""
+        leading shape is an independent 2-D problem: each batch entry is filtered with the grid of its own index.  Float64 flux-form
+        grids without a tripole seam fold all of them into ONE stacked plan (gcmf_plan_create_levels) that one call runs; every
+        other grid type, and the calls a stacked plan does not take (one Laplacian, evaluation="reference", ...), run one device
+        plan and one call per index -- those Laplacian objects are then built when the first such call arrives."""
         leads = [tuple(a.shape[:-2]) for a in self._planes]
         self._glead = tuple(np.broadcast_shapes(*leads))
+        want = self._stack_levels
+        if want is None and os.environ.get("GCMF_STACK_LEVELS", "") in ("0", "1"):
+            want = os.environ["GCMF_STACK_LEVELS"] == "1"
+        if want is None:
+            want = int(np.prod(self._glead, dtype=np.int64)) > STACK_LEVELS_ABOVE
+        self._stacked = bool(want) and self.GRID_TYPE in STACKED_GRID_TYPES and compute_dtype(self._planes) == _lib.F64
+        if self._stacked:   # validation happens at construction: the library applies the reference's tests to all levels together
+            self._fp = tuple(_fingerprint(a) for a in self._planes)
+            self._stacked_plan()
+            return
         if self.GRID_TYPE is GridType.IRREGULAR_WITH_LAND and not self._skip_kappa_one:
             # the reference tests the WHOLE kappa arrays (kernels.py:262-281); the per-plane plans repeat the > 1 test
             kw, ks = (np.asarray(x.detach().cpu() if _is_torch(x) else x) for x in (self.kappa_w, self.kappa_s))
@@ -469,16 +497,110 @@ class _DeviceLaplacian:
                     and not (np.any(kw > 1.0) or np.any(ks > 1.0)):
                 raise ValueError("At least one place in the domain must have either kappa_w = 1 or kappa_s = 1. "
                                  "Otherwise the filter's scale will not be equal to filter_scale anywhere in the domain.")
-        self._levels = {}
-        for g in np.ndindex(*self._glead):
-            sub = []
-            for a, lead in zip(self._planes, leads):
-                if a.ndim == 2:
-                    sub.append(a)
-                else:  # align the plane's own leading dims with the tail of the broadcast shape
-                    gi = g[len(g) - len(lead):]
-                    sub.append(a[tuple(0 if n == 1 else i for i, n in zip(gi, lead))])
-            self._levels[g] = type(self)(*sub, _skip_kappa_one=True)
+        self._level_laps()
+
+    def _level_laps(self):
+        """{index of the broadcast leading shape: the Laplacian of that index's 2-D grid variables}, built on first use."""
+        if self._levels is None:
+            leads = [tuple(a.shape[:-2]) for a in self._planes]
+            levels = {}
+            for g in np.ndindex(*self._glead):
+                sub = []
+                for a, lead in zip(self._planes, leads):
+                    if a.ndim == 2:
+                        sub.append(a)
+                    else:  # align the plane's own leading dims with the tail of the broadcast shape
+                        gi = g[len(g) - len(lead):]
+                        sub.append(a[tuple(0 if n == 1 else i for i, n in zip(gi, lead))])
+                levels[g] = type(self)(*sub, _skip_kappa_one=True)
+            self._levels = levels
+        return self._levels
+
+    def _stacked_plan(self, device: Optional[int] = None) -> _lib.Plan:
+        """The ONE plan of all levels (self._stacked): grid variables with a leading extent are laid out (nlev, ny, nx), the broadcast
+        leading shape flattened in C order; the others are passed once, shared by every level."""
+        core = tuple(self._planes[0].shape[-2:])
+        nlev = int(np.prod(self._glead, dtype=np.int64))
+        on_gpu = all(_on_gpu(a) for a in self._planes)
+        if device is None:
+            device = self._planes[0].device.index if on_gpu else current_device()
+        key = ("levels", self.GRID_TYPE.value, _lib.F64, core, self._glead, device, self._skip_kappa_one, self._fp)
+
+        def factory():
+            planes, plane_levels = [], []
+            for a in self._planes:
+                if tuple(a.shape[-2:]) != core:
+                    raise ValueError(f"grid variables have spatial shapes {tuple(a.shape[-2:])} and {core}")
+                if not on_gpu and _is_torch(a):
+                    a = a.detach().cpu().numpy()
+                if int(np.prod(a.shape[:-2], dtype=np.int64)) == 1:   # no leading extent: one plane for all levels
+                    planes.append(a.reshape(core))
+                    plane_levels.append(1)
+                    continue
+                full = self._glead + core
+                if on_gpu:
+                    import torch
+                    planes.append(a.expand(*full).to(torch.float64).contiguous().reshape(nlev, *core))
+                else:
+                    planes.append(np.ascontiguousarray(np.broadcast_to(a, full), dtype=np.float64).reshape(nlev, *core))
+                plane_levels.append(nlev)
+            try:
+                if on_gpu:
+                    import torch
+                    keep = [t.to(torch.float64).contiguous() for t in planes]
+                    torch.cuda.synchronize(device)
+                    return _lib.Plan.create_levels(self.GRID_TYPE.value, _lib.F64, core[0], core[1], [t.data_ptr() for t in keep], plane_levels,
+                                                   nlev, device=device, planes_on_device=True, skip_kappa_one=self._skip_kappa_one)
+                return _lib.Plan.create_levels(self.GRID_TYPE.value, _lib.F64, core[0], core[1], planes, plane_levels, nlev, device=device,
+                                               skip_kappa_one=self._skip_kappa_one)
+            except _lib.GcmfError as e:
+                raise _translate(e) from None
+
+        mode = cache_mode()
+        if mode == "off":
+            old = getattr(self, "_own_plan", None)
+            if old is not None:
+                old.close()
+            self._own_plan = factory()
+            return self._own_plan
+        return PLAN_CACHE.get(key, factory, () if (on_gpu or mode == "verify") else self._planes)
+
+    def _run_stacked(self, given, field, spec, out_lead, core):
+        """One call of the stacked plan on the field broadcast to (..., *glead, ny, nx), or None where that plan does not take the call
+        (the library offers no backward evaluation for this polynomial: the per-level route then runs)."""
+        nbatch = int(np.prod(out_lead, dtype=np.int64))
+        full = tuple(out_lead) + tuple(core)
+        c = 2 / spec.s_max if self.is_dimensional else 2 / (spec.s_max * spec.dx_min_sq)
+        p = np.asarray(spec.p, dtype=np.float64)
+        gpu = _on_gpu(field)
+        plan = self._stacked_plan(field.device.index if gpu else None)
+        if (plan.ny, plan.nx) != tuple(core):
+            raise ValueError(f"field has spatial shape {tuple(core)} but the grid variables have shape {(plan.ny, plan.nx)}")
+        if nbatch and not plan.clenshaw_cut(int(spec.n_steps), nbatch):
+            return None
+        try:
+            if gpu:
+                import torch
+                dev = field.device.index
+                fb = field if tuple(field.shape) == full else field.expand(*full)
+                src = fb if (fb.dtype == torch.float64 and fb.is_contiguous()) else fb.to(torch.float64).contiguous()
+                out = torch.empty(full, dtype=torch.float64, device=field.device)
+                if nbatch:
+                    cur = torch.cuda.current_stream(dev)
+                    plan.apply(p, c, [src.data_ptr()], [out.data_ptr()], nbatch, device_ptrs=True, stream=cur.cuda_stream)
+                    if src is not field:
+                        src.record_stream(cur)
+            else:
+                host = field.detach().cpu().numpy() if _is_torch(field) else np.asarray(field)
+                src = np.ascontiguousarray(np.broadcast_to(host, full), dtype=np.float64)
+                out = _host_output(full, np.float64)
+                if nbatch:
+                    plan.apply(p, c, [src.ctypes.data], [out.ctypes.data], nbatch, device_ptrs=False)
+            if nbatch:
+                _note_path(plan.last_path(), plan.device)
+        except _lib.GcmfError as e:
+            raise _translate(e) from None
+        return [_same_kind(out, given)]
 
     def _run_levels(self, fields, spec, out_f32, forward=False, backward_f32=False, mask_from_nan=False):
         given = list(fields)
@@ -489,8 +611,14 @@ class _DeviceLaplacian:
         core = shape[-2:]
         out_lead = tuple(np.broadcast_shapes(shape[:-2], self._glead))
         pad = len(out_lead) - len(self._glead)
+        # the stacked plan: a whole filter, backward evaluation; entry b of the flattened leading shape runs on level b % nlev, so the
+        # grid variables' leading shape must be the TAIL of the field's (none of its size-1 dims stretched by the field)
+        if self._stacked and spec is not None and not forward and not mask_from_nan and self._NCOMP == 1 and out_lead[pad:] == self._glead:
+            res = self._run_stacked(given[0], fields[0], spec, out_lead, core)
+            if res is not None:
+                return res
         outs = None
-        for g, lap in self._levels.items():
+        for g, lap in self._level_laps().items():
             idx = tuple([slice(None)] * pad + [slice(None) if n == 1 else i for i, n in zip(g, self._glead)])
             sub = []
             for f in fields:
@@ -560,7 +688,7 @@ class _DeviceLaplacian:
         if mask_from_nan and (spec is None or self.GRID_TYPE not in NAN_MASK_GRID_TYPES):
             raise ValueError("mask_from_nan needs a filter application on one of the grid types "
                              + ", ".join(g.name for g in NAN_MASK_GRID_TYPES))
-        if self._levels is not None:
+        if self._glead is not None:
             return self._run_levels(fields, spec, out_f32, forward, backward_f32, mask_from_nan)
         given = list(fields)
         fields = [_unwrap(f) for f in fields]

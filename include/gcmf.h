@@ -18,7 +18,9 @@
  * with respect to *different* plans; calls on one plan are serialised by a per-plan mutex.
  *
  * Array conventions: C order, (nbatch, ny, nx) with x fastest.  Grid planes are 2-D (ny, nx) and
- * shared by every batch entry.  "Rows" are indices along y (the slow, sharded axis).
+ * shared by every batch entry -- except on a STACKED plan (gcmf_plan_create_levels), whose grid planes
+ * have a level axis and whose batch entry b is filtered with level b % nlev.  "Rows" are indices along
+ * y (the slow, sharded axis).
  */
 #ifndef GCMF_H
 #define GCMF_H
@@ -147,6 +149,31 @@ typedef struct gcmf_plan_desc {
  */
 int gcmf_plan_create(const gcmf_plan_desc *desc, const void *const *planes, int nplanes, gcmf_plan **out);
 void gcmf_plan_destroy(gcmf_plan *plan);
+
+/*
+ * A STACKED plan: grid variables with a leading level axis -- wet_mask(z, y, x), kappa(z, y, x): what the reference gets when
+ * xarray.apply_ufunc broadcasts the leading dims of field and grid variables against each other (filter.py:478-486) -- folded into ONE
+ * plan whose coefficient planes and land bytes are (nlev, ny, nx).  planes[i] is a C-ordered (plane_levels[i], ny, nx) array,
+ * plane_levels[i] = 1 (shared by all levels) or nlev; the planes' order is gcmf_plan_create's.  Validation is the reference's on the
+ * whole arrays (kernels.py:262-281): a kappa > 1 on any level fails, GCMF_ERR_KAPPA_NONE_ONE only when NO level has a kappa of 1.  The
+ * plan has land (gcmf_has_land) when any level has.
+ *   Scope: IRREGULAR_WITH_LAND, MOM5U, MOM5T; dtype f64; the whole grid (row_begin = 0, row_end = ny, no GCMF_PLAN_SELF_RING) --
+ *   anything else returns GCMF_ERR_UNSUPPORTED and names the limit: build one plan per level.
+ *   gcmf_apply(plan, ..., nbatch, ...) filters batch entry b with the grid of level b % nlev: a (..., nlev, ny, nx) field in C order is
+ *   one call.  nbatch must be a multiple of nlev (GCMF_ERR_INVALID_ARG); host and device pointers are both taken (the chunks of the
+ *   pipelined host path keep their place in the batch).  The call runs the backward evaluation's plain strips (k_ringc, one workgroup
+ *   column per entry; never the on-chip kernel, "single_launch", the packed walk, the zipped strips or the wet-row tables) and
+ *   gcmf_clenshaw_cut_batch answers for those launches; the result has the bits of nlev ordinary plans run entry by entry.  Where the
+ *   backward evaluation is not on offer (gcmf_clenshaw_cut_batch returns 0: fewer than five steps, nx not a multiple of 4 on a grid
+ *   with land, GCMF_CLENSHAW=0 ...) gcmf_apply returns GCMF_ERR_UNSUPPORTED, as it does for GCMF_FORWARD_RECURRENCE and
+ *   GCMF_MASK_FROM_NAN; so do gcmf_laplacian, the gcmf_cheb_* / gcmf_slab_* / gcmf_resident_* building blocks, gcmf_prepare,
+ *   gcmf_zero_land and gcmf_land_fix.  gcmf_last_kernel names the ordinary kernel (the launches are an instantiation of their own of
+ *   it); gcmf_last_kernel_geometry appends " levels=<nlev>".
+ * gcmf_plan_levels: nlev of a stacked plan, 1 for an ordinary one (0 for NULL).
+ */
+extern int gcmf_plan_create_levels(const gcmf_plan_desc *desc, const void *const *planes, const int64_t *plane_levels, int nplanes, int64_t nlev,
+                                   gcmf_plan **out);
+extern int64_t gcmf_plan_levels(const gcmf_plan *plan);
 
 /* Static facts (no device needed). */
 int gcmf_grid_nplanes(int grid_type);        /* number of grid planes, -1 if unknown           */
