@@ -499,14 +499,16 @@ class Plan:
         return buf.value.decode()
 
     def last_kernel_geometry(self) -> dict:
-        """Launch geometry of the kernel last_kernel() named: {"H", "nstrips", "nwx", "xcd", "grid", "rows"} ({} if none)."""
+        """Launch geometry of the kernel last_kernel() named: {"H", "nstrips", "nwx", "xcd", "grid", "rows"} ({} if none)
+        (+ "units": a wet-row table's pairs, and behind it "xoff": the first column of the window grid of the tight cut, option "wet_rows" 3 / 4;
+        "levels": a stacked plan's)."""
         buf = C.create_string_buffer(256)
         check(load().gcmf_last_kernel_geometry(self._h, buf, 256))
         out = {}
         for tok in buf.value.decode().split():
             k, _, v = tok.partition("=")
             out[k] = v if "x" in v else int(v)
-        return out   # (+ "units": a wet-row table's pairs; "levels": a stacked plan's)
+        return out
 
     def last_wet_units(self) -> int:
         """Pairs of strips of the kernel last_kernel() named if k_ringcz cut them from the wet rows of each window (option "wet_rows"; 0: a grid
@@ -528,7 +530,9 @@ class Plan:
 
     def set_option(self, name: str, value: int):
         """Named per-plan switch (gcmf_set_option, include/gcmf.h): "cgrid_ring", "cgrid_ring_smax", "cgrid_ring_hmax", "cgrid_ring_ncarry", "pack_batch",
-        "single_launch", "ringc9", "ringc_zip", "ringc_smax", "band_seq_cells", "zip_fold", "slab_nines", "clenshaw_f32", "ring_flux_f32", "wet_rows"."""
+        "single_launch", "ringc9", "ringc_zip", "ringc_smax", "band_seq_cells", "zip_fold", "slab_nines", "clenshaw_f32", "ring_flux_f32", "wet_rows"
+        ("wet_rows": 0 the even cut, 3 (default) / 4 the tight wet-row table where it marches 10 % fewer rows / whenever eligible, 1 / 2 the
+        same policies with the wider table of round 7)."""
         check(load().gcmf_set_option(self._h, name.encode(), int(value)))
 
 

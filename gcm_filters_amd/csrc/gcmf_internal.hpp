@@ -101,12 +101,15 @@ struct WetProfile {
   int WI = 0;
   std::vector<uint8_t> need;
 };
-// The pairs of one launch geometry: units = (window, lo, mid, hi) on the device; dev == nullptr: this geometry keeps the even cut.
+// The pairs of one launch geometry and cut: units = (x0, lo, mid, hi) on the device, x0 = the window's first footprint column; dev == nullptr:
+// this geometry keeps the even cut.  tight: the cut of round 8 (gcmf_wet_cut.hpp; options 3 and 4) -- round 7's otherwise (options 1 and 2).
+// xlim: a lane owns its cells below this column, nx + the offset of the window grid (round 7's grid starts at column 0).
 struct WetTable {
   int S = 0, row_lo = 0, row_hi = 0;
   int64_t nbatch = 0;
+  bool tight = false;
   void *dev = nullptr;
-  int nunits = 0, H = 0, nstrips = 0, march = 0;
+  int nunits = 0, H = 0, nstrips = 0, march = 0, xlim = 0;
 };
 
 }  // namespace gcmf
@@ -199,15 +202,16 @@ struct gcmf_plan {
   long long band_seq_cells = 3000000;   // tripolar plans: blocked launches over at most this many cells run k_fold_band AFTER themselves (its 1024-thread form), not beside (env GCMF_BAND_SEQ_CELLS; 0 = never)
   int zip_fold = 1;       // tripolar f64 flux plans, backward evaluation: k_ringcz advances the seam's rows itself (no k_fold_band); gcmf_set_option "zip_fold", env GCMF_ZIP_FOLD
   // Whole f64 flux grids with land, a lone field (round 7): k_ringcz's strips are cut from the rows of each window that hold anything wet
-  // (wet_table, gcmf_ringc_zip.hip).  0 off, 1 where that marches at least 10 % fewer rows than the even cut, 2 whenever eligible;
-  // gcmf_set_option "wet_rows".  Cells no strip owns are never written, but they are read as ghost cells (against zero coefficients:
+  // (wet_table, gcmf_ringc_zip.hip).  0 off, 1 where that marches at least 10 % fewer rows than the even cut, 2 whenever eligible; 3 and 4
+  // (round 8; 3 is the default): the same two policies with the TIGHT cut (gcmf_wet_cut.hpp), whose unowned cells may be direct neighbours
+  // of wet ones.  gcmf_set_option "wet_rows".  Cells no strip owns are never written, but they are read as ghost cells (against zero coefficients:
   // harmless while finite), so the four state planes must be finite there: pool_clean says they are (zero-filled once, and the flux
   // kinds' backward launches only ever write +-0 into isolated cells).  What can put a NaN / inf there: a new or regrown work buffer
   // (anything), the one-launch-per-step schedule (k_scalar_step carries a NaN on land through every T_k), and calls whose work layout
   // puts other planes where the pool lies (without the blocked schedules: fbar and the staged host input, NaN on land and all).  The
   // blocked forward schedule zeroes land in its state too, but no schedule is trusted: every one other than sched_backward_scalar on
   // an eligible call clears the flag, and so does a work buffer or layout other than the last call's.
-  int wet_rows = 1;
+  int wet_rows = 3;
   bool wet_now = false;         // this launch belongs to a gcmf_apply schedule that may take the table (sched_backward_scalar)
   bool pool_clean = false;
   void *pool_base = nullptr;    // the four state planes of the call that runs now (contiguous) ...

@@ -115,9 +115,10 @@ template <typename T, typename FB> struct MultiP {
                      // per window, cut into runs of H rows -- a wave walks its run, at most two (field, row range) segments (0: gridDim.y = batch)
   int fold_rows;     // k_ringcz on the plan that owns the tripole seam (round 6): the top fold_rows rows are strips that START at the seam, each
   int nfw;           // zipped with the strip of its MIRROR window (nfw such window pairs cover the two halves of a row); 0 = none
+                     // (k_ringcz's table launches, which have no fold strips: the column limit of ownership, nx + the window grid's offset)
   int mper = 0;      // land-mask kinds, GCMF_MASK_FROM_NAN: mbits / lbits hold one plane per batch entry, addressed with the field's own offset
   int nunits = 0;    // k_ringcz, strips cut from the wet rows of each window (round 7): the pairs of the launch come from a table,
-  const int4 *utab = nullptr;   // (window, lo, mid, hi) per pair, instead of from nstrips (NULL: the even cut of [out_lo, out_hi))
+  const int4 *utab = nullptr;   // (x0 = the window's first footprint column, lo, mid, hi) per pair, instead of from nstrips (NULL: the even cut of [out_lo, out_hi))
   long long bstride;
   double pk[MAX_PK];  // coefficient of level t (1-based) at pk[t-1]
   double p0;         // first only

@@ -60,7 +60,10 @@ template <bool ZIP> constexpr bool ringc_ramp_on(int t, int ph) { return ZIP ? (
 // LV: a stacked plan (gcmf_plan_create_levels; the f64 flux kinds' plain strips) -- the coefficient planes and the land bytes have a level
 // axis and batch entry b marches with the planes of level (P.lev0 + b) % P.nlev: one wave-uniform offset on row pointers that are scalar
 // already, and, like PF, an instantiation of its own.
-template <typename T, int KIND, int S, bool FIRST, bool SANI, bool XE = false, bool ZIP = false, bool PF = false, bool LV = false>
+// XO (round 8: k_ringcz's table launches, whose window grid may start at any even column): `wx` is the window's first FOOTPRINT column x0
+// instead of its number, and a lane owns its cells below column khi (the table's limit, nx + the grid's offset) instead of below nx -- a
+// compile-time form of its own again: every other instantiation is the instruction stream it was.
+template <typename T, int KIND, int S, bool FIRST, bool SANI, bool XE = false, bool ZIP = false, bool PF = false, bool LV = false, bool XO = false>
 __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx, const int a, const int b, const long long boff, const bool odd,
                                             T *zmine = nullptr, const T *zpart = nullptr, const bool fold = false, const int pos_at = 0,
                                             const int klo = -(1 << 30), const int khi = 1 << 30) {
@@ -73,17 +76,18 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
   constexpr bool FLUX = (KIND == K_FLUX), MASK = (KIND == K_MASKZ);
   static_assert(!ZIP || FLUX, "the seam exchange is the flux kinds' (a carried face flux per level)");
   static_assert(!LV || (FLUX && !ZIP && !PF), "stacked plans: the flux kinds' plain strips");
+  static_assert(!XO || ZIP, "a window origin per pair: k_ringcz's table launches");
   constexpr bool WATCH = (KIND != K_REG) && !SANI;  // K_REG has no nan_to_num in the reference: NaN spreads by plain arithmetic
   constexpr bool FUSED = true;   // nothing here is bit-identical with numpy anyway: every multiply-add pair is one fma
 
   const int lane = threadIdx.x & 63;
   const int nx = P.nx, rows = P.rows;
-  const int pos = ((ZIP && fold) ? pos_at : wx * WI - M) + lane * VEC;
+  const int pos = (XO ? wx : (ZIP && fold) ? pos_at : wx * WI - M) + lane * VEC;
   int col_s = pos % nx;
   if (col_s < 0) col_s += nx;
   const unsigned col = (unsigned)col_s;
   const unsigned colT = col * (unsigned)sizeof(T);
-  const bool keep = (lane * VEC >= M) && (lane * VEC < W - M) && (pos < nx) && (!ZIP || (pos >= klo && pos < khi));
+  const bool keep = (lane * VEC >= M) && (lane * VEC < W - M) && (XO || pos < nx) && (!ZIP || (pos >= klo && pos < khi));
   const T c = (T)P.c;
   const bool last = P.last;
 
@@ -547,6 +551,8 @@ __global__ __launch_bounds__(256, 1) void k_ringcs(const MultiP<T, T> P) {
 // TAB (round 7): the pairs come from the launch's table (MultiP::utab: strips cut from the rows of each window that hold anything wet,
 // wet_table in gcmf_ringc_zip.hip) -- a kernel of its own, k_ringcz<T, S, FIRST, XE, true>: as a wave-uniform branch inside the one kernel
 // the table cost the ordinary launch 3-4 % (these marches are paced by their instruction stream, see PF above and DESIGN.md 6).
+// Round 8: a pair's first int is its window's first footprint column x0 (ringc_march<XO>), so that the window grid of a table may start at
+// any even column; the column limit of ownership travels in MultiP::nfw, which a table launch (no fold strips) has no other use for.
 template <typename T, int S, bool FIRST, bool XE, bool TAB>
 __device__ __forceinline__ void ringcz_body(const MultiP<T, T> &P, T (*zl)[S * 64 * (16 / sizeof(T))]) {
   constexpr int VEC = 16 / sizeof(T), W = 64 * VEC, M = (S + VEC - 1) / VEC * VEC, WI = W - 2 * M;
@@ -563,7 +569,8 @@ __device__ __forceinline__ void ringcz_body(const MultiP<T, T> &P, T (*zl)[S * 6
   if (TAB) {
     active = unit < P.nunits;
     const int4 e = P.utab[active ? unit : 0];   // (wave-uniform: scalar loads)
-    wx = e.x;
+    wx = e.x;        // (x0)
+    khi = P.nfw;     // (the table's column limit)
     a = upper ? e.z : e.y;
     b = upper ? e.w : e.z;
     odd = !upper;
@@ -590,13 +597,13 @@ __device__ __forceinline__ void ringcz_body(const MultiP<T, T> &P, T (*zl)[S * 6
   }
   const int nbar = P.fold_rows > 0 ? S : S - 1;   // (barriers of a march: one more in a launch with fold strips)
   bool bad = false;
-  if (active) bad = ringc_march<T, K_FLUX, S, FIRST, false, XE, true>(P, wx, a, b, boff, odd, zl[w], zl[w ^ 1], fold, pos_at, klo, khi);
+  if (active) bad = ringc_march<T, K_FLUX, S, FIRST, false, XE, true, false, false, TAB>(P, wx, a, b, boff, odd, zl[w], zl[w ^ 1], fold, pos_at, klo, khi);
   else
     for (int k = 0; k < nbar; ++k) __syncthreads();
   if (__syncthreads_or(bad ? 1 : 0)) {
     if (active) {
       if (P.nfb && (threadIdx.x & 63) == 0) atomicAdd(P.nfb, 1u);
-      ringc_march<T, K_FLUX, S, FIRST, true, XE, true>(P, wx, a, b, boff, odd, zl[w], zl[w ^ 1], fold, pos_at, klo, khi);
+      ringc_march<T, K_FLUX, S, FIRST, true, XE, true, false, false, TAB>(P, wx, a, b, boff, odd, zl[w], zl[w ^ 1], fold, pos_at, klo, khi);
     } else {
       for (int k = 0; k < nbar; ++k) __syncthreads();
     }
@@ -705,6 +712,7 @@ static int launch_ringc_zip_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut
   if (tab) {
     P.utab = (const int4 *)tab->dev;
     P.nunits = tab->nunits;
+    P.nfw = tab->xlim;   // (no fold strips in a table launch: the field carries the column limit of ownership, ringcz_body)
   }
   const bool xe = c.xe;
   dim3 block(256), grid(c.grid_x, c.grid_y);
@@ -722,7 +730,7 @@ static int launch_ringc_zip_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut
   }
   GCMF_HIP(hipGetLastError());
   note_kernel(pl, std::string("gcmf::k_ringcz<") + tyname<T>() + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ", " + (xe ? "true" : "false") + (tab ? ", true>" : ">"), S,
-              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + (tab ? " units=" + std::to_string(tab->nunits) : std::string()));
+              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + (tab ? " units=" + std::to_string(tab->nunits) + (tab->tight ? " xoff=" + std::to_string(tab->xlim - P.nx) : std::string()) : std::string()));
   return GCMF_OK;
 }
 

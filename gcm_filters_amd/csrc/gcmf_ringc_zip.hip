@@ -1,5 +1,6 @@
 // k_ringcz<double>: pairs of strips zipped at a shared seam (gcmf_ringc_impl.hpp), nine levels (with early exits and in whole ring periods); eight, seven, six and five: gcmf_ringc_zip_{b,c,d}.hip
 #include "gcmf_ringc_impl.hpp"
+#include "gcmf_wet_cut.hpp"
 
 namespace gcmf {
 int launch_ringc_zip_b(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
@@ -18,6 +19,37 @@ int launch_ringc_zip(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hip
 // pairs (lo, mid, hi) of equal height, the height being the smallest at which all pairs of the launch fit ONE round of the 512 pair
 // slots.  Same march, same operands for every cell a pair owns; cells no pair owns are isolated, hold +-0 in the state planes
 // (gcmf_plan::pool_clean) and get their result from k_land_fix.
+// Round 8: options 3 and 4 take the TIGHT cut instead (wet_cut_tight, gcmf_wet_cut.hpp: no widening, rows needed by a window's owned columns
+// only, the window grid shifted to the coast); options 1 and 2 keep the rules above and the code below.  Either way a pair goes to the
+// device as (x0, lo, mid, hi), x0 = its window's first footprint column.
+static bool land_bytes(gcmf_plan *pl, std::vector<uint8_t> &bits, hipStream_t s, const char *who, int *rc) {
+  bits.resize((size_t)pl->g.rows * pl->g.nx);
+  if (hipMemcpyAsync(bits.data(), pl->lbits, bits.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+    set_error("%s: reading the plan's land bytes back failed: %s", who, hipGetErrorString(hipGetLastError()));
+    *rc = GCMF_ERR_HIP;
+    return false;
+  }
+  return true;
+}
+// the pairs of a table on the device (at least one entry: an all-land grid has none and launches nothing)
+static bool upload_units(gcmf_plan *pl, WetTable &nt, const std::vector<int4> &units, int *rc) {
+  nt.nunits = (int)units.size();
+  const size_t bytes = std::max<size_t>(1, units.size()) * sizeof(int4);
+  if (hipMalloc(&nt.dev, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    nt.dev = nullptr;
+    set_error("wet_table: no memory for %zu pairs", units.size());
+    *rc = GCMF_ERR_HIP;
+    return false;
+  }
+  pl->owned.push_back(nt.dev);
+  if (!units.empty() && hipMemcpy(nt.dev, units.data(), units.size() * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess) {
+    set_error("wet_table: uploading %zu pairs failed: %s", units.size(), hipGetErrorString(hipGetLastError()));
+    *rc = GCMF_ERR_HIP;
+    return false;
+  }
+  return true;
+}
 static const WetProfile *wet_profile(gcmf_plan *pl, int WI, hipStream_t s, int *rc) {
   for (const WetProfile &p : pl->wet_prof)
     if (p.WI == WI) return &p;
@@ -25,12 +57,8 @@ static const WetProfile *wet_profile(gcmf_plan *pl, int WI, hipStream_t s, int *
   // its running count of cells that exchange with a neighbour (the window's 128 columns: WI owned ones and the ghost columns, across
   // the x wrap)
   const int rows = pl->g.rows, nx = pl->g.nx, nwx = (nx + WI - 1) / WI, M = (128 - WI) / 2;
-  std::vector<uint8_t> bits((size_t)rows * nx);
-  if (hipMemcpyAsync(bits.data(), pl->lbits, bits.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
-    set_error("wet_profile: reading the plan's land bytes back failed: %s", hipGetErrorString(hipGetLastError()));
-    *rc = GCMF_ERR_HIP;
-    return nullptr;
-  }
+  std::vector<uint8_t> bits;
+  if (!land_bytes(pl, bits, s, "wet_profile", rc)) return nullptr;
   WetProfile p;
   p.WI = WI;
   p.need.assign((size_t)nwx * rows, 0);
@@ -63,9 +91,28 @@ const WetTable *wet_table(gcmf_plan *pl, const MultiArgs &a, long long even_marc
   if (!pl->wet_rows || !pl->wet_now || pl->mask_per_field || pl->stacked || pl->n_land <= 0 || !pl->lbits || pl->d.dtype != GCMF_F64 || pl->kind != K_FLUX ||
       g.fold || a.nbatch != 1 || !pl->pool_base || !pl->pool_bytes || S < 5 || S > 9 || nrows < 4)
     return nullptr;
+  const bool tight = pl->wet_rows >= 3;
   const WetTable *t = nullptr;
   for (const WetTable &c : pl->wet_tabs)
-    if (c.S == S && c.row_lo == a.row_lo && c.row_hi == a.row_hi && c.nbatch == a.nbatch) t = &c;
+    if (c.S == S && c.row_lo == a.row_lo && c.row_hi == a.row_hi && c.nbatch == a.nbatch && c.tight == tight) t = &c;
+  if (!t && tight) {
+    // once per plan, launch geometry and cut: the land bytes come back and the host-only planner weighs every offset of the window grid
+    // (no profile is kept: each depth of a filter asks once)
+    std::vector<uint8_t> bits;
+    if (!land_bytes(pl, bits, s, "wet_table", rc)) return nullptr;
+    const WetCut cut = wet_cut_tight(bits.data(), rows, g.nx, S, a.row_lo, a.row_hi);
+    WetTable nt;
+    nt.S = S; nt.row_lo = a.row_lo; nt.row_hi = a.row_hi; nt.nbatch = a.nbatch; nt.tight = true;
+    if (cut.ok) {
+      std::vector<int4> units;
+      units.reserve(cut.units.size());
+      for (const WetUnit &u : cut.units) units.push_back(make_int4(u.x0, u.lo, u.mid, u.hi));
+      nt.H = cut.H; nt.nstrips = cut.nstrips; nt.march = cut.march; nt.xlim = g.nx + cut.xoff;
+      if (!upload_units(pl, nt, units, rc)) return nullptr;
+    }
+    pl->wet_tabs.push_back(nt);
+    t = &pl->wet_tabs.back();
+  }
   if (!t) {
     const int WI = ringc_window(true, S), nwx = (g.nx + WI - 1) / WI, reach = S + 1;
     const WetProfile *prof = wet_profile(pl, WI, s, rc);
@@ -119,29 +166,19 @@ const WetTable *wet_table(gcmf_plan *pl, const MultiArgs &a, long long even_marc
       }
       // neighbours in x side by side, then up the grid: the order in which the even cut numbers its pairs (they share an XCD's L2)
       std::stable_sort(units.begin(), units.end(), [](const int4 &p, const int4 &q) { return p.z != q.z ? p.z < q.z : p.x < q.x; });
-      nt.nunits = (int)units.size();
       nt.nstrips = 2 * (nwx ? *std::max_element(per_window.begin(), per_window.end()) : 0);
       nt.march = (int)ringc_zip_rows(nt.H + S + 1, S, nullptr);
-      const size_t bytes = std::max<size_t>(1, units.size()) * sizeof(int4);
-      if (hipMalloc(&nt.dev, bytes) != hipSuccess) {
-        (void)hipGetLastError();
-        set_error("wet_table: no memory for %zu pairs", units.size());
-        *rc = GCMF_ERR_HIP;
-        return nullptr;
-      }
-      pl->owned.push_back(nt.dev);
-      if (!units.empty() && hipMemcpy(nt.dev, units.data(), units.size() * sizeof(int4), hipMemcpyHostToDevice) != hipSuccess) {
-        set_error("wet_table: uploading %zu pairs failed: %s", units.size(), hipGetErrorString(hipGetLastError()));
-        *rc = GCMF_ERR_HIP;
-        return nullptr;
-      }
+      nt.xlim = g.nx;   // this cut's window grid starts at column 0: window wx's footprint at wx WI - M, ownership below nx
+      const int M = (128 - WI) / 2;
+      for (int4 &u : units) u.x = u.x * WI - M;
+      if (!upload_units(pl, nt, units, rc)) return nullptr;
     }
     pl->wet_tabs.push_back(nt);
     t = &pl->wet_tabs.back();
   }
   if (!t->dev) return nullptr;
   // the policy of the zipped strips themselves: only where it marches at least 10 % fewer rows than the even cut (RingcCut::march)
-  if (pl->wet_rows == 1 && (even_march < 1 || (long long)t->march * 100 > even_march * 90)) return nullptr;
+  if ((pl->wet_rows == 1 || pl->wet_rows == 3) && (even_march < 1 || (long long)t->march * 100 > even_march * 90)) return nullptr;
   return t;
 }
 }  // namespace gcmf

@@ -337,7 +337,8 @@ int gcmf_last_kernel(gcmf_plan *plan, char *buf, int n);
  * "" for kernels that are not strip-marched).  Survives gcmf_last_kernel's reset.  A PMC traffic record only
  * describes the kernel at the geometry it was profiled with.  A k_ringcz launch whose strips were cut from the wet rows of each
  * window (option "wet_rows") appends " units=<pairs of strips>" (0: a grid that is all land, nothing was launched); H is then the
- * tallest strip and nstrips twice the largest number of pairs of a window. */
+ * tallest strip and nstrips twice the largest number of pairs of a window.  The tight cut (values 3 and 4 of the option) appends
+ * " xoff=<columns>" after that: the column at which its window grid starts. */
 int gcmf_last_kernel_geometry(gcmf_plan *plan, char *buf, int n);
 /* Wave strips of the register-ring kernels (k_ring) that met a NaN / inf since this was last called and were redone by the
  * general kernel (results are the same; each costs about two strip times).  Synchronises the device; reading resets.  A large
@@ -455,9 +456,12 @@ int gcmf_set_tuning(gcmf_plan *plan, int rows_per_wave, int xcd_remap, int multi
  * separated by grid-wide barriers instead of launch boundaries; same bits, measured 7 % slower at 2400 x 3600, hence opt-in; also env
  * GCMF_SINGLE_LAUNCH=1), "clenshaw_f32" 0 / 1 (GCMF_BACKWARD_F32
  * for every call of this plan, the slab drivers and gcmf_clenshaw_cut included), "ring_flux_f32" 1 / 0 (the forward ring kernel of the f32
- * flux kinds, gcmf_ring_flux_f32.hip; 0 = k_flux_multi2, same bits), "wet_rows" 1 / 0 / 2 (whole f64 flux grids with land, a lone field:
+ * flux kinds, gcmf_ring_flux_f32.hip; 0 = k_flux_multi2, same bits), "wet_rows" 3 / 0 / 1 / 2 / 4 (whole f64 flux grids with land, a lone field:
  * k_ringcz's strips are cut from the rows of each window that hold anything wet, so that no wave marches a tile that is all land;
- * 1 = where that marches at least 10 % fewer rows than the even cut, 2 = whenever eligible, 0 = never; same values -- the sign of an
+ * 3 (the default) = the TIGHT cut -- rows that a window's OWNED columns need, not widened, the window grid shifted in x to where the
+ * launch marches fewest rows (csrc/gcmf_wet_cut.hpp) -- where that marches at least 10 % fewer rows than the even cut, 4 = the tight
+ * cut whenever eligible; 1 and 2 = the same two policies with the cut of round 7 (rows needed by a window's 128-column footprint,
+ * widened by S + 1 rows, windows from column 0); 0 = never; same values -- the sign of an
  * exact zero next to land may differ; the FIRST eligible gcmf_apply of a plan builds the tables: it copies the plan's land bytes
  * (one byte per cell) to the host, synchronises the caller's stream and uploads the tables with a blocking copy -- once per plan and
  * launch depth, but not asynchronous and not legal inside a stream capture: capture after one warm-up call, or set 0).  Unknown names: GCMF_ERR_INVALID_ARG. */
