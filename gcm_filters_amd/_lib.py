@@ -22,6 +22,7 @@ ERR_KAPPA_W_GT1, ERR_KAPPA_S_GT1, ERR_KAPPA_NONE_ONE = 16, 17, 18
 ERR_WET_SOUTH_ROW, ERR_DXN_FOLD, ERR_DYN_FOLD = 19, 20, 21
 F32, F64 = 0, 1
 DEVICE_PTRS, OUT_F32, FORWARD_RECURRENCE, NO_RESIDENT, BACKWARD_F32, MASK_FROM_NAN = 0x1, 0x2, 0x4, 0x8, 0x10, 0x20
+FACES_FROM_NAN = 0x40   # the flux-form kinds' counterpart of MASK_FROM_NAN (include/gcmf.h)
 STEP_FIRST, STEP_LAST, STEP_LAND_ZERO, STEP_LAND_FIXED, STEP_CLENSHAW = 0x1, 0x2, 0x4, 0x8, 0x10
 
 EXPORTS = [
@@ -351,10 +352,11 @@ class Plan:
     # -- whole-filter / one-Laplacian calls ----------------------------------------------------
     def apply(self, p: np.ndarray, c: float, ins: Sequence[int], outs: Sequence[int], nbatch: int, *,
               device_ptrs: bool, out_f32: bool = False, stream: int = 0, forward: bool = False, backward_f32: bool = False,
-              mask_from_nan: bool = False):
+              mask_from_nan: bool = False, faces_from_nan: bool = False):
         p = np.ascontiguousarray(p, dtype=np.float64)
         flags = ((DEVICE_PTRS if device_ptrs else 0) | (OUT_F32 if out_f32 else 0) | (FORWARD_RECURRENCE if forward else 0)
-                 | (BACKWARD_F32 if backward_f32 else 0) | (MASK_FROM_NAN if mask_from_nan else 0))
+                 | (BACKWARD_F32 if backward_f32 else 0) | (MASK_FROM_NAN if mask_from_nan else 0)
+                 | (FACES_FROM_NAN if faces_from_nan else 0))
         check(load().gcmf_apply(self._h, p.ctypes.data_as(C.POINTER(C.c_double)), len(p) - 1, float(c),
                                 _ptr_array(ins), _ptr_array(outs), int(nbatch), flags, C.c_void_p(stream or None)))
 
@@ -532,7 +534,8 @@ class Plan:
         """Named per-plan switch (gcmf_set_option, include/gcmf.h): "cgrid_ring", "cgrid_ring_smax", "cgrid_ring_hmax", "cgrid_ring_ncarry", "pack_batch",
         "single_launch", "ringc9", "ringc_zip", "ringc_smax", "band_seq_cells", "zip_fold", "slab_nines", "clenshaw_f32", "ring_flux_f32", "wet_rows"
         ("wet_rows": 0 the even cut, 3 (default) / 4 the tight wet-row table where it marches 10 % fewer rows / whenever eligible, 1 / 2 the
-        same policies with the wider table of round 7)."""
+        same policies with the wider table of round 7), "gap_scratch_mb" (apply(faces_from_nan=True): the most scratch, in MiB, the
+        per-entry planes of one launch may take; default 4096, longer batches run as consecutive launches)."""
         check(load().gcmf_set_option(self._h, name.encode(), int(value)))
 
 

@@ -519,6 +519,40 @@ struct FieldMasks {
   FieldMasks &operator=(const FieldMasks &) = delete;
 };
 
+// GCMF_FACES_FROM_NAN: while one launch of such a call runs (the plan's mutex is held) the plan looks like a STACKED plan whose levels
+// are the launch's entries -- coefficient planes and land bytes in the work buffer, folded from the plan's own planes and each entry's
+// NaNs (launch_gap_fold) -- so the launches are exactly a stacked plan's: launch_ringc_levels and the level form of k_land_fix.  The
+// plan's own planes are never written; everything is put back however the call leaves.
+struct GapFaces {
+  gcmf_plan *pl;
+  const void *coef[3];
+  const uint8_t *lbits;
+  int64_t n_land, nlev, entry0;
+  bool stacked;
+  GapFaces(gcmf_plan *p, const double *cE, const double *cN, const double *ra, const uint8_t *bits, int64_t nbatch)
+      : pl(p), lbits(p->lbits), n_land(p->n_land), nlev(p->nlev), entry0(p->entry0), stacked(p->stacked) {
+    for (int k = 0; k < 3; ++k) coef[k] = pl->g.coef[k];
+    pl->g.coef[0] = cE; pl->g.coef[1] = cN; pl->g.coef[2] = ra;
+    pl->lbits = bits;
+    pl->n_land = std::max<int64_t>(1, n_land);
+    pl->stacked = true;
+    pl->nlev = nbatch;
+    pl->entry0 = 0;
+  }
+  ~GapFaces() {
+    for (int k = 0; k < 3; ++k) pl->g.coef[k] = coef[k];
+    pl->lbits = lbits;
+    pl->n_land = n_land;
+    pl->stacked = stacked;
+    pl->nlev = nlev;
+    pl->entry0 = entry0;
+  }
+  GapFaces(const GapFaces &) = delete;
+  GapFaces &operator=(const GapFaces &) = delete;
+};
+
+static const char *const FACES_WHERE = "GCMF_FACES_FROM_NAN is a gcmf_apply flag for whole-grid f64 ordinary plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T";
+
 static int lapl_step(ApplyCtx &x) {
   StepArgs a{};
   for (int k = 0; k < x.pl->ncomp; ++k) { a.t1[k] = x.din[k]; a.t0[k] = x.dout[k]; a.fb_out[k] = nullptr; }
@@ -914,6 +948,10 @@ static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double 
   const size_t oOut = per; if (!on_dev) per += szF;
   const bool from_nan = flags & GCMF_MASK_FROM_NAN;   // (run_whole has checked the plan: one component, a land-mask kind)
   const size_t oM = per; if (from_nan) per += align_up(ncell, 256);   // the entries' own mask bytes
+  // GCMF_FACES_FROM_NAN (run_whole has checked the plan and cut the batch to the scratch bound): the entries' own cE, cN, ra and land bytes
+  const bool faces = flags & GCMF_FACES_FROM_NAN;
+  const size_t szG = align_up(ncell * 8 + 256, 256), szL = align_up(ncell + 256, 256);   // (padded as precompute_levels pads a stacked plan's)
+  const size_t oG = per; if (faces) per += 3 * szG + szL;
   int rc = ensure_work(pl, per * pl->ncomp);
   if (rc || (rc = wait_for_work(pl, x.s))) return rc;
   char *w = (char *)pl->work;
@@ -943,6 +981,22 @@ static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double 
     if ((rc = launch_field_masks(pl, pl->g.mbits, x.din[0], bits, nbatch, x.s))) return rc;
     ++x.launches;
     FieldMasks own(pl, bits);
+    if ((rc = run_schedule(x, flags, use_multi, use_vmulti))) return rc;
+    return finish_call(x, on_dev, out, ncell * fbs, timing, timed);
+  }
+  if (faces) {
+    double *cEb = (double *)(w + oG), *cNb = (double *)(w + oG + szG), *rab = (double *)(w + oG + 2 * szG);
+    uint8_t *bits = (uint8_t *)(w + oG + 3 * szG);
+    const double *cE = (const double *)pl->g.coef[0], *cN = (const double *)pl->g.coef[1], *ra = (const double *)pl->g.coef[2];
+    GapFaces own(pl, cEb, cNb, rab, bits, nbatch);
+    int depths[1024];   // (asked with the guard in place: the answer run_schedule will get)
+    if (!use_multi || clenshaw_cut(pl, n_steps, depths, 1024, false, nbatch) <= 0) {
+      set_error("%s; for this plan and a polynomial of %d steps the stacked strips offer no backward cut (gcmf_clenshaw_cut_batch: fewer than "
+                "five steps, nx not a multiple of 4, GCMF_CLENSHAW=0 ...): filter with a plan built from wet_mask * [not NaN]", FACES_WHERE, n_steps);
+      return GCMF_ERR_UNSUPPORTED;
+    }
+    if ((rc = launch_gap_fold(pl, cE, cN, ra, x.din[0], cEb, cNb, rab, bits, nbatch, x.s))) return rc;
+    ++x.launches;
     if ((rc = run_schedule(x, flags, use_multi, use_vmulti))) return rc;
     return finish_call(x, on_dev, out, ncell * fbs, timing, timed);
   }
@@ -1071,6 +1125,17 @@ static int run_whole(gcmf_plan *pl, const double *p, int n_steps, double c, cons
         set_error("gcmf_apply: `out` must not alias `in` (filtering in place is not supported)");
         return GCMF_ERR_INVALID_ARG;
       }
+  if (flags & GCMF_FACES_FROM_NAN) {
+    const int gt = pl->d.grid_type;
+    const bool kind_ok = gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T;
+    const char *why = lapl_only ? "this is gcmf_laplacian" : !kind_ok ? "another grid type" : pl->d.dtype != GCMF_F64 ? "an f32 plan" : !pl->full ? "a row slab" :
+                      pl->stacked ? "a stacked plan (gcmf_plan_create_levels)" : (flags & GCMF_FORWARD_RECURRENCE) ? "combined with GCMF_FORWARD_RECURRENCE" :
+                      (flags & GCMF_MASK_FROM_NAN) ? "combined with GCMF_MASK_FROM_NAN" : nullptr;
+    if (why) {
+      set_error("%s (%s; grid type %d)", FACES_WHERE, why, gt);
+      return GCMF_ERR_UNSUPPORTED;
+    }
+  }
   if ((flags & GCMF_MASK_FROM_NAN) && (lapl_only || pl->kind != K_MASK || !pl->full)) {
     set_error("GCMF_MASK_FROM_NAN is a gcmf_apply flag for whole-grid plans of REGULAR_WITH_LAND, REGULAR_WITH_LAND_AREA_WEIGHTED and "
               "TRIPOLAR_REGULAR_WITH_LAND_AREA_WEIGHTED (this %s grid type %d%s)", lapl_only ? "is gcmf_laplacian on" : "plan has",
@@ -1101,22 +1166,29 @@ static int run_whole(gcmf_plan *pl, const double *p, int n_steps, double c, cons
   std::lock_guard<std::mutex> lk(pl->mu);
   GCMF_HIP(hipSetDevice(pl->d.device));
   pl->entry0 = 0;
+  // the most entries one launch takes: the scalar kernels index the batch with gridDim.y (<= 65535); GCMF_FACES_FROM_NAN: as many as
+  // keep the entries' own planes (25 bytes per cell and entry) at or under option "gap_scratch_mb", at least one
+  int64_t launch_nb = MAX_LAUNCH_BATCH;
+  if (flags & GCMF_FACES_FROM_NAN) {
+    const long long bound = (long long)std::max(0, pl->gap_scratch_mb) << 20, per_entry = 25LL * pl->d.ny * pl->d.nx;
+    launch_nb = std::max<int64_t>(1, std::min<int64_t>(MAX_LAUNCH_BATCH, bound / per_entry));
+  }
   if (!(flags & GCMF_DEVICE_PTRS) && nbatch > 1 && pl->host_chunk_bytes > 0) {
     const size_t entry = (size_t)pl->d.ny * pl->d.nx * dtype_size(pl->d.dtype);
     int64_t chunk_nb = (int64_t)(pl->host_chunk_bytes / entry);
     if (chunk_nb < 1) chunk_nb = 1;
-    if (chunk_nb > MAX_LAUNCH_BATCH) chunk_nb = MAX_LAUNCH_BATCH;
+    if (chunk_nb > launch_nb) chunk_nb = launch_nb;
     if (chunk_nb < nbatch) return run_host_pipelined(pl, p, n_steps, c, in, out, nbatch, flags, stream, lapl_only, chunk_nb);
   }
-  if (nbatch <= MAX_LAUNCH_BATCH)
+  if (nbatch <= launch_nb)
     return run_whole_locked(pl, p, n_steps, c, in, out, nbatch, flags, stream, lapl_only, true);
-  // very long batches of small fields: the scalar kernels index the batch with gridDim.y (<= 65535)
+  // very long batches of small fields, and batches whose per-entry planes exceed the scratch bound: consecutive launches
   const size_t cell = (size_t)pl->d.ny * pl->d.nx, ts = dtype_size(pl->d.dtype);
   const size_t fbs = lapl_only ? ts : ((pl->d.dtype == GCMF_F32 && !(flags & GCMF_OUT_F32)) ? 8 : ts);
   float ms_total = 0.f;
   int launches = 0;
-  for (int64_t b0 = 0; b0 < nbatch; b0 += MAX_LAUNCH_BATCH) {
-    const int64_t nb = nbatch - b0 < MAX_LAUNCH_BATCH ? nbatch - b0 : MAX_LAUNCH_BATCH;
+  for (int64_t b0 = 0; b0 < nbatch; b0 += launch_nb) {
+    const int64_t nb = nbatch - b0 < launch_nb ? nbatch - b0 : launch_nb;
     const void *in2[2] = {nullptr, nullptr};
     void *out2[2] = {nullptr, nullptr};
     for (int k = 0; k < pl->ncomp; ++k) {

@@ -15,6 +15,10 @@ bool land_ok(const gcmf_plan *pl, int n_steps) {
 
 // The building blocks and the slab drivers read the plan's own mask: GCMF_MASK_FROM_NAN is gcmf_apply's alone
 static bool refuse_mask_from_nan(uint32_t flags, const char *who) {
+  if (flags & GCMF_FACES_FROM_NAN) {   // (the flux kinds' counterpart: the entries' own coefficient planes exist inside gcmf_apply only)
+    set_error("%s: GCMF_FACES_FROM_NAN is a gcmf_apply flag (whole-grid f64 ordinary plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T)", who);
+    return true;
+  }
   if (!(flags & GCMF_MASK_FROM_NAN)) return false;
   set_error("%s: GCMF_MASK_FROM_NAN is a gcmf_apply flag (whole-grid plans of REGULAR_WITH_LAND, REGULAR_WITH_LAND_AREA_WEIGHTED and "
             "TRIPOLAR_REGULAR_WITH_LAND_AREA_WEIGHTED)", who);

@@ -192,7 +192,13 @@ struct gcmf_plan {
   bool stacked = false;
   int64_t nlev = 1;
   int64_t entry0 = 0;
-  int zero_land = 1;      // env GCMF_ZERO_LAND=0 turns it off
+  // GCMF_FACES_FROM_NAN (whole f64 plans of IRREGULAR_WITH_LAND, MOM5U, MOM5T): for the duration of such a gcmf_apply launch (the plan's
+  // mutex is held) the plan LOOKS stacked -- g.coef[0..2] and lbits point at the launch's own planes in the work buffer, one per batch entry,
+  // folded from the plan's planes and the entry's NaNs (launch_gap_fold), nlev = the launch's batch, entry0 = 0, n_land says "has land" --
+  // and everything is put back when the launch leaves (GapFaces, gcmf_api.hip).  The lock-free queries may see the launch's values, as
+  // with mask_per_field.  gap_scratch_mb: the most scratch one launch may take (25 bytes per cell and entry); longer batches are cut.
+  int gap_scratch_mb = 4096;   // gcmf_set_option "gap_scratch_mb"
+  int zero_land = 1;     // env GCMF_ZERO_LAND=0 turns it off
   int ring = 1;           // env GCMF_RING=0: deep launches stay with k_flux_multi2 / k_scalar_multi
   unsigned *ring_nfb = nullptr;    // device counter behind gcmf_ring_fallbacks (lives behind zero_row)
   const void *zero_row = nullptr;  // nx zeros: what rows beyond a closed boundary read as coefficients / mask bits (k_ring)
@@ -339,4 +345,8 @@ int precompute(gcmf_plan *pl, const void *const *dplanes, const void *const *hpl
 int precompute_levels(gcmf_plan *pl, const void *const *dplanes, const int64_t *plane_levels);
 // GCMF_MASK_FROM_NAN: the mask bytes of every entry of a batch, from the plan's own bytes `wet` and the entries' NaNs (k_pre_mask)
 int launch_field_masks(gcmf_plan *pl, const uint8_t *wet, const void *fields, uint8_t *bits, int64_t nbatch, hipStream_t s);
+// GCMF_FACES_FROM_NAN: the coefficient planes and land bytes of every entry of a batch of f64 fields, from an ordinary flux plan's own
+// planes (cE, cN, ra) and the entries' NaNs (k_pre_isolated<double, true, MOM5>, gcmf_gap_fold.hpp); nx must be a multiple of 4
+int launch_gap_fold(gcmf_plan *pl, const double *cE, const double *cN, const double *ra, const void *fields, double *cEo, double *cNo,
+                    double *rao, uint8_t *bits, int64_t nbatch, hipStream_t s);
 }  // namespace gcmf

@@ -6,6 +6,7 @@
 // Every kernel here works on GLOBAL (ny, nx) planes with periodic wrap in x and y (np.roll semantics) and
 // the tripole fold where the grid type has one; row slabs for multi-GPU plans are cut out afterwards.
 #include "gcmf_internal.hpp"
+#include "gcmf_gap_fold.hpp"   // the per-entry fold rule of GCMF_FACES_FROM_NAN, shared with a host program
 
 #include <cmath>
 
@@ -85,8 +86,77 @@ int launch_field_masks(gcmf_plan *pl, const uint8_t *wet, const void *fields, ui
 
 // ---- cells that exchange nothing with their neighbours ---------------------------------------------------
 // flux form: all four faces of the cell are closed (and, on the tripole seam, the partner's face onto it)
-template <typename T>
-__global__ void k_pre_isolated(const T *cE, const T *cN, uint8_t *bits, int ny, int nx, int tripolar, int *count) {
+//
+// GAPS (GCMF_FACES_FROM_NAN, per call; f64, nx a multiple of 4, no tripole seam): cE / cN / ra = an ordinary plan's planes, `field` = the
+// fields of a batch (gridDim.y entries of ny x nx cells); entry b gets its own cEo / cNo / rao planes and plane of `bits`, folded from the
+// plan's planes and the entry's NaNs by the rule of gcmf_gap_fold.hpp (MOM5: the reference's transposed mask pairs) -- ONE streaming pass:
+// a lane owns four consecutive cells of a row, reads three rows of the field (columns i0 - 1 .. i0 + 4: 16-byte loads where the caller's
+// array allows them), cE at i0 - 1 .. i0 + 3, cN and ra of its row and cN of the row below, and writes 2 x 32 bytes of coefficients, 32
+// bytes of ra and the four land bytes as one 32-bit word.  The fold needs the west and south neighbours' ENTRY coefficients for the byte:
+// they are recomputed from the same loads, not read back.
+template <typename T> struct alignas(16) GapPair { T a, b; };
+template <typename T> __device__ __forceinline__ void gap_load4(const T *p, bool al16, T *v) {
+  if (al16) {
+    const GapPair<T> lo = *reinterpret_cast<const GapPair<T> *>(p), hi = *reinterpret_cast<const GapPair<T> *>(p + 2);
+    v[0] = lo.a; v[1] = lo.b; v[2] = hi.a; v[3] = hi.b;
+  } else {
+    v[0] = p[0]; v[1] = p[1]; v[2] = p[2]; v[3] = p[3];
+  }
+}
+template <typename T> __device__ __forceinline__ void gap_store4(T *p, const T *v) {   // (the work buffer's planes: always aligned)
+  *reinterpret_cast<GapPair<T> *>(p) = GapPair<T>{v[0], v[1]};
+  *reinterpret_cast<GapPair<T> *>(p + 2) = GapPair<T>{v[2], v[3]};
+}
+
+template <typename T, bool GAPS = false, bool MOM5 = false>
+__global__ void k_pre_isolated(const T *cE, const T *cN, uint8_t *bits, int ny, int nx, int tripolar, int *count, const T *field,
+                               T *cEo, T *cNo, const T *ra, T *rao) {
+  if constexpr (GAPS) {
+    static_assert(sizeof(T) == 8, "the per-entry fold exists for f64 plans");
+    const long long plane = (long long)ny * nx, eoff = (long long)blockIdx.y * plane;
+    field += eoff; cEo += eoff; cNo += eoff; rao += eoff; bits += eoff;
+    const bool al16 = (reinterpret_cast<uintptr_t>(field) & 15u) == 0;   // (nx % 4 == 0: one answer for every quad of the entry)
+    const int nq = nx >> 2;
+    const long long nquad = (long long)ny * nq;
+    for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nquad; q += (long long)gridDim.x * blockDim.x) {
+      const int j = (int)(q / nq), i0 = (int)(q - (long long)j * nq) * 4;
+      const int iw = wrapi(i0 - 1, nx), ie = wrapi(i0 + 4, nx);
+      const long long rj = (long long)j * nx, rn = (long long)wrapi(j + 1, ny) * nx, rs = (long long)wrapi(j - 1, ny) * nx;
+      // n[r][k]: is the field present at row (south, own, north)[r], column i0 - 1 + k
+      bool n[3][6];
+      const long long rows[3] = {rs, rj, rn};
+#pragma unroll
+      for (int r = 0; r < 3; ++r) {
+        T v[4];
+        gap_load4(field + rows[r] + i0, al16, v);
+        n[r][0] = gap_present(field[rows[r] + iw]);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) n[r][1 + k] = gap_present(v[k]);
+        n[r][5] = gap_present(field[rows[r] + ie]);
+      }
+      T e[5], cn[4], cs[4], rv[4];
+      e[0] = cE[rj + iw];
+      gap_load4(cE + rj + i0, true, e + 1);
+      gap_load4(cN + rj + i0, true, cn);
+      gap_load4(cN + rs + i0, true, cs);
+      gap_load4(ra + rj + i0, true, rv);
+      T eb[5], nb[4];
+      unsigned word = 0;
+#pragma unroll
+      for (int k = 0; k < 5; ++k) eb[k] = gap_fold_cE<T, MOM5>(e[k], n[1][k], n[1][k + 1], n[2][k]);   // columns i0 - 1 .. i0 + 3
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        nb[k] = gap_fold_cN<T, MOM5>(cn[k], n[1][k + 1], n[1][k + 2], n[2][k + 1]);
+        const T sb = gap_fold_cN<T, MOM5>(cs[k], n[0][k + 1], n[0][k + 2], n[1][k + 1]);   // the southern neighbour's north face
+        word |= gap_land_byte(eb[k + 1], eb[k], nb[k], sb) << (8 * k);
+      }
+      gap_store4(cEo + rj + i0, eb + 1);
+      gap_store4(cNo + rj + i0, nb);
+      gap_store4(rao + rj + i0, rv);
+      *reinterpret_cast<unsigned *>(bits + rj + i0) = word;
+    }
+    return;
+  }
   int mine = 0;
   CELL_LOOP(ny, nx) {
     CELL_JI(nx)
@@ -437,7 +507,7 @@ template <typename T> static int precompute_t(gcmf_plan *pl, const void *const *
     } else {
       if ((rc = galloc((void **)&gisol, plane))) return rc;
       hipLaunchKernelGGL(k_pre_isolated<T>, grid, block, 0, s, (const T *)gplanes[0], (const T *)gplanes[1], gisol, ny, nx,
-                         pl->tripolar ? 1 : 0, dcount);
+                         pl->tripolar ? 1 : 0, dcount, (const T *)nullptr, (T *)nullptr, (T *)nullptr, (const T *)nullptr, (T *)nullptr);
     }
     GCMF_HIP(hipGetLastError());
   }
@@ -529,7 +599,8 @@ int precompute_levels(gcmf_plan *pl, const void *const *dp, const int64_t *plane
       hipLaunchKernelGGL(k_pre_irregular<T>, grid, block, 0, s, P(0), P(1), P(2), P(3), P(4), P(5), P(6), P(7), cE, cN, ra, ny, nx, dflags);
     else
       hipLaunchKernelGGL(k_pre_mom5<T>, grid, block, 0, s, P(0), P(1), P(2), P(3), P(4), P(5), cE, cN, ra, ny, nx, gt == GCMF_MOM5U ? 1 : 0);
-    hipLaunchKernelGGL(k_pre_isolated<T>, grid, block, 0, s, (const T *)cE, (const T *)cN, isol + (size_t)l * plane, ny, nx, 0, dflags + 1);
+    hipLaunchKernelGGL(k_pre_isolated<T>, grid, block, 0, s, (const T *)cE, (const T *)cN, isol + (size_t)l * plane, ny, nx, 0, dflags + 1,
+                       (const T *)nullptr, (T *)nullptr, (T *)nullptr, (const T *)nullptr, (T *)nullptr);
     GCMF_HIP(hipGetLastError());
     int got[2] = {0, 0};   // (per level: the count of a deep stack would not fit an int)
     GCMF_HIP(hipMemcpyAsync(got, dflags, sizeof got, hipMemcpyDeviceToHost, s));
@@ -557,6 +628,27 @@ int precompute_levels(gcmf_plan *pl, const void *const *dp, const int64_t *plane
   for (int k = 0; k < 3; ++k) pl->g.coef[k] = c[k];
   pl->lbits = isol;
   pl->n_land = n_land;   // of all levels: a plan with land on any level has land
+  return GCMF_OK;
+}
+
+// The planes of every entry of a batch of fields (GCMF_FACES_FROM_NAN; the caller has checked: a whole f64 plan of IRREGULAR_WITH_LAND,
+// MOM5U or MOM5T, nx % 4 == 0; the outputs are nbatch planes each, 16-byte aligned)
+int launch_gap_fold(gcmf_plan *pl, const double *cE, const double *cN, const double *ra, const void *fields, double *cEo, double *cNo,
+                    double *rao, uint8_t *bits, int64_t nbatch, hipStream_t s) {
+  const int ny = (int)pl->d.ny, nx = (int)pl->d.nx;
+  if (nx % 4 || pl->d.dtype != GCMF_F64 || nbatch < 1 || nbatch > 65535) {
+    set_error("k_pre_isolated (GCMF_FACES_FROM_NAN): needs an f64 plan, nx a multiple of 4 and 1 .. 65535 entries");
+    return GCMF_ERR_INVALID_ARG;
+  }
+  const long long nquad = (long long)ny * (nx / 4);
+  dim3 block(256), grid((unsigned)std::min<long long>((nquad + 255) / 256, 4096), (unsigned)nbatch);
+  if (pl->d.grid_type == GCMF_IRREGULAR_WITH_LAND)
+    hipLaunchKernelGGL((k_pre_isolated<double, true, false>), grid, block, 0, s, cE, cN, bits, ny, nx, 0, (int *)nullptr, (const double *)fields,
+                       cEo, cNo, ra, rao);
+  else
+    hipLaunchKernelGGL((k_pre_isolated<double, true, true>), grid, block, 0, s, cE, cN, bits, ny, nx, 0, (int *)nullptr, (const double *)fields,
+                       cEo, cNo, ra, rao);
+  GCMF_HIP(hipGetLastError());
   return GCMF_OK;
 }
 

@@ -10,11 +10,11 @@ from __future__ import annotations
 import enum
 import warnings
 from dataclasses import dataclass, field
-from typing import Iterable, NamedTuple, Optional
+from typing import Any, Iterable, NamedTuple, Optional
 
 import numpy as np
 
-from .kernels import NAN_MASK_GRID_TYPES, PLAN_CACHE_MODES, plan_cache_mode, kernels_cache_enabled
+from .kernels import GAP_FOLD_GRID_TYPES, NAN_MASK_GRID_TYPES, PLAN_CACHE_MODES, plan_cache_mode, kernels_cache_enabled
 from .kernels import last_path as kernels_last_path
 from .kernels import (
     ALL_KERNELS,
@@ -168,19 +168,24 @@ def _compute_filter_spec(filter_scale, dx_min, filter_shape, transition_width=np
 # ------------------------------------------------------------------------------------------------
 # the operator interface xarray.apply_ufunc calls (reference filter.py:154-291)
 # ------------------------------------------------------------------------------------------------
-def _create_filter_func(filter_spec: FilterSpec, Laplacian, evaluation: str = "auto", plan_cache=None, nan_mask: bool = False):
+def _create_filter_func(filter_spec: FilterSpec, Laplacian, evaluation: str = "auto", plan_cache=None, nan_mask=False):
     """Returns ``filter_func(field, *grid_args)``: first argument the field (last two axes = y, x; leading
     axes are independent batches), then the grid variables in ``Laplacian.required_grid_args()`` order.
     ``evaluation``, ``plan_cache``, ``nan_mask``: see ``Filter``."""
     forward = _forward_only(evaluation)
     backward = evaluation == "backward"
     memo = _LaplacianMemo(Laplacian)
+    # nan_mask="auto": per-slice masks by whichever route the library has for the kind -- mask bytes (the land-mask kinds) or face
+    # coefficients (the flux-form kinds)
+    faces = nan_mask == "auto" and Laplacian.GRID_TYPE in GAP_FOLD_GRID_TYPES
+    masks = bool(nan_mask) and not faces
 
     def filter_func(field, *args):
         assert len(args) == len(Laplacian.required_grid_args())
         with plan_cache_mode(plan_cache):
             laplacian = memo.get(args)  # device plan: cached while the grid arrays are unchanged
-            out = laplacian._run([field], spec=filter_spec, forward=forward, backward_f32=backward, mask_from_nan=nan_mask)[0]
+            out = laplacian._run([field], spec=filter_spec, forward=forward, backward_f32=backward, mask_from_nan=masks,
+                                 faces_from_nan=faces)[0]
         filter_func.last_path = kernels_last_path()
         return out
 
@@ -315,6 +320,13 @@ class Filter:
         one plan per slice.  The output is NaN exactly where the input is; +-inf is data, not a gap; a slice without NaN gives the bits
         of ``nan_mask=False``.  Only for ``REGULAR_WITH_LAND``, ``REGULAR_WITH_LAND_AREA_WEIGHTED`` and
         ``TRIPOLAR_REGULAR_WITH_LAND_AREA_WEIGHTED`` (``ValueError`` otherwise); ``last_path`` is ``"strips"``.
+        ``"auto"``: the same contract wherever the library has per-slice masks -- on those three grid types it is ``True``'s route, on
+        ``IRREGULAR_WITH_LAND``, ``MOM5U`` and ``MOM5T`` every slice's FACE coefficients are folded on the device from the plan's own
+        and the slice's NaNs inside the call (``GCMF_FACES_FROM_NAN``: one streaming pass, 25 bytes of scratch per cell and slice, no
+        plan build), bit for bit what the stacked plan of ``wet_mask(n, y, x) = wet_mask * notnull(field)`` gives.  Where that call is
+        not on offer -- ``evaluation="reference"``, float32 grids, ``nx % 4 != 0``, polynomials without a backward cut -- the masks are
+        built here and run as grid variables with a leading axis: the same contract, slower.  ``ValueError`` on the other five grid
+        types, and for any other string.
 
     Attributes
     ----------
@@ -331,7 +343,7 @@ class Filter:
     grid_vars: dict = field(default_factory=dict, repr=False)
     evaluation: str = field(default="auto", kw_only=True, repr=False)   # extension, see the docstring
     plan_cache: Optional[str] = field(default=None, kw_only=True, repr=False)   # extension, see the docstring
-    nan_mask: bool = field(default=False, kw_only=True, repr=False)   # extension, see the docstring
+    nan_mask: Any = field(default=False, kw_only=True, repr=False)   # False / True / "auto": extension, see the docstring
 
     # Same fields, defaults, attribute names (Laplacian, filter_spec, n_steps, grid_ds) and exception / warning texts as
     # the reference class (gcm_filters/filter.py:294-393): they are the contract its users and tests rely on.  The
@@ -341,7 +353,14 @@ class Filter:
         _forward_only(self.evaluation)   # ValueError for anything else
         if self.plan_cache is not None and self.plan_cache not in PLAN_CACHE_MODES:
             raise ValueError(f"plan_cache must be one of {PLAN_CACHE_MODES} or None, not {self.plan_cache!r}")
-        if self.nan_mask and self.grid_type not in NAN_MASK_GRID_TYPES:
+        if isinstance(self.nan_mask, str):
+            if self.nan_mask != "auto":
+                raise ValueError(f'nan_mask must be False, True or "auto", not {self.nan_mask!r}')
+            if self.grid_type not in NAN_MASK_GRID_TYPES + GAP_FOLD_GRID_TYPES:
+                raise ValueError(f'nan_mask="auto" needs one of the grid types '
+                                 f"{', '.join(g.name for g in NAN_MASK_GRID_TYPES + GAP_FOLD_GRID_TYPES)}, "
+                                 f"not {getattr(self.grid_type, 'name', self.grid_type)}")
+        elif self.nan_mask and self.grid_type not in NAN_MASK_GRID_TYPES:
             raise ValueError(f"nan_mask=True needs one of the grid types {', '.join(g.name for g in NAN_MASK_GRID_TYPES)}, "
                              f"not {getattr(self.grid_type, 'name', self.grid_type)}")
         self._reject_bad_arguments()
@@ -441,12 +460,12 @@ class Filter:
     def _operator(self, make):
         """``make(filter_spec, Laplacian, evaluation)`` (one of the two factories above), built once per Filter: the closure
         remembers the Laplacian object of its last call (_LaplacianMemo)."""
-        key = (make, id(self.filter_spec), self.Laplacian, self.evaluation, self.plan_cache, bool(self.nan_mask))
+        key = (make, id(self.filter_spec), self.Laplacian, self.evaluation, self.plan_cache, self.nan_mask if isinstance(self.nan_mask, str) else bool(self.nan_mask))
         hit = self.__dict__.get("_op")
         if hit is None or hit[0] != key:
             extra = {} if self.plan_cache is None else {"plan_cache": self.plan_cache}
             if self.nan_mask:
-                extra["nan_mask"] = True
+                extra["nan_mask"] = self.nan_mask if isinstance(self.nan_mask, str) else True
             hit = (key, make(self.filter_spec, self.Laplacian, self.evaluation, **extra))
             self.__dict__["_op"] = hit
         return hit[1]

@@ -51,6 +51,9 @@ NAN_MASK_GRID_TYPES = (GridType.REGULAR_WITH_LAND, GridType.REGULAR_WITH_LAND_AR
 # the grid types whose per-level grid variables (wet_mask(z, y, x), kappa(z, y, x)) fold into ONE stacked plan (gcmf_plan_create_levels):
 # flux form, no tripole seam; float64 and the default (backward) evaluation only
 STACKED_GRID_TYPES = (GridType.IRREGULAR_WITH_LAND, GridType.MOM5U, GridType.MOM5T)
+# ... and the same three are the ones whose per-entry FACE coefficients the library folds on the device from each field's own NaNs
+# (Filter(nan_mask="auto"), GCMF_FACES_FROM_NAN): the launches are a stacked plan's, the levels are the call's entries
+GAP_FOLD_GRID_TYPES = STACKED_GRID_TYPES
 # ... by default only for MORE levels than the plan cache holds plans (GCMF_PLAN_CACHE_SIZE, 64): there the per-level route rebuilds every
 # level's plan on every call (80 levels of 1080 x 1440: 600 ms against 26 ms per application); up to that many levels the cached
 # per-level plans run a lone field each on the zipped strips and measured the same as the stacked call's plain strips (16 levels of
@@ -602,7 +605,7 @@ class _DeviceLaplacian:
             raise _translate(e) from None
         return [_same_kind(out, given)]
 
-    def _run_levels(self, fields, spec, out_f32, forward=False, backward_f32=False, mask_from_nan=False):
+    def _run_levels(self, fields, spec, out_f32, forward=False, backward_f32=False, mask_from_nan=False, faces_from_nan=False):
         given = list(fields)
         fields = [_unwrap(f) for f in fields]
         shape = tuple(fields[0].shape)
@@ -613,7 +616,9 @@ class _DeviceLaplacian:
         pad = len(out_lead) - len(self._glead)
         # the stacked plan: a whole filter, backward evaluation; entry b of the flattened leading shape runs on level b % nlev, so the
         # grid variables' leading shape must be the TAIL of the field's (none of its size-1 dims stretched by the field)
-        if self._stacked and spec is not None and not forward and not mask_from_nan and self._NCOMP == 1 and out_lead[pad:] == self._glead:
+        # (faces_from_nan: the stacked plan's levels are not the entries' -- the per-level plans run the flagged call, as for mask_from_nan)
+        if self._stacked and spec is not None and not forward and not mask_from_nan and not faces_from_nan and self._NCOMP == 1 \
+                and out_lead[pad:] == self._glead:
             res = self._run_stacked(given[0], fields[0], spec, out_lead, core)
             if res is not None:
                 return res
@@ -624,7 +629,8 @@ class _DeviceLaplacian:
             for f in fields:
                 fb = f.expand(*out_lead, *core) if _is_torch(f) else np.broadcast_to(f, out_lead + core)
                 sub.append(fb[idx])
-            res = lap._run(sub, spec=spec, out_f32=out_f32, forward=forward, backward_f32=backward_f32, mask_from_nan=mask_from_nan)
+            res = lap._run(sub, spec=spec, out_f32=out_f32, forward=forward, backward_f32=backward_f32, mask_from_nan=mask_from_nan,
+                           faces_from_nan=faces_from_nan)
             if outs is None:
                 if _is_torch(res[0]):
                     import torch
@@ -677,19 +683,25 @@ class _DeviceLaplacian:
         return PLAN_CACHE.get(key, factory, () if (on_gpu or mode == "verify") else self._planes)
 
     def _run(self, fields: Sequence, spec=None, out_f32: bool = False, forward: bool = False, backward_f32: bool = False,
-             mask_from_nan: bool = False):
+             mask_from_nan: bool = False, faces_from_nan: bool = False):
         """Shared driver of __call__ (spec None: one Laplacian) and of filter_func (spec: whole polynomial).
         forward: evaluate the polynomial by the reference's forward recurrence with its accumulation scheme (f64 running sum
         also for f32 state) even where the library would evaluate it backwards (Filter(evaluation="reference")).
         backward_f32: evaluate it backwards also for f32 scalar / B-grid fields, whose default is the forward recurrence
         (Filter(evaluation="backward"): faster, all f32).
         mask_from_nan: every 2-D slice of the field is filtered with its own wet mask, wet_mask * [slice is not NaN]
-        (Filter(nan_mask=True); the three land-mask grid types, spec given)."""
+        (Filter(nan_mask=True); the three land-mask grid types, spec given).
+        faces_from_nan: the same contract on the three flux-form grid types (Filter(nan_mask="auto"), spec given): the library folds
+        every slice's face coefficients from the plan's and the slice's NaNs inside the call (GCMF_FACES_FROM_NAN); where that call is
+        not on offer -- forward, float32, nx % 4 != 0, no backward cut -- the explicit masks run as grid variables (_gap_fallback)."""
         if mask_from_nan and (spec is None or self.GRID_TYPE not in NAN_MASK_GRID_TYPES):
             raise ValueError("mask_from_nan needs a filter application on one of the grid types "
                              + ", ".join(g.name for g in NAN_MASK_GRID_TYPES))
+        if faces_from_nan and (spec is None or mask_from_nan or self.GRID_TYPE not in GAP_FOLD_GRID_TYPES):
+            raise ValueError("faces_from_nan needs a filter application (without mask_from_nan) on one of the grid types "
+                             + ", ".join(g.name for g in GAP_FOLD_GRID_TYPES))
         if self._glead is not None:
-            return self._run_levels(fields, spec, out_f32, forward, backward_f32, mask_from_nan)
+            return self._run_levels(fields, spec, out_f32, forward, backward_f32, mask_from_nan, faces_from_nan)
         given = list(fields)
         fields = [_unwrap(f) for f in fields]
         shape = tuple(fields[0].shape)
@@ -702,6 +714,8 @@ class _DeviceLaplacian:
         ny, nx = shape[-2:]
         nbatch = int(np.prod(shape[:-2], dtype=np.int64)) if len(shape) > 2 else 1
         gpu = all(_on_gpu(f) for f in fields)
+        if faces_from_nan and nbatch and (forward or dtype != _lib.F64 or nx % 4):
+            return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32)
         if spec is None:
             out_np = _lib.np_dtype(dtype)
         else:
@@ -710,6 +724,8 @@ class _DeviceLaplacian:
             import torch
             dev = fields[0].device.index
             plan = self._plan(dtype, (ny, nx), dev)
+            if faces_from_nan and nbatch and not plan.clenshaw_cut(int(spec.n_steps), nbatch):
+                return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32)
             tdt = torch.float64 if dtype == _lib.F64 else torch.float32
             ins = [f if (f.dtype == tdt and f.is_contiguous()) else f.to(tdt).contiguous() for f in fields]
             outs = [torch.empty(shape, dtype=torch.float64 if out_np == np.float64 else torch.float32,
@@ -718,18 +734,25 @@ class _DeviceLaplacian:
                 # (the device index is passed explicitly: torch.cuda.current_stream() without one costs ~10 us per call, and
                 # libgcmf selects the plan's device itself -- no device context manager on this path)
                 cur = torch.cuda.current_stream(dev)
-                self._call(plan, spec, [t.data_ptr() for t in ins], [t.data_ptr() for t in outs], nbatch,
-                           True, out_f32, cur.cuda_stream, forward, backward_f32, mask_from_nan)
+                try:
+                    self._call(plan, spec, [t.data_ptr() for t in ins], [t.data_ptr() for t in outs], nbatch,
+                               True, out_f32, cur.cuda_stream, forward, backward_f32, mask_from_nan, faces_from_nan)
+                except _lib.GcmfError as e:
+                    if not (faces_from_nan and _no_backward_cut(e)):
+                        raise
+                    return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32)
                 for t, f in zip(ins, fields):   # inputs converted above are temporaries: keep them alive until the stream is done
                     if t is not f:
                         t.record_stream(cur)
             return [_same_kind(o, g) for o, g in zip(outs, given)]   # (cupy in, cupy out -- as the reference's gpu_compat path)
         plan = self._plan(dtype, (ny, nx))
+        if faces_from_nan and nbatch and not plan.clenshaw_cut(int(spec.n_steps), nbatch):
+            return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32)
         host = [f.detach().cpu().numpy() if _is_torch(f) else np.asarray(f) for f in fields]
         ins = [np.ascontiguousarray(f, dtype=_lib.np_dtype(dtype)) for f in host]
         outs = [_host_output(shape, out_np) for _ in fields]
         if nbatch == 1 and spec is not None and self._NCOMP == 1 and ny * nx >= host_blocks.MIN_CELLS and not forward and not backward_f32 \
-                and not mask_from_nan:   # (the row blocks are plans of their own, with the static mask)
+                and not mask_from_nan and not faces_from_nan:   # (the row blocks are plans of their own, with the static mask)
             # one large host field: upload / recurrence / download overlapped by row blocks (host_blocks.py)
             pipe = self._row_blocks(plan, dtype, ny, nx, spec)
             if pipe is not None:
@@ -742,9 +765,31 @@ class _DeviceLaplacian:
                 _PATH.last = "host-row-blocks"
                 return outs
         if nbatch:
-            self._call(plan, spec, [a.ctypes.data for a in ins], [a.ctypes.data for a in outs], nbatch, False,
-                       out_f32, 0, forward, backward_f32, mask_from_nan)
+            try:
+                self._call(plan, spec, [a.ctypes.data for a in ins], [a.ctypes.data for a in outs], nbatch, False,
+                           out_f32, 0, forward, backward_f32, mask_from_nan, faces_from_nan)
+            except _lib.GcmfError as e:
+                if not (faces_from_nan and _no_backward_cut(e)):
+                    raise
+                return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32)
         return outs
+
+    def _gap_fallback(self, given, fields, spec, out_f32, forward, backward_f32):
+        """faces_from_nan where the flagged call is not on offer: wet_mask * notnull(field) built here and handed in as a grid variable
+        with the field's leading dims -- the per-level (or stacked) route that existed before the flag, the same contract, slower.  The
+        plans it makes belong to this one field's gaps and do not stay in the plan cache."""
+        f = fields[0]
+        wm = self._planes[0]   # (wet_mask is the first grid argument of the three kinds)
+        if _is_torch(f):
+            import torch
+            w = wm if _is_torch(wm) else torch.as_tensor(np.asarray(wm))
+            m = (~torch.isnan(f)).to(w.dtype) * w.to(f.device)
+        else:
+            w = wm.detach().cpu().numpy() if _is_torch(wm) else np.asarray(wm)
+            m = (~np.isnan(np.asarray(f))).astype(w.dtype) * w
+        with plan_cache_mode("off"):
+            lap = type(self)(m, *self._planes[1:], _skip_kappa_one=True, _stack_levels=self._stack_levels)
+            return lap._run(given, spec=spec, out_f32=out_f32, forward=forward, backward_f32=backward_f32)
 
     def _row_blocks(self, plan, dtype, ny, nx, spec):
         """The row-block pipeline of `plan` for this polynomial length, built once the plan has seen a few single-field
@@ -777,7 +822,7 @@ class _DeviceLaplacian:
             return pipe
 
     def _call(self, plan, spec, ins, outs, nbatch, device_ptrs, out_f32, stream, forward=False, backward_f32=False,
-              mask_from_nan=False):
+              mask_from_nan=False, faces_from_nan=False):
         try:
             if spec is None:
                 plan.laplacian(ins, outs, nbatch, device_ptrs=device_ptrs, stream=stream)
@@ -786,10 +831,15 @@ class _DeviceLaplacian:
                 c = 2 / spec.s_max if self.is_dimensional else 2 / (spec.s_max * spec.dx_min_sq)
                 plan.apply(np.asarray(spec.p, dtype=np.float64), c, ins, outs, nbatch, device_ptrs=device_ptrs,
                            out_f32=out_f32, stream=stream, forward=forward, backward_f32=backward_f32,
-                           mask_from_nan=mask_from_nan)
+                           mask_from_nan=mask_from_nan, faces_from_nan=faces_from_nan)
                 _note_path(plan.last_path(), plan.device)
         except _lib.GcmfError as e:
             raise _translate(e) from None
+
+
+def _no_backward_cut(err) -> bool:
+    """GCMF_FACES_FROM_NAN refused because the stacked strips offer this plan and polynomial no backward cut (include/gcmf.h)."""
+    return err.status == _lib.ERR_UNSUPPORTED and "no backward cut" in err.message
 
 
 # ---- which path ran (VERDICT r5 item 8) ------------------------------------------------------------------------------------------

@@ -95,6 +95,23 @@ typedef enum gcmf_dtype { GCMF_F32 = 0, GCMF_F64 = 1 } gcmf_dtype;
                               /* GCMF_ERR_UNSUPPORTED for it.  While a flagged call runs, the plan's queries that take no lock            */
                               /* (gcmf_has_land, gcmf_clenshaw_cut[_batch], gcmf_resident_supported) may see the call's own masks         */
                               /* ("has land"): do not call them from another thread during a flagged gcmf_apply on the same plan.         */
+#define GCMF_FACES_FROM_NAN 0x40u /* gcmf_apply, whole-grid f64 ORDINARY (not stacked) plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T (host or     */
+                              /* device pointers, any nbatch): the same contract as GCMF_MASK_FROM_NAN for the flux-form kinds -- batch    */
+                              /* entry b is filtered with wet_mask * [in_b is not NaN]; the output is NaN exactly where the input is;      */
+                              /* +-inf is data; an entry without NaN gives the values of an unflagged call.  The entry's face coefficients */
+                              /* and land bytes are folded on the device from the plan's own planes (csrc/gcmf_gap_fold.hpp: cE, cN times  */
+                              /* a 0 / 1 factor per face -- bit for bit the planes a plan built from wet_mask * [not NaN] holds) into the   */
+                              /* plan's work buffer, 25 bytes per cell and entry (cE, cN, a copy of 1 / area, one land byte); a batch is    */
+                              /* cut into consecutive launches so that this scratch stays at or under option "gap_scratch_mb" (default     */
+                              /* 4096; at least one entry per launch).  The launches are those of a stacked plan (gcmf_plan_create_levels) */
+                              /* whose levels are the entries: the backward evaluation's plain strips and k_land_fix, never the on-chip    */
+                              /* kernel, the zipped strips or the wet-row tables; the result has the bits of such a plan built from the    */
+                              /* explicit masks.  The plan's own planes are never written: flagged and unflagged calls may alternate.      */
+                              /* GCMF_ERR_UNSUPPORTED, with a message that names the flag and the three grid types, for: any other grid     */
+                              /* type, f32 plans, row slabs, stacked plans, gcmf_laplacian, the gcmf_cheb_* and gcmf_slab_* building blocks */
+                              /* and gcmf_land_fix, the flag combined with GCMF_FORWARD_RECURRENCE or GCMF_MASK_FROM_NAN, and a polynomial  */
+                              /* or grid for which the stacked strips offer no backward cut (fewer than five steps, nx not a multiple of 4, */
+                              /* GCMF_CLENSHAW=0 ...).  The lock-free queries are not to be raced with a flagged call, as above.            */
 
 /* Chebyshev step modes for gcmf_cheb_step */
 #define GCMF_STEP_FIRST 0x1u /* T1 = A(T0);            fbar  = p0*T0 + p1*T1                  */
@@ -464,7 +481,9 @@ int gcmf_set_tuning(gcmf_plan *plan, int rows_per_wave, int xcd_remap, int multi
  * widened by S + 1 rows, windows from column 0); 0 = never; same values -- the sign of an
  * exact zero next to land may differ; the FIRST eligible gcmf_apply of a plan builds the tables: it copies the plan's land bytes
  * (one byte per cell) to the host, synchronises the caller's stream and uploads the tables with a blocking copy -- once per plan and
- * launch depth, but not asynchronous and not legal inside a stream capture: capture after one warm-up call, or set 0).  Unknown names: GCMF_ERR_INVALID_ARG. */
+ * launch depth, but not asynchronous and not legal inside a stream capture: capture after one warm-up call, or set 0),
+ * "gap_scratch_mb" N (GCMF_FACES_FROM_NAN: the most scratch, in MiB, the per-entry planes of one launch may take; default 4096; a batch
+ * whose planes need more is cut into consecutive launches of at least one entry; same bits).  Unknown names: GCMF_ERR_INVALID_ARG. */
 int gcmf_set_option(gcmf_plan *plan, const char *name, int value);
 
 /* Last error text of the calling thread (never NULL). */
