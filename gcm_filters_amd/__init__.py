@@ -6,7 +6,7 @@ behind the C ABI of ``include/gcmf.h`` -- there is no CPU fallback.
 """
 __version__ = "0.1.0"
 
-from .filter import Filter, FilterShape
+from .filter import Filter, FilterBank, FilterShape
 from .kernels import GridType, required_grid_vars
 
-__all__ = ["Filter", "FilterShape", "GridType", "required_grid_vars"]
+__all__ = ["Filter", "FilterBank", "FilterShape", "GridType", "required_grid_vars"]

@@ -39,6 +39,8 @@ EXPORTS = [
 ]
 # the entry points of stacked plans (include/gcmf.h: gcmf_plan_create_levels), a list of their own; load() binds both lists
 EXPORTS_LEVELS = ["gcmf_plan_create_levels", "gcmf_plan_levels"]
+# ... and of filter banks (gcmf_apply_bank): likewise
+EXPORTS_BANK = ["gcmf_apply_bank", "gcmf_bank_cut"]
 PATH_NAMES = {0: None, 1: "resident", 2: "strips", 3: "resident-lock-busy", 4: "resident-disabled"}
 RESIDENT_STATES = {0: "ok", 1: "lock-busy", 2: "disabled", 3: "off"}
 PLAN_SELF_RING, PLAN_SKIP_KAPPA_ONE = 0x1, 0x2
@@ -116,6 +118,10 @@ def load() -> C.CDLL:
         lib.gcmf_plan_rows.restype = C.c_int
         lib.gcmf_apply.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_double, vpp, vpp, C.c_int64, C.c_uint32, vp]
         lib.gcmf_apply.restype = C.c_int
+        lib.gcmf_apply_bank.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double, vp, vp, C.c_int64, C.c_uint32, vp]
+        lib.gcmf_apply_bank.restype = C.c_int
+        lib.gcmf_bank_cut.argtypes = [vp, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int]
+        lib.gcmf_bank_cut.restype = C.c_int
         lib.gcmf_laplacian.argtypes = [vp, vpp, vpp, C.c_int64, C.c_uint32, vp]
         lib.gcmf_laplacian.restype = C.c_int
         lib.gcmf_cheb_step.argtypes = [vp, vpp, vpp, vpp, vpp, vpp, C.c_double, C.c_double, C.c_double, C.c_uint32,
@@ -360,6 +366,26 @@ class Plan:
         check(load().gcmf_apply(self._h, p.ctypes.data_as(C.POINTER(C.c_double)), len(p) - 1, float(c),
                                 _ptr_array(ins), _ptr_array(outs), int(nbatch), flags, C.c_void_p(stream or None)))
 
+    def apply_bank(self, p: np.ndarray, c: float, src: int, out: int, nfield: int, *, device_ptrs: bool = True, stream: int = 0,
+                   flags: int = 0):
+        """A filter bank (gcmf_apply_bank): the rows of `p`, (nbank, n_steps + 1), are polynomials of one degree; out[j, i] = row j
+        applied to field i of `src` -- (nfield, ny, nx) and (nbank, nfield, ny, nx) float64 device pointers that do not overlap.
+        Ordinary whole-grid float64 IRREGULAR_WITH_LAND / MOM5U / MOM5T plans with a backward cut (bank_cut); anything else raises
+        GcmfError(ERR_UNSUPPORTED).  flags: further GCMF_* bits (the library refuses all but GCMF_NO_RESIDENT)."""
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        if p.ndim != 2:
+            raise ValueError(f"apply_bank: p must be (nbank, n_steps + 1), not {p.shape}")
+        check(load().gcmf_apply_bank(self._h, p.ctypes.data_as(C.POINTER(C.c_double)), p.shape[0], p.shape[1] - 1, float(c),
+                                     C.c_void_p(src or None), C.c_void_p(out or None), int(nfield),
+                                     (DEVICE_PTRS if device_ptrs else 0) | int(flags), C.c_void_p(stream or None)))
+
+    def bank_cut(self, n_steps: int, nentries: int = 1):
+        """Launch depths gcmf_apply_bank uses for polynomials of n_steps steps and nbank * nfield = nentries entries ([] = no bank on
+        offer for this plan / polynomial)."""
+        buf = (C.c_int * 1024)()
+        n = load().gcmf_bank_cut(self._h, int(n_steps), int(nentries), buf, 1024)
+        return [buf[i] for i in range(n)]
+
     def laplacian(self, ins: Sequence[int], outs: Sequence[int], nbatch: int, *, device_ptrs: bool, stream: int = 0):
         flags = DEVICE_PTRS if device_ptrs else 0
         check(load().gcmf_laplacian(self._h, _ptr_array(ins), _ptr_array(outs), int(nbatch), flags,
@@ -503,7 +529,7 @@ class Plan:
     def last_kernel_geometry(self) -> dict:
         """Launch geometry of the kernel last_kernel() named: {"H", "nstrips", "nwx", "xcd", "grid", "rows"} ({} if none)
         (+ "units": a wet-row table's pairs, and behind it "xoff": the first column of the window grid of the tight cut, option "wet_rows" 3 / 4;
-        "levels": a stacked plan's)."""
+        "levels": a stacked plan's; "bank": the polynomials of a filter bank)."""
         buf = C.create_string_buffer(256)
         check(load().gcmf_last_kernel_geometry(self._h, buf, 256))
         out = {}

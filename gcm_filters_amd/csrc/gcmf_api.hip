@@ -101,6 +101,7 @@ static int launch_ringc(gcmf_plan *pl, const MultiArgs &m, const RingcCut &cut, 
     case K_REG: return launch_ringc_reg(pl, m, cut, s);
     case K_MASK: return launch_ringc_maskz(pl, m, cut, s);
     case K_FLUX:
+      if (pl->bank_n > 0) return launch_ringc_bank(pl, m, cut, s);   // (gcmf_apply_bank: always the plain strips, ringc_cut)
       if (pl->stacked) return launch_ringc_levels(pl, m, cut, s);   // (always the plain strips: ringc_cut)
       if (cut.xe) return launch_ringc_flux_slab(pl, m, cut, s);   // (k_ringcs, or k_ringcp's early-exit form)
       if (m.S == 9) return launch_ringc_flux9(pl, m, cut, s);
@@ -303,6 +304,8 @@ void gcmf_plan_destroy(gcmf_plan *pl) {
   }
   if (pl->stage) (void)hipFree(pl->stage);
   if (pl->dev_p) (void)hipFree(pl->dev_p);
+  if (pl->bank_rev) (void)hipFree(pl->bank_rev);
+  if (pl->bank_fwd) (void)hipFree(pl->bank_fwd);
   resident_free(pl);
   if (pl->stream) (void)hipStreamDestroy(pl->stream);
   delete pl;
@@ -614,7 +617,7 @@ static int sched_backward_scalar(ApplyCtx &x, const int *depths, int n_clen, boo
     gcmf_plan *pl;
     ~WetNow() { pl->wet_now = false; }
   } wet_guard{pl};
-  pl->wet_now = pl->wet_rows > 0 && x.nbatch == 1 && !pl->mask_per_field && !pl->stacked && pl->full && !pl->g.fold && pl->kind == K_FLUX &&
+  pl->wet_now = pl->wet_rows > 0 && x.nbatch == 1 && !pl->mask_per_field && !pl->stacked && !pl->bank_n && pl->full && !pl->g.fold && pl->kind == K_FLUX &&
                 pl->d.dtype == GCMF_F64 && pl->n_land > 0 && pl->pool_bytes > 0;
   pl->pool_clean = pl->wet_now && was_clean;
   for (int q = 0, lvl = 1; q < n_clen; lvl += depths[q++]) {
@@ -827,7 +830,7 @@ static int run_schedule(ApplyCtx &x, uint32_t flags, bool use_multi, bool use_vm
     return GCMF_ERR_UNSUPPORTED;
   }
   // (the on-chip kernel reads the plan's own mask, and one level's planes)
-  if (n_clen > 0 && x.nbatch == 1 && !(flags & GCMF_NO_RESIDENT) && !pl->mask_per_field && !pl->stacked) {
+  if (n_clen > 0 && x.nbatch == 1 && !(flags & GCMF_NO_RESIDENT) && !pl->mask_per_field && !pl->stacked && !pl->bank_n) {
     int why = GCMF_RESIDENT_OFF;
     resident = resident_supported(pl, 0, x.rows, std::min(x.n_steps, 64), x.n_steps, &why);   // (small whole grids; GCMF_RESIDENT=1: whatever fits)
     if (!resident && why == GCMF_RESIDENT_LOCK_BUSY) path = GCMF_PATH_STRIPS_LOCK_BUSY;
@@ -840,10 +843,11 @@ static int run_schedule(ApplyCtx &x, uint32_t flags, bool use_multi, bool use_vm
     int rc = GCMF_OK;
     if (resident)
       rc = sched_resident(x);
-    else if ((flags & GCMF_NO_RESIDENT) || pl->mask_per_field || pl->stacked || ringc_one_depth(pl, x.n_steps, x.nbatch) <= 0 || !sched_single_launch(x))
+    else if ((flags & GCMF_NO_RESIDENT) || pl->mask_per_field || pl->stacked || pl->bank_n || ringc_one_depth(pl, x.n_steps, x.nbatch) <= 0 || !sched_single_launch(x))
       rc = sched_backward_scalar(x, depths, n_clen, was_clean);
     if (rc || pl->n_land == 0) return rc;
     // the isolated cells' own polynomial (forward recurrence, as the reference computes it)
+    if (pl->bank_n > 0) return launch_land_fix_bank(pl, x.din[0], x.dout[0], x.n_steps, x.c, x.nbatch, x.s);   // (every entry its own)
     return land_fix_tail(pl, x.p, x.n_steps, x.c, x.din[0], x.dout[0], x.fb32, x.nbatch, x.s);
   }
   if (use_multi) return sched_forward_scalar(x);
@@ -1209,6 +1213,105 @@ static int run_whole(gcmf_plan *pl, const double *p, int n_steps, double c, cons
 int gcmf_apply(gcmf_plan *pl, const double *p, int n_steps, double c, const void *const *in, void *const *out,
                int64_t nbatch, uint32_t flags, void *stream) {
   return run_whole(pl, p, n_steps, c, in, out, nbatch, flags, stream, false);
+}
+
+// The two coefficient tables of a filter bank on the device (gcmf_plan::bank_rev / bank_fwd), uploaded only when they changed -- as
+// ensure_dev_p: the previous call's kernels may still be reading the old ones, so the stream is drained first (and the device, when
+// that call ran on another stream)
+static int ensure_bank_tables(gcmf_plan *pl, const double *p, int nbank, int n_steps, hipStream_t s) {
+  const size_t stride = (size_t)n_steps + 1, n = (size_t)nbank * stride;
+  if (pl->bank_cap < n) {
+    if (pl->bank_rev) GCMF_HIP(hipFree(pl->bank_rev));
+    pl->bank_rev = nullptr;
+    if (pl->bank_fwd) GCMF_HIP(hipFree(pl->bank_fwd));
+    pl->bank_fwd = nullptr;
+    pl->bank_cap = 0;
+    pl->bank_host.clear();
+    GCMF_HIP(hipMalloc((void **)&pl->bank_rev, n * sizeof(double)));
+    GCMF_HIP(hipMalloc((void **)&pl->bank_fwd, n * sizeof(double)));
+    pl->bank_cap = n;
+  }
+  if (pl->bank_stride != stride || pl->bank_host.size() != n || memcmp(pl->bank_host.data(), p, n * sizeof(double)) != 0) {
+    pl->bank_host.assign(p, p + n);
+    pl->bank_stride = stride;
+    std::vector<double> rev(n);
+    for (int j = 0; j < nbank; ++j)
+      for (size_t q = 0; q < stride; ++q) rev[j * stride + q] = p[j * stride + (stride - 1 - q)];
+    GCMF_HIP(hipStreamSynchronize(s));  // nothing may still read the old coefficients
+    if (pl->busy_valid && pl->busy_stream != s) GCMF_HIP(hipDeviceSynchronize());
+    GCMF_HIP(hipMemcpy(pl->bank_fwd, pl->bank_host.data(), n * sizeof(double), hipMemcpyHostToDevice));
+    GCMF_HIP(hipMemcpy(pl->bank_rev, rev.data(), n * sizeof(double), hipMemcpyHostToDevice));
+  }
+  return GCMF_OK;
+}
+
+int gcmf_apply_bank(gcmf_plan *pl, const double *p, int nbank, int n_steps, double c, const void *in, void *out, int64_t nfield,
+                    uint32_t flags, void *stream) {
+  if (!pl || !p || !in || !out) {
+    set_error("gcmf_apply_bank: null argument");
+    return GCMF_ERR_INVALID_ARG;
+  }
+  if (nbank < 1 || n_steps < 1 || nfield < 0) {
+    set_error("gcmf_apply_bank: %d polynomials of %d steps on %lld fields (at least one polynomial of at least one step)", nbank, n_steps, (long long)nfield);
+    return GCMF_ERR_INVALID_ARG;
+  }
+  const int gt = pl->d.grid_type;
+  const bool kind_ok = gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T;
+  const char *why = !kind_ok ? "another grid type" : pl->d.dtype != GCMF_F64 ? "an f32 plan" : (pl->d.flags & GCMF_PLAN_SELF_RING) ? "GCMF_PLAN_SELF_RING" :
+                    !pl->full ? "a row slab" : pl->stacked ? "a stacked plan (gcmf_plan_create_levels)" : !(flags & GCMF_DEVICE_PTRS) ? "host pointers (GCMF_DEVICE_PTRS is required)" :
+                    (flags & GCMF_FORWARD_RECURRENCE) ? "GCMF_FORWARD_RECURRENCE" : (flags & GCMF_MASK_FROM_NAN) ? "GCMF_MASK_FROM_NAN" :
+                    (flags & GCMF_FACES_FROM_NAN) ? "GCMF_FACES_FROM_NAN" : (flags & GCMF_OUT_F32) ? "GCMF_OUT_F32" : nullptr;
+  if (why) {
+    set_error("gcmf_apply_bank: filter banks run on ordinary whole-grid f64 plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T with device pointers, "
+              "backwards, on the plan's own mask and into f64 (%s; grid type %d): call gcmf_apply once per polynomial", why, gt);
+    return GCMF_ERR_UNSUPPORTED;
+  }
+  const size_t cell = (size_t)pl->d.ny * pl->d.nx;
+  if ((int64_t)nbank * nfield > (int64_t)2000000000) {
+    set_error("gcmf_apply_bank: %d polynomials x %lld fields: at most 2e9 entries per call", nbank, (long long)nfield);
+    return GCMF_ERR_INVALID_ARG;
+  }
+  const int64_t nent = (int64_t)nbank * nfield;
+  {
+    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (size_t)nfield * cell * 8, o0 = (uintptr_t)out, o1 = o0 + (size_t)nent * cell * 8;
+    if ((nfield > 0 && i0 < o1 && o0 < i1) || in == out) {   // every launch and k_land_fix read the input
+      set_error("gcmf_apply_bank: `out` must not overlap `in` (filtering in place is not supported)");
+      return GCMF_ERR_INVALID_ARG;
+    }
+  }
+  int depths[1024];
+  if (bank_cut(pl, n_steps, std::max<int64_t>(1, nent), depths, 1024) <= 0) {
+    set_error("gcmf_apply_bank: for this plan and a polynomial of %d steps the plain strips offer no backward cut (gcmf_bank_cut returns 0: fewer "
+              "than five steps, nx = %lld not a multiple of 4 on a grid with land, GCMF_CLENSHAW=0 ...): call gcmf_apply once per polynomial",
+              n_steps, (long long)pl->d.nx);
+    return GCMF_ERR_UNSUPPORTED;
+  }
+  if (nfield == 0) return GCMF_OK;
+  std::lock_guard<std::mutex> lk(pl->mu);
+  GCMF_HIP(hipSetDevice(pl->d.device));
+  int rc = ensure_bank_tables(pl, p, nbank, n_steps, (hipStream_t)stream);
+  if (rc) return rc;
+  struct Bank {   // (put back however the call leaves)
+    gcmf_plan *pl;
+    ~Bank() { pl->bank_n = 0; pl->bank_nfield = 1; pl->entry0 = 0; }
+  } guard{pl};
+  pl->bank_n = nbank;
+  pl->bank_nfield = nfield;
+  float ms_total = 0.f;
+  int launches = 0;
+  for (int64_t e0 = 0; e0 < nent; e0 += MAX_LAUNCH_BATCH) {   // (consecutive launches: an entry keeps its place through entry0)
+    const int64_t nb = std::min<int64_t>(nent - e0, MAX_LAUNCH_BATCH);
+    const void *in1[2] = {in, nullptr};
+    void *out1[2] = {(char *)out + (size_t)e0 * cell * 8, nullptr};
+    pl->entry0 = e0;
+    // (p: the schedule reads the polynomial's degree only -- the launches and k_land_fix take the coefficients from the tables)
+    if ((rc = run_whole_locked(pl, p, n_steps, c, in1, out1, nb, (flags & GCMF_DEVICE_PTRS) | GCMF_NO_RESIDENT, stream, false, true))) return rc;
+    ms_total += pl->last_ms;
+    launches += pl->last_launches;
+  }
+  pl->last_ms = ms_total;
+  pl->last_launches = launches;
+  return GCMF_OK;
 }
 
 int gcmf_laplacian(gcmf_plan *pl, const void *const *in, void *const *out, int64_t nbatch, uint32_t flags,

@@ -75,7 +75,24 @@ const char *clenshaw_depth_refused(const gcmf_plan *pl, int S, bool first, int64
 // launches run at memcpy rate and gain the plane they no longer move (config 3: +10 %); 2: every scalar kind (the land-mask
 // kernel is bound by its instruction stream and gains nothing: 93 -> 92-95 us per launch).  Needs the isolated cells fixed up
 // by k_land_fix when there is land (land_ok).
+static int clenshaw_cut_for(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, bool f32_asked, int64_t nbatch, bool plain_only);
 int clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, bool f32_asked, int64_t nbatch) {
+  return clenshaw_cut_for(pl, n_steps, depths, max_depths, f32_asked, nbatch, pl && (pl->stacked || pl->bank_n > 0));
+}
+
+// A filter bank (gcmf_apply_bank): the cut of the plain strips -- what a stacked plan of the same grid gets
+bool bank_plan_ok(const gcmf_plan *pl) {
+  const int gt = pl ? pl->d.grid_type : -1;
+  return pl && (gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T) && pl->kind == K_FLUX && pl->d.dtype == GCMF_F64 && pl->full &&
+         !pl->stacked && !pl->g.fold && !pl->mask_per_field;
+}
+int bank_cut(const gcmf_plan *pl, int n_steps, int64_t nentries, int *depths, int max_depths) {
+  if (!bank_plan_ok(pl) || !depths || max_depths < 1 || nentries < 1 || n_steps < 1) return 0;
+  return clenshaw_cut_for(pl, n_steps, depths, max_depths, false, nentries, true);
+}
+
+// plain_only: the launches are the plain strips whatever the batch (stacked plans, filter banks)
+static int clenshaw_cut_for(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, bool f32_asked, int64_t nbatch, bool plain_only) {
   if (!pl || pl->ncomp != 1 || !(pl->clenshaw >= 2 || (pl->clenshaw == 1 && pl->kind == K_FLUX))) return 0;
   // f32 state (round 5): only when asked for (plan option clenshaw_f32 / GCMF_BACKWARD_F32 per call).  Summed backwards in f32 the
   // polynomial is 15-45 x further from f64 arithmetic than the reference's own f32 path (f32 T_k, f64 running sum; measured:
@@ -92,7 +109,7 @@ int clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, 
   const bool nines_full = ringc9_ok(pl) || ringc9_fold_ok(pl, nbatch, 0, pl->g.rows), nines = nines_full || ringc9_slab_ok(pl);
   if (!(n_steps >= 10 || (n_steps >= 5 && n_steps <= 8) || (n_steps == 9 && nines))) return 0;
   int smax = pl->ringc_smax;
-  if (!smax && nbatch == 1 && !pl->stacked && nines_full && pl->ringc_zip && (long long)pl->g.rows * pl->g.nx <= 2500000LL && n_steps >= 10) {
+  if (!smax && nbatch == 1 && !plain_only && nines_full && pl->ringc_zip && (long long)pl->g.rows * pl->g.nx <= 2500000LL && n_steps >= 10) {
     // Whole grids that live in the caches and run k_ringcz (1/4-degree grids): a launch is paced by the rows its strips march, not by the
     // bytes it moves, so fewer launches are not always faster -- a strip marches H + S + 1 rows whose cost grows with S, and fewer
     // levels mean narrower ghost columns (sometimes a window less).  Measured (experiments/scripts/zip_ab.py, us per launch):
@@ -211,6 +228,10 @@ int gcmf_clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_dep
 int gcmf_clenshaw_cut_batch(const gcmf_plan *pl, int n_steps, int64_t nbatch, int *depths, int max_depths) {
   if (!pl || !depths || max_depths < 1 || nbatch < 1) return 0;
   return clenshaw_cut(pl, n_steps, depths, max_depths, false, nbatch);
+}
+
+int gcmf_bank_cut(const gcmf_plan *pl, int n_steps, int64_t nentries, int *depths, int max_depths) {
+  return bank_cut(pl, n_steps, nentries, depths, max_depths);
 }
 
 int gcmf_cheb_multi(gcmf_plan *pl, const void *u, const void *v, void *uo, void *vo, const void *fbar_in,

@@ -18,6 +18,8 @@ int dom_collect(gcmf_plan *pl);
 bool land_ok(const gcmf_plan *pl, int n_steps);
 bool ringc9_ok(const gcmf_plan *pl);
 int clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, bool f32_asked = false, int64_t nbatch = 1);   // (nbatch: a lone field on a cache-resident grid may be cut into shallower launches)
+bool bank_plan_ok(const gcmf_plan *pl);   // an ordinary whole-grid f64 plan of the flux kinds without a seam: what gcmf_apply_bank runs on
+int bank_cut(const gcmf_plan *pl, int n_steps, int64_t nentries, int *depths, int max_depths);   // gcmf_bank_cut
 bool ptr_al16(const void *p);
 int vec_backward_next_depth(const gcmf_plan *pl, int64_t nbatch, int left, int smax);
 
@@ -42,7 +44,7 @@ inline MultiArgs backward_args(const double *p, int n_steps, double c, int lvl, 
   MultiArgs m{};
   m.u0 = u; m.v0 = v; m.uo = fr[0]; m.vo = fr[1];
   m.fb_in = f; m.fb_out = out;
-  m.first = (lvl == 1); m.last = (lvl + S - 1 == n_steps); m.S = S;
+  m.first = (lvl == 1); m.last = (lvl + S - 1 == n_steps); m.S = S; m.lvl = lvl;
   if (!pk) pk = m.pk;
   for (int t = 0; t < S; ++t) pk[t] = p[n_steps - (lvl + t)];
   m.p0 = p[n_steps]; m.c = c;

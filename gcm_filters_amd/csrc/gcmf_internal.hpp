@@ -76,6 +76,8 @@ struct MultiArgs {
   int land_zero;  // the caller guarantees that isolated (land) cells of u0 and v0 are zero: GCMF_STEP_LAND_ZERO
   int ring_first; // first launch: the caller will overwrite the result of the isolated (land) cells (k_land_fix) or there are
                   // none, so the launch may take them as zero while it loads the field (k_ring<..., FIRST>)
+  int lvl;        // backward evaluation (backward_args): the launch's first level, 1-based (0: not told) -- what a filter bank's launch
+                  // finds its coefficients by (ringc_march<..., PB>)
 };
 
 // Arguments of one S-step vector launch (gcmf_cgrid_stream2.hip / gcmf_bgrid_stream2.hip): T_{k-1}, T_{k-2} -> T_{k+S-2}, T_{k+S-1}.
@@ -241,6 +243,17 @@ struct gcmf_plan {
   double *dev_p = nullptr;   // p[0..n_steps] of the last filter, for k_land_fix
   size_t dev_p_n = 0;
   std::vector<double> host_p;
+  // A FILTER BANK (gcmf_apply_bank; ordinary whole-grid f64 plans of the flux kinds without a seam): for the duration of such a call (the plan's mutex
+  // is held) bank_n polynomials of one degree are applied to bank_nfield fields -- entry e of the call is polynomial e / bank_nfield on
+  // field e % bank_nfield, entry0 the first entry of the launch that runs now -- by the plain strips of the backward evaluation alone
+  // (ringc_march<..., PB>, k_land_fix<..., PB>), which read the polynomials from two grow-only tables of bank_stride doubles per row: bank_rev
+  // reversed (MultiP::ptab) and bank_fwd as given; bank_host is what both hold (bank_fwd's order).  The lock-free queries may see the
+  // call's values, as with mask_per_field.
+  int bank_n = 0;
+  int64_t bank_nfield = 1;
+  double *bank_rev = nullptr, *bank_fwd = nullptr;
+  size_t bank_cap = 0, bank_stride = 0;   // doubles each table holds; doubles per row
+  std::vector<double> bank_host;
   std::mutex mu;
 };
 
@@ -275,13 +288,14 @@ int launch_ring_flux_f32(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);   //
 // (gcmf_ringc_cut.hpp), which the launchers apply: advance_multi asks once and picks the launcher by cut.form
 inline RingcCutIn ringc_cut_in(const gcmf_plan *pl, int rows, bool seam, int64_t nbatch, int S, bool band_beside) {
   return RingcCutIn{pl->g.nx, rows, seam, (long long)nbatch, S, pl->d.dtype == GCMF_F64, pl->kind, band_beside, pl->mask_per_field != 0,
-                    pl->strip_rows, pl->ringc_xe_rows, pl->ringc_zip, pl->zip_fold, pl->pack_batch, pl->stacked};
+                    pl->strip_rows, pl->ringc_xe_rows, pl->ringc_zip, pl->zip_fold, pl->pack_batch, pl->stacked || pl->bank_n > 0};
 }
 int launch_ringc_reg(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
 int launch_ringc_maskz(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
 int launch_ringc_flux(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
 int launch_ringc_flux9(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // nine levels: whole f64 flux grids without a seam (gcmf_ringc_flux9.hip)
 int launch_ringc_levels(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // a stacked plan's plain strips (gcmf_ringc_levels.hip)
+int launch_ringc_bank(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // a filter bank's plain strips (gcmf_ringc_bank.hip)
 int launch_ringc_flux_slab(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // no seam's band beside, short strips: early exits (k_ringcs)
 int launch_ringc_flux_slab_f32(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
 int launch_ringc_zip(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // f64 flux plans: pairs of strips zipped at a shared seam, fold strips at the tripole seam (k_ringcz, gcmf_ringc_zip.hip)
@@ -339,6 +353,9 @@ int launch_prepare(gcmf_plan *pl, const void *const *in, void *const *out, int64
 int launch_zero_land(gcmf_plan *pl, void *a, void *b, int64_t nbatch, hipStream_t s, int row_lo = 0, int row_hi = 0);
 int launch_land_fix(gcmf_plan *pl, const void *in, void *out, const double *dp, int n_steps, double c, int fb_is_f32,
                     int64_t nbatch, hipStream_t s);
+// ... of a filter bank (gcmf_apply_bank): entry e of the launch's nbatch, counted from pl->entry0, is row e / bank_nfield of pl->bank_fwd
+// on field e % bank_nfield of `in`
+int launch_land_fix_bank(gcmf_plan *pl, const void *in, void *out, int n_steps, double c, int64_t nbatch, hipStream_t s);
 // plan-time precompute (gcmf_precompute.hip): fills pl->g from the raw global planes (device pointers)
 int precompute(gcmf_plan *pl, const void *const *dplanes, const void *const *hplanes_or_null);
 // ... of a stacked plan (f64 flux kinds without a seam, whole grid): plane k holds plane_levels[k] (1 or pl->nlev) planes

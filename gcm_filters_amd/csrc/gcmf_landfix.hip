@@ -12,11 +12,20 @@ namespace gcmf {
 // LV: a stacked plan (gcmf_plan_create_levels) -- lbits holds nlev planes, one per level, and entry b reads plane (lev0 + b) % nlev;
 // per_field = nlev | lev0 << 16 (nlev <= 32768).  An instantiation of its own: as a runtime branch in the one kernel (with its second
 // 64-bit division) BASELINE config 3 measured 0.7 % slower, 0.747 against 0.741 ms per application, three alternating runs each
-template <typename T, typename FB, bool FUSED, bool LV = false>
+// PB: a filter bank (gcmf_apply_bank) -- blockIdx.y is the launch's entry, entry e = ent0 + blockIdx.y is row e / nfield of the table p
+// (n_steps + 1 doubles per row) on field e % nfield of `in`, its result the launch's plane blockIdx.y of `out`; per_field = nfield,
+// ntotal = ncell (a workgroup stays inside one entry: one polynomial in its LDS), lbits the plan's one plane.  An instantiation of its own.
+template <typename T, typename FB, bool FUSED, bool LV = false, bool PB = false>
 __global__ __launch_bounds__(256) void k_land_fix(const T *in, FB *out, const uint8_t *lbits, const T *area,
                                                   const double *p, int n_steps, double c_, long long ncell,
-                                                  long long ntotal, int per_field) {
+                                                  long long ntotal, int per_field, int ent0) {
   extern __shared__ double sp[];  // p[0..n_steps], read by every step of every cell
+  if constexpr (PB) {
+    const int e = ent0 + (int)blockIdx.y, pol = e / per_field;
+    p += (long long)pol * (n_steps + 1);
+    in += (long long)(e - pol * per_field) * ncell;
+    out += (long long)blockIdx.y * ncell;
+  }
   for (int k = threadIdx.x; k <= n_steps; k += blockDim.x) sp[k] = p[k];
   __syncthreads();
   const T c = (T)c_;
@@ -26,6 +35,7 @@ __global__ __launch_bounds__(256) void k_land_fix(const T *in, FB *out, const ui
     const long long cell = q4 % ncell;
     unsigned m;
     if constexpr (LV) m = *reinterpret_cast<const unsigned *>(lbits + (((per_field >> 16) + q4 / ncell) % (per_field & 0xFFFF)) * ncell + cell);
+    else if constexpr (PB) m = *reinterpret_cast<const unsigned *>(lbits + q4);
     else m = *reinterpret_cast<const unsigned *>(lbits + (per_field ? q4 : cell));   // (per_field: every entry its own plane of bytes)
     if ((m & 0x01010101u) == 0x01010101u) continue;
     T xm2[4], xm1[4];
@@ -126,7 +136,7 @@ static int launch_lf(gcmf_plan *pl, const void *in, void *out, const double *dp,
     if (pl->stacked) {   // (f64 flux kinds; one level: the plan's one plane, the ordinary kernel)
       if (pl->nlev >= 2) {
         hipLaunchKernelGGL((k_land_fix<T, FB, true, true>), grid, block, lds, s, (const T *)in, (FB *)out, pl->lbits, area, dp, n_steps, c, ncell,
-                           ntotal, (int)pl->nlev | ((int)(pl->entry0 % pl->nlev) << 16));
+                           ntotal, (int)pl->nlev | ((int)(pl->entry0 % pl->nlev) << 16), 0);
         GCMF_HIP(hipGetLastError());
         return GCMF_OK;
       }
@@ -134,10 +144,27 @@ static int launch_lf(gcmf_plan *pl, const void *in, void *out, const double *dp,
   }
   if (pl->kind == K_FLUX)
     hipLaunchKernelGGL((k_land_fix<T, FB, true>), grid, block, lds, s, (const T *)in, (FB *)out, pl->lbits, area, dp, n_steps, c,
-                       ncell, ntotal, pl->mask_per_field);
+                       ncell, ntotal, pl->mask_per_field, 0);
   else
     hipLaunchKernelGGL((k_land_fix<T, FB, false>), grid, block, lds, s, (const T *)in, (FB *)out, pl->lbits, area, dp, n_steps,
-                       c, ncell, ntotal, pl->mask_per_field);
+                       c, ncell, ntotal, pl->mask_per_field, 0);
+  GCMF_HIP(hipGetLastError());
+  return GCMF_OK;
+}
+
+int launch_land_fix_bank(gcmf_plan *pl, const void *in, void *out, int n_steps, double c, int64_t nbatch, hipStream_t s) {
+  if (pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || pl->stacked || pl->area_weighted || pl->bank_n < 1 || !pl->bank_fwd ||
+      pl->bank_stride != (size_t)n_steps + 1 || nbatch < 1 || nbatch > 65535 || (pl->d.nx % 4) != 0) {
+    set_error("k_land_fix (filter bank): not an ordinary f64 flux plan inside gcmf_apply_bank");
+    return GCMF_ERR_INVALID_ARG;
+  }
+  const long long ncell = (long long)pl->rows_alloc * pl->d.nx;
+  long long nb = (ncell / 4 + 255) / 256;
+  if (nb > 32768) nb = 32768;
+  dim3 block(256), grid((unsigned)nb, (unsigned)nbatch);
+  const size_t lds = ((size_t)n_steps + 1) * sizeof(double);
+  hipLaunchKernelGGL((k_land_fix<double, double, true, false, true>), grid, block, lds, s, (const double *)in, (double *)out, pl->lbits, (const double *)nullptr,
+                     pl->bank_fwd, n_steps, c, ncell, ncell, (int)pl->bank_nfield, (int)pl->entry0);
   GCMF_HIP(hipGetLastError());
   return GCMF_OK;
 }

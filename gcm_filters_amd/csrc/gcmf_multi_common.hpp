@@ -127,6 +127,13 @@ template <typename T, typename FB> struct MultiP {
   // filtered with the planes of level (lev0 + b) % nlev (k_ringc<..., LV = true> only: no other kernel reads these)
   long long lstride = 0;
   int nlev = 1, lev0 = 0;
+  // a filter bank (gcmf_apply_bank; ringc_march<..., PB> only: no other kernel reads these): entry e = ent0 + blockIdx.y of the launch is
+  // polynomial e / nfield applied to field e % nfield of fb_in.  ptab: the polynomials REVERSED, row j = p_j[n], p_j[n - 1], .. p_j[0],
+  // pstride doubles apart; a launch whose first level is l (1-based) carries poff = l - 1 and finds, at ptab[j * pstride + poff ..],
+  // p_j[n - l + 1] (a first launch's p_n) and then the coefficients of its levels 1 .. S, consecutively
+  const double *ptab = nullptr;
+  int pstride = 0, poff = 0;
+  int nfield = 1, ent0 = 0;
 };
 
 

@@ -63,7 +63,13 @@ template <bool ZIP> constexpr bool ringc_ramp_on(int t, int ph) { return ZIP ? (
 // XO (round 8: k_ringcz's table launches, whose window grid may start at any even column): `wx` is the window's first FOOTPRINT column x0
 // instead of its number, and a lane owns its cells below column khi (the table's limit, nx + the grid's offset) instead of below nx -- a
 // compile-time form of its own again: every other instantiation is the instruction stream it was.
-template <typename T, int KIND, int S, bool FIRST, bool SANI, bool XE = false, bool ZIP = false, bool PF = false, bool LV = false, bool XO = false>
+// PB: a filter bank (gcmf_apply_bank; the f64 flux kinds' plain strips of an ordinary plan) -- batch entry e = P.ent0 + blockIdx.y is polynomial
+// e / P.nfield applied to field e % P.nfield: the constant input comes from that field's plane, the state and result planes stay the entry's
+// own, and the coefficients of the launch's levels come from row e / nfield of a table in device memory (MultiP::ptab) instead of from the
+// kernel arguments -- wave-uniform addresses read once per march through the constant address space (scalar loads into scalar registers,
+// where the kernel arguments' P.pk[] live too).  Like PF, LV and XO an instantiation of its own.
+template <typename T, int KIND, int S, bool FIRST, bool SANI, bool XE = false, bool ZIP = false, bool PF = false, bool LV = false, bool XO = false,
+          bool PB = false>
 __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx, const int a, const int b, const long long boff, const bool odd,
                                             T *zmine = nullptr, const T *zpart = nullptr, const bool fold = false, const int pos_at = 0,
                                             const int klo = -(1 << 30), const int khi = 1 << 30) {
@@ -77,6 +83,7 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
   static_assert(!ZIP || FLUX, "the seam exchange is the flux kinds' (a carried face flux per level)");
   static_assert(!LV || (FLUX && !ZIP && !PF), "stacked plans: the flux kinds' plain strips");
   static_assert(!XO || ZIP, "a window origin per pair: k_ringcz's table launches");
+  static_assert(!PB || (FLUX && sizeof(T) == 8 && !ZIP && !XE && !PF && !LV), "filter banks: the f64 flux kinds' plain strips of an ordinary plan");
   constexpr bool WATCH = (KIND != K_REG) && !SANI;  // K_REG has no nan_to_num in the reference: NaN spreads by plain arithmetic
   constexpr bool FUSED = true;   // nothing here is bit-identical with numpy anyway: every multiply-add pair is one fma
 
@@ -168,6 +175,16 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
     cout_ = !wrap && (cr < 0 || cr >= rows);
   };
   const T *fplane = P.fb_in + boff;  // the constant input f (Clenshaw has no fbar: the pointer slot is reused)
+  T pbk[S + 1];   // PB: p_n (a first launch's) and the coefficients of levels 1 .. S, from the entry's row of the table
+  if constexpr (PB) {   // (wave-uniform: blockIdx.y and kernel arguments only)
+    typedef const __attribute__((address_space(4))) double *ctab_t;   // (nothing writes the table while a launch runs)
+    const int ent = P.ent0 + (int)blockIdx.y;
+    const int pol = ent / P.nfield;
+    fplane = P.fb_in + (long long)(ent - pol * P.nfield) * P.bstride;
+    const ctab_t row = (ctab_t)P.ptab + ((long long)pol * P.pstride + P.poff);
+#pragma unroll
+    for (int t = 0; t <= S; ++t) pbk[t] = (T)row[t];
+  }
   const long long moff = (MASK && PF) ? boff : 0;   // (wave-uniform) the entry's own plane of mask bytes
   const long long loff = LV ? (long long)((P.lev0 + (int)blockIdx.y) % P.nlev) * P.lstride : 0;   // (wave-uniform) the entry's level
   const bool has_land = P.lbits != nullptr;
@@ -285,7 +302,8 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
       T tk;
       if (FUSED) {
         tk = rfma(two, av, -x2);
-        tk = rfma((T)P.pk[t - 1], Ff[sl][k], tk);
+        if constexpr (PB) tk = rfma(pbk[t], Ff[sl][k], tk);
+        else tk = rfma((T)P.pk[t - 1], Ff[sl][k], tk);
       } else {
         tk = two * av - x2;
         tk = tk + (T)P.pk[t - 1] * Ff[sl][k];
@@ -309,7 +327,8 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
     load_u(ic<(ph + D) % RU>{});
     if constexpr (FIRST) {  // the row of f that has just arrived becomes a row of b_n = p_n f (prepared, land out)
       constexpr int su = ph % RU;
-      const T pn = (T)P.p0;
+      T pn = (T)P.p0;
+      if constexpr (PB) pn = pbk[0];
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
         if constexpr (!FLUX) G0[su][k] = weigh ? G0[su][k] * ARu[su][k] : G0[su][k];
@@ -479,17 +498,17 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
 // its run, which crosses at most one field boundary (H <= nrows): up to two (field, row range) segments, each a march of its own with its
 // 2 S warm-up rows.  16 fields x 33 windows of a 300-row slab tile 1024 wave slots at ~70 % as whole strips (a strip cannot cross from one
 // field into the next) and at ~95 % this way.
-template <typename T, int KIND, int S, bool FIRST, bool XE, bool PACK, bool PF = false, bool LV = false>   // (PF, LV: never packed, ringc_cut)
+template <typename T, int KIND, int S, bool FIRST, bool XE, bool PACK, bool PF = false, bool LV = false, bool PB = false>   // (PF, LV, PB: never packed, ringc_cut)
 __device__ __forceinline__ void ringc_walk(const MultiP<T, T> &P, const int wid) {
   const int wx = wid % P.nwx, st = wid / P.nwx;
   if constexpr (!PACK) {   // one strip of one field (the instruction stream of rounds 2-5: the walk below costs the land-mask kernel 5 %)
     const int a = P.out_lo + st * P.H;
     const int b = min(a + P.H, P.out_hi);
     const long long boff = (long long)blockIdx.y * P.bstride;
-    if (ringc_march<T, KIND, S, FIRST, false, XE, false, PF, LV>(P, wx, a, b, boff, (st & 1) != 0)) {
+    if (ringc_march<T, KIND, S, FIRST, false, XE, false, PF, LV, false, PB>(P, wx, a, b, boff, (st & 1) != 0)) {
       if constexpr (KIND != K_REG) {
         if (P.nfb && (threadIdx.x & 63) == 0) atomicAdd(P.nfb, 1u);                      // instrumentation: gcmf_ring_fallbacks
-        ringc_march<T, KIND, S, FIRST, true, XE, false, PF, LV>(P, wx, a, b, boff, (st & 1) != 0);   // the same strip again, operands through nan_to_num
+        ringc_march<T, KIND, S, FIRST, true, XE, false, PF, LV, false, PB>(P, wx, a, b, boff, (st & 1) != 0);   // the same strip again, operands through nan_to_num
       }
     }
     return;
@@ -512,13 +531,17 @@ __device__ __forceinline__ void ringc_walk(const MultiP<T, T> &P, const int wid)
   }
 }
 
+// PF and LV TOGETHER (neither means anything beside the other: a plane of mask bytes per entry is the land-mask kinds', a level axis the flux
+// kinds') name the filter bank's form, ringc_march<PB>: the kernel keeps its six template arguments, and with them the names of all its
+// other instantiations
 template <typename T, int KIND, int S, bool FIRST, bool PF = false, bool LV = false>
 __global__ __launch_bounds__(256, 1) void k_ringc(const MultiP<T, T> P) {
   int bx = blockIdx.x;
   if (P.xcd_per > 0 && bx < 8 * P.xcd_per) bx = (bx & 7) * P.xcd_per + (bx >> 3);
   const int wid = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (wid >= P.nwaves) return;
-  ringc_walk<T, KIND, S, FIRST, false, false, PF, LV>(P, wid);
+  constexpr bool PB = PF && LV;
+  ringc_walk<T, KIND, S, FIRST, false, false, PF && !PB, LV && !PB, PB>(P, wid);
 }
 
 // ... and for packed batches (ringc_walk<PACK>): XE = the early-exit form of the flux kinds (k_ringcs)
@@ -784,6 +807,31 @@ static int launch_ringc_levels_sf(gcmf_plan *pl, const MultiArgs &a, const Ringc
   GCMF_HIP(hipGetLastError());
   note_kernel(pl, std::string("gcmf::k_ringc<double, ") + std::to_string((int)K_FLUX) + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
               launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " levels=" + std::to_string((long long)pl->nlev));
+  return GCMF_OK;
+}
+
+// a filter bank's launch (gcmf_apply_bank): k_ringc<double, K_FLUX, S, FIRST, true, true>; reported under the ordinary kernel's name,
+// as the stacked plans' instantiation is, with " bank=<nbank>" behind the geometry
+template <int S, bool FIRST>
+static int launch_ringc_bank_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+  if (cut.form != RINGC_PLAIN || cut.xe || pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || pl->stacked || pl->bank_n < 1 || !pl->bank_rev ||
+      a.lvl < 1 || (size_t)(a.lvl - 1 + S) >= pl->bank_stride) {
+    set_error("k_ringc (filter bank): the cut is not the plain strips of an ordinary f64 flux plan inside gcmf_apply_bank");
+    return GCMF_ERR_INVALID_ARG;
+  }
+  MultiP<double, double> P;
+  ringc_params(P, pl, a, cut);
+  P.ptab = pl->bank_rev;
+  P.pstride = (int)pl->bank_stride;
+  P.poff = a.lvl - 1;
+  P.nfield = (int)pl->bank_nfield;
+  P.ent0 = (int)pl->entry0;
+  const int nrows = a.row_hi - a.row_lo;
+  dim3 block(256), grid(cut.grid_x, cut.grid_y);
+  hipLaunchKernelGGL((k_ringc<double, K_FLUX, S, FIRST, true, true>), grid, block, 0, s, P);
+  GCMF_HIP(hipGetLastError());
+  note_kernel(pl, std::string("gcmf::k_ringc<double, ") + std::to_string((int)K_FLUX) + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
+              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " bank=" + std::to_string(pl->bank_n));
   return GCMF_OK;
 }
 

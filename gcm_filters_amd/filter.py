@@ -10,6 +10,8 @@ from __future__ import annotations
 import enum
 import warnings
 from dataclasses import dataclass, field
+import os
+import types
 from typing import Any, Iterable, NamedTuple, Optional
 
 import numpy as np
@@ -517,3 +519,190 @@ class Filter:
             return filter_func_vec(ufield, vfield, *self._grid_args(as_xarray=False))
         u_filtered, v_filtered = self._through_apply_ufunc(filter_func_vec, [ufield, vfield], dims)
         return (u_filtered, v_filtered)
+
+
+def _bank_by_default(nbank: int, ny: int, nx: int) -> bool:
+    """Whether FilterBank takes the one-batch route where the library offers it and GCMF_FILTER_BANK does not say: wherever
+    tools/measure_filter_bank.py measured it at least as fast as the loop over the scales beyond both spreads (README, "Filter banks")."""
+    return True
+
+
+class FilterBank:
+    """One field filtered at many scales: the ``Filter`` objects of a sweep over ``filter_scales`` sharing everything else -- shape,
+    ``dx_min``, grid, and ONE polynomial degree -- applied in one call (not in the reference, whose users loop over ``Filter`` objects).
+
+    ``s_max`` does not depend on the filter scale, so the operator of every scale is the same and only the Chebyshev coefficients
+    differ: on float64 ``IRREGULAR_WITH_LAND`` / ``MOM5U`` / ``MOM5T`` grids the scales run as ONE batch of the backward evaluation with
+    a polynomial per entry (``gcmf_apply_bank``); everything else runs ``filters[j]`` one after the other.  Either way
+    ``bank.apply(f)[j]`` is what ``bank.filters[j].apply(f)`` returns.
+
+    Parameters
+    ----------
+    filter_scales : sequence of float
+        The filter scales, positive and finite (``ValueError`` otherwise, and for an empty sequence)
+    n_steps : int, optional
+        One degree for all scales: the largest of ``Filter``'s default ``n_steps`` over the scales; a caller's ``n_steps >= 3`` is taken
+        instead (with ``Filter``'s warning when it is below that largest default)
+    dx_min, filter_shape, transition_width, ndim, grid_type, grid_vars, evaluation, plan_cache
+        As for ``Filter``, validated as ``Filter`` validates them
+
+    Attributes
+    ----------
+    n_steps : int
+    filters : list of Filter
+        ``Filter(filter_scale=s, n_steps=bank.n_steps, <the same other arguments>)`` for every scale
+    filter_specs : list of FilterSpec
+        Their FilterSpecs: the same ``n_steps``, ``s_max`` and ``dx_min_sq``, different ``p``
+    last_route : {"bank", "loop", None}
+        Which route the last application took.  ``"bank"``: float64 data on the three grid types above with 2-D grid variables,
+        ``evaluation != "reference"``, more than one scale and a backward cut for the polynomial (``Plan.bank_cut``); ``"loop"``:
+        everything else.  ``GCMF_FILTER_BANK=0`` forces the loop, ``=1`` the bank wherever it is on offer.  At most
+        ``GCMF_BANK_ENTRIES`` (64) entries -- scales x 2-D slices -- go into one library call, which bounds the device memory of a
+        sweep: longer ones are cut over the scales, and over the leading axes of the field where those alone exceed the bound.
+    """
+
+    def __init__(self, filter_scales, dx_min, filter_shape=FilterShape.GAUSSIAN, transition_width=np.pi, ndim=2, n_steps=0,
+                 grid_type=GridType.REGULAR, grid_vars=None, *, evaluation="auto", plan_cache=None):
+        self.dx_min, self.filter_shape, self.transition_width, self.ndim = dx_min, filter_shape, transition_width, ndim
+        self.grid_type, self.grid_vars = grid_type, dict(grid_vars or {})
+        self.evaluation, self.plan_cache = evaluation, plan_cache
+        self.Laplacian = ALL_KERNELS[grid_type]
+        try:
+            scales = [float(s) for s in filter_scales]
+        except TypeError:
+            raise ValueError(f"filter_scales must be a sequence of positive finite numbers, not {filter_scales!r}") from None
+        if not scales:
+            raise ValueError("filter_scales is empty: a FilterBank needs at least one filter scale")
+        for s in scales:
+            if not (np.isfinite(s) and s > 0):
+                raise ValueError(f"filter_scales must be positive finite numbers, not {s!r}")
+        self.filter_scales = scales
+        # Filter's own checks, once (the per-scale objects below repeat them silently: they pass)
+        _forward_only(evaluation)
+        if plan_cache is not None and plan_cache not in PLAN_CACHE_MODES:
+            raise ValueError(f"plan_cache must be one of {PLAN_CACHE_MODES} or None, not {plan_cache!r}")
+        Filter._reject_bad_arguments(types.SimpleNamespace(Laplacian=self.Laplacian, dx_min=dx_min, transition_width=transition_width,
+                                                           ndim=ndim, n_steps=n_steps))
+        asked = int(n_steps)
+        if ndim > 2:
+            self.n_steps = asked
+        else:
+            default = max(int(_compute_n_steps_default(ndim, filter_shape, s, dx_min, transition_width)) for s in scales)
+            if asked >= 3 and asked < default:
+                warnings.warn("You have set n_steps below the default. Results might not be accurate.", stacklevel=2)
+            self.n_steps = asked if asked >= 3 else default
+        with warnings.catch_warnings():   # (a scale whose own default lies above the bank's degree: said once, above, or meant)
+            warnings.filterwarnings("ignore", message="You have set n_steps below the default")
+            self.filters = [Filter(filter_scale=s, dx_min=dx_min, filter_shape=filter_shape, transition_width=transition_width, ndim=ndim,
+                                   n_steps=self.n_steps, grid_type=grid_type, grid_vars=self.grid_vars, evaluation=evaluation,
+                                   plan_cache=plan_cache) for s in scales]
+        self.filter_specs = [f.filter_spec for f in self.filters]
+        self.last_route = None
+        self._memo = _LaplacianMemo(self.Laplacian)
+
+    def __repr__(self):
+        return (f"FilterBank(filter_scales={self.filter_scales!r}, dx_min={self.dx_min!r}, filter_shape={self.filter_shape!r}, "
+                f"transition_width={self.transition_width!r}, ndim={self.ndim!r}, n_steps={self.n_steps!r}, grid_type={self.grid_type!r})")
+
+    # -- the two routes ----------------------------------------------------------------------------
+    def _wants_bank(self):
+        """None: the measured default decides; False / True: GCMF_FILTER_BANK=0 / 1."""
+        env = os.environ.get("GCMF_FILTER_BANK", "")
+        return {"0": False, "1": True}.get(env)
+
+    def _stack(self, parts):
+        if _is_torch(parts[0]):
+            import torch
+            return torch.stack(list(parts))
+        return np.stack([np.asarray(x) for x in parts])
+
+    def _bank_func(self, field, *args):
+        """(len(filter_scales),) + field.shape: every scale's filter of `field`."""
+        want = self._wants_bank()
+        eligible = (len(self.filters) > 1 and self.evaluation != "reference" and want is not False
+                    and not issubclass(self.Laplacian, BaseVectorLaplacian))
+        if eligible and want is None:
+            shape = tuple(getattr(field, "shape", ()))
+            eligible = len(shape) >= 2 and _bank_by_default(len(self.filters), int(shape[-2]), int(shape[-1]))
+        if eligible:
+            with plan_cache_mode(self.plan_cache):
+                out = self._memo.get(args)._run_bank(field, self.filter_specs)
+            if out is not None:
+                self.last_route = "bank"
+                self.last_path = kernels_last_path()
+                return out
+        outs = [f._operator(_create_filter_func)(field, *args) for f in self.filters]
+        self.last_route = "loop"
+        self.last_path = self.filters[-1].last_path
+        return self._stack(outs)
+
+    last_path = None
+
+    def apply(self, field, dims=None):
+        """Every scale's filter of a scalar field: a bare ``numpy.ndarray`` / ``torch.Tensor`` (filtered over its last two axes)
+        gives the same kind of array of shape ``(len(filter_scales),) + field.shape``; an ``xarray.DataArray`` gives one with a
+        new dimension ``filter_scale`` directly before ``dims`` (and, with real xarray, the scales as its coordinate)."""
+        if issubclass(self.Laplacian, BaseVectorLaplacian):
+            raise ValueError(f"Provided Laplacian {self.Laplacian} is a vector Laplacian. "
+                             f"The ``.apply`` method is only suitable for scalar Laplacians.")
+        f0 = self.filters[0]
+        if _is_bare_array(field):
+            return self._bank_func(field, *f0._grid_args(as_xarray=False))
+        xr = _xarray()
+        if xr is None:
+            raise ImportError("xarray is required to filter xarray objects; pass numpy arrays or torch tensors instead")
+        if isinstance(field, xr.Dataset):
+            raise TypeError("FilterBank.apply filters one DataArray at a time: pass the Dataset's variables one by one")
+        assert len(dims) == 2
+
+        def scales_before_core(f, *args):   # apply_ufunc wants the new core dim behind the broadcast dims
+            out = self._bank_func(f, *args)
+            return out.movedim(0, -3) if _is_torch(out) else np.moveaxis(out, 0, -3)
+
+        operands = [field] + f0._grid_args(as_xarray=True)
+        res = xr.apply_ufunc(
+            scales_before_core,
+            *operands,
+            input_core_dims=len(operands) * [list(dims)],
+            output_core_dims=[["filter_scale"] + list(dims)],
+            output_dtypes=[field.dtype],
+            dask="parallelized",
+        )
+        if hasattr(res, "assign_coords"):
+            res = res.assign_coords(filter_scale=list(self.filter_scales))
+        return res
+
+    def apply_to_vector(self, ufield, vfield, dims=None):
+        """Every scale's filter of a vector field (u, v): two results shaped as ``apply``'s.  Vector Laplacians have no one-batch route:
+        the scales run one after the other."""
+        if not issubclass(self.Laplacian, BaseVectorLaplacian):
+            raise ValueError(f"Provided Laplacian {self.Laplacian} is a scalar Laplacian. "
+                             f"The ``.apply_to_vector`` method is only suitable for vector Laplacians.")
+        f0 = self.filters[0]
+
+        def both(u, v, *args):
+            parts = [f._operator(_create_filter_func_vec)(u, v, *args) for f in self.filters]
+            self.last_route = "loop"
+            self.last_path = self.filters[-1].last_path
+            return self._stack([x[0] for x in parts]), self._stack([x[1] for x in parts])
+
+        if _is_bare_array(ufield) and _is_bare_array(vfield):
+            return both(ufield, vfield, *f0._grid_args(as_xarray=False))
+        xr = _xarray()
+        if xr is None:
+            raise ImportError("xarray is required to filter xarray objects; pass numpy arrays or torch tensors instead")
+        assert len(dims) == 2
+
+        def scales_before_core(u, v, *args):
+            return tuple(x.movedim(0, -3) if _is_torch(x) else np.moveaxis(x, 0, -3) for x in both(u, v, *args))
+
+        operands = [ufield, vfield] + f0._grid_args(as_xarray=True)
+        res = xr.apply_ufunc(
+            scales_before_core,
+            *operands,
+            input_core_dims=len(operands) * [list(dims)],
+            output_core_dims=2 * [["filter_scale"] + list(dims)],
+            output_dtypes=[ufield.dtype, vfield.dtype],
+            dask="parallelized",
+        )
+        return tuple(r.assign_coords(filter_scale=list(self.filter_scales)) if hasattr(r, "assign_coords") else r for r in res)

@@ -60,6 +60,13 @@ GAP_FOLD_GRID_TYPES = STACKED_GRID_TYPES
 # 2400 x 3600: 12.86 against 12.84 ms, inside the spread)
 STACK_LEVELS_ABOVE = 64
 
+# ... and the ones whose FILTER BANKS -- several polynomials of one degree on the same fields (FilterBank, gcmf_apply_bank) -- run as one
+# batch with a polynomial per entry; float64, 2-D grid variables and the default (backward) evaluation only
+BANK_GRID_TYPES = STACKED_GRID_TYPES
+# the most entries (polynomials x fields) of one gcmf_apply_bank call: a memory bound, not a tuned number -- an entry costs its output
+# plane plus the four state planes of the work buffer (GCMF_BANK_ENTRIES)
+BANK_ENTRIES = 64
+
 ArrayType = np.ndarray
 
 
@@ -773,6 +780,69 @@ class _DeviceLaplacian:
                     raise
                 return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32)
         return outs
+
+    def _run_bank(self, field, specs):
+        """FilterBank's one-batch route: the polynomials of `specs` (one degree, one s_max) on every 2-D slice of `field` through
+        gcmf_apply_bank; the result has shape (len(specs),) + field.shape and, slice by slice, the bits of _run with each spec.  None
+        where the library has no bank for this Laplacian, data or polynomial (the caller then runs the specs one after the other).
+        At most GCMF_BANK_ENTRIES entries per call: a longer sweep is cut over the polynomials, and over the fields where they alone
+        exceed the bound; every call writes straight into the one output array.  A host array goes up through torch."""
+        if self._glead is not None or self._NCOMP != 1 or self.GRID_TYPE not in BANK_GRID_TYPES or not self._planes:
+            return None
+        given = field
+        f = _unwrap(field)
+        shape = tuple(f.shape)
+        if len(shape) < 2:
+            raise ValueError("fields need at least two (y, x) dimensions")
+        if compute_dtype([f] + list(self._planes)) != _lib.F64:
+            return None
+        import torch
+        ny, nx = shape[-2:]
+        nfield = int(np.prod(shape[:-2], dtype=np.int64)) if len(shape) > 2 else 1
+        nbank, n_steps = len(specs), int(specs[0].n_steps)
+        gpu = _on_gpu(f)
+        dev = f.device.index if gpu else current_device()
+        plan = self._plan(_lib.F64, (ny, nx), dev)
+        if not plan.bank_cut(n_steps, max(1, nbank * nfield)):
+            return None
+        spec = specs[0]
+        c = 2 / spec.s_max if self.is_dimensional else 2 / (spec.s_max * spec.dx_min_sq)
+        P = np.ascontiguousarray([np.asarray(s.p, dtype=np.float64) for s in specs])
+        try:
+            bound = max(1, int(os.environ.get("GCMF_BANK_ENTRIES", "") or BANK_ENTRIES))
+        except ValueError:
+            bound = BANK_ENTRIES
+        if gpu:
+            src = f if (f.dtype == torch.float64 and f.is_contiguous()) else f.to(torch.float64).contiguous()
+            out = torch.empty((nbank,) + shape, dtype=torch.float64, device=f.device)
+            out4 = out.view(nbank, nfield, ny, nx)
+        else:
+            host = f.detach().cpu().numpy() if _is_torch(f) else np.asarray(f)
+            src = torch.as_tensor(np.ascontiguousarray(host, dtype=np.float64)).to(f"cuda:{dev}")
+            out = _host_output((nbank,) + shape, np.float64)
+            out4 = torch.from_numpy(out.reshape(nbank, nfield, ny, nx))
+        if nfield == 0:
+            return _same_kind(out, given)
+        src3 = src.view(nfield, ny, nx)
+        # all fields and as many polynomials as fit, or -- more fields than the bound -- one polynomial and as many fields as fit:
+        # either way the call's input and output are contiguous slices
+        if nfield <= bound:
+            chunks = [(j, min(nbank, j + bound // nfield), 0, nfield) for j in range(0, nbank, bound // nfield)]
+        else:
+            chunks = [(j, j + 1, i, min(nfield, i + bound)) for j in range(nbank) for i in range(0, nfield, bound)]
+        cur = torch.cuda.current_stream(dev)
+        try:
+            for j0, j1, i0, i1 in chunks:
+                dst = out4[j0:j1, i0:i1] if gpu else torch.empty((j1 - j0, i1 - i0, ny, nx), dtype=torch.float64, device=src.device)
+                plan.apply_bank(P[j0:j1], c, src3[i0:i1].data_ptr(), dst.data_ptr(), i1 - i0, stream=cur.cuda_stream)
+                if not gpu:
+                    out4[j0:j1, i0:i1].copy_(dst)   # (synchronises)
+            _note_path(plan.last_path(), plan.device)
+        except _lib.GcmfError as e:
+            raise _translate(e) from None
+        if gpu and src is not f:
+            src.record_stream(cur)
+        return _same_kind(out, given)
 
     def _gap_fallback(self, given, fields, spec, out_f32, forward, backward_f32):
         """faces_from_nan where the flagged call is not on offer: wet_mask * notnull(field) built here and handed in as a grid variable

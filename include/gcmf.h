@@ -225,6 +225,33 @@ int gcmf_plan_rows(const gcmf_plan *plan, int64_t *rows_alloc, int64_t *first_ow
 int gcmf_apply(gcmf_plan *plan, const double *p, int n_steps, double c, const void *const *in,
                void *const *out, int64_t nbatch, uint32_t flags, void *stream);
 
+/*
+ * A FILTER BANK: nbank polynomials of ONE degree applied to the same nfield fields in one call -- a sweep over filter scales, whose
+ * polynomials share n_steps, c and the grid (s_max does not depend on the filter scale) and differ in p alone:
+ *     out[j * nfield + i] = the polynomial p[j * (n_steps + 1) .. (j + 1) * (n_steps + 1)) applied to in[i]      (j < nbank, i < nfield)
+ * `p`: nbank x (n_steps + 1) host doubles, row-major.  `in`: (nfield, ny, nx) f64, `out`: (nbank, nfield, ny, nx) f64, device pointers
+ * (GCMF_DEVICE_PTRS is required), which must not overlap.  `stream` as for gcmf_apply with device pointers.
+ *   Scope: ordinary (not stacked) f64 plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T that cover the whole grid (no row slab, no
+ *   GCMF_PLAN_SELF_RING), and a polynomial for which gcmf_bank_cut offers a cut -- anything else returns GCMF_ERR_UNSUPPORTED and names
+ *   the function and the limit: host pointers, an f32 plan, another grid type, a stacked plan, GCMF_FORWARD_RECURRENCE,
+ *   GCMF_MASK_FROM_NAN, GCMF_FACES_FROM_NAN, GCMF_OUT_F32, fewer than five steps, nx not a multiple of 4 on a grid with land,
+ *   GCMF_CLENSHAW=0.  GCMF_ERR_INVALID_ARG: nbank < 1, n_steps < 1, a null pointer, `in` overlapping `out`.  nfield = 0: GCMF_OK.
+ *   The call runs the backward evaluation's plain strips with the nbank * nfield entries as the batch (k_ringc, one workgroup column per
+ *   entry, every entry reading the coefficients of its own polynomial from a table on the device and the input plane of its own field)
+ *   and k_land_fix in the same form; never the on-chip kernel, "single_launch", the packed walk, the zipped strips or the wet-row tables.
+ *   More than 32768 entries are cut into consecutive launches.  out[j, i] has the bits of
+ *   gcmf_apply(plan, p_j, ..., in_i, nbatch = 1, GCMF_NO_RESIDENT) -- the backward result does not depend on how the levels or the
+ *   strips are cut -- NaN, +-inf and land cells included.  The two coefficient tables live in the plan (grow-only, freed by
+ *   gcmf_plan_destroy) and are uploaded only when `p` differs from the previous call's, after the stream has drained.
+ *   gcmf_last_timing, gcmf_last_kernel and gcmf_plan_last_path (GCMF_PATH_STRIPS) work as after gcmf_apply; gcmf_last_kernel names the
+ *   ordinary kernel (the launches are an instantiation of their own of it), gcmf_last_kernel_geometry appends " bank=<nbank>".
+ * gcmf_bank_cut: the launch depths (5 .. 9 levels each) gcmf_apply_bank uses for a polynomial of n_steps steps and nentries = nbank *
+ * nfield entries, written to depths[0 .. return value); 0 = a bank is not on offer for this plan / polynomial.
+ */
+extern int gcmf_apply_bank(gcmf_plan *plan, const double *p, int nbank, int n_steps, double c, const void *in, void *out, int64_t nfield,
+                           uint32_t flags, void *stream);
+extern int gcmf_bank_cut(const gcmf_plan *plan, int n_steps, int64_t nentries, int *depths, int max_depths);
+
 /* One application of the Laplacian: `ALL_KERNELS[grid_type](**grid_vars)(field)` (kernels.py
  * __call__ methods; no prepare/finalize).  `out` has the plan dtype. */
 int gcmf_laplacian(gcmf_plan *plan, const void *const *in, void *const *out, int64_t nbatch,
