@@ -26,6 +26,7 @@
 // below the seam and k_fold_band's backward form (gcmf_foldband.hip) advances those rows beside it.
 #pragma once
 #include "gcmf_ring_impl.hpp"
+#include "gcmf_wet_cut.hpp"
 
 namespace gcmf {
 
@@ -196,8 +197,64 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
   const bool weigh = !FLUX && P.area_weighted;
   const T *abase = weigh ? P.area : P.fb_in;  // (an unconditional load, ignored when there is no area)
 
+  // XO (round 9): a table march keeps its rows as RUNNING BYTE OFFSETS inside a plane instead of row numbers.  xco is the cursor row's
+  // offset, cj nx sizeof(T), a 32-bit scalar; it moves by xstep (one row, down or up the grid) and on reaching xlim (one row beyond the
+  // grid's end on that side) becomes xreset, the other end: the table is taken on grids that wrap in y only, and only where
+  // rows nx sizeof(T) < 2^32 (table_rows_ok, gcmf_wet_cut.hpp; the launcher asks).  A strip of a table starts inside the grid -- the
+  // cursor's first row is mid - 2 or mid + 1 of a pair lo + 2 <= mid <= hi - 2 -- so this is the whole of advance().  A lane's address
+  // is a wave-uniform plane base + ONE 32-bit offset per row, xvc (cursor) / xvp (the row before it, the centre row), shared by all
+  // planes: the scalar-base form of the global loads and stores; the bases never change during a march.  The store rows trail the cursor
+  // by a fixed number of phases and lie inside [a, b): one more running offset, xsu, no wrap.
+  unsigned xco = 0u, xstep = 0u, xlim = 0u, xreset = 0u, xsu = 0u, xhv = 0u;
+  unsigned xvc = 0u, xvp = 0u;
+  const char *xbE = nullptr, *xbN = nullptr, *xbA = nullptr, *xbF = nullptr, *xbZ = nullptr, *xbU = nullptr, *xbV = nullptr;
+  char *xbSu = nullptr, *xbSv = nullptr;
+  T xtwo = T(2);
+  if constexpr (XO) {
+    const unsigned rowB = (unsigned)nx * (unsigned)sizeof(T);
+    xstep = up ? 0u - rowB : rowB;
+    xlim = up ? 0u - rowB : (unsigned)rows * rowB;
+    xreset = up ? (unsigned)(rows - 1) * rowB : 0u;
+    xco = (unsigned)cr * rowB;
+    xvc = xco + colT;
+    xvp = xvc;
+    xbE = reinterpret_cast<const char *>(P.cE);
+    xbN = reinterpret_cast<const char *>(P.cN);
+    xbA = reinterpret_cast<const char *>(P.ra);
+    xbF = reinterpret_cast<const char *>(fplane);
+    xbZ = reinterpret_cast<const char *>(zbase);
+    xbU = reinterpret_cast<const char *>(P.u0 + boff);
+    xbV = reinterpret_cast<const char *>(P.v0 + boff);
+    xbSu = reinterpret_cast<char *>((last ? P.fb_out : P.uo) + boff);
+    xbSv = reinterpret_cast<char *>(P.vo + boff);
+    const int m0 = r_begin - S;   // the first phase's store row in march order
+    xsu = (unsigned)(up ? mir - m0 : m0) * rowB;   // (mod 2^32: exact whenever the row lies inside [a, b))
+    xhv = last ? 0u : (unsigned)(b - a);   // (a last launch stores no second state)
+    xtwo = last ? T(1) : T(2);
+  }
+  auto xadvance = [&]() {
+    xvp = xvc;
+    const unsigned t = xco + xstep;
+    if (__builtin_expect(t == xlim, 0)) {
+      xco = xreset;
+    } else {
+      xco = t;
+    }
+    xvc = xco + colT;
+  };
+  auto xat = [](auto *base, unsigned off) { return base + off; };   // (uniform base) + (zero-extended 32-bit lane offset)
+
   auto load_u = [&](auto slot_c) {  // the cursor's row of b_{k+1}; in a first launch that is b_n = p_n f, formed from the row of f
     constexpr int sl = decltype(slot_c)::value;
+    if constexpr (XO) {
+      if constexpr (!FIRST) {
+        mload<T, VEC>(G0[sl], reinterpret_cast<const T *>(xat(xbU, xvc)));
+      } else {
+        mload<T, VEC>(G0[sl], reinterpret_cast<const T *>(xat(xbF, xvc)));
+        Zu[sl] = cell_bytes<VEC>(reinterpret_cast<const uint8_t *>(xat(xbZ, xvc / (unsigned)sizeof(T))));
+      }
+      return;
+    }
     const long long rcur = (long long)(cj * nx);
     if constexpr (!FIRST) {
       mload<T, VEC>(G0[sl], lane_ptr(P.u0 + boff + rcur, colT));
@@ -210,6 +267,21 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
   auto load_centre = [&](auto slot_c, auto vslot_c) {  // what travels with the row before it: b_{k+2}, f, coefficients / mask bits
     constexpr int sl = decltype(slot_c)::value;
     constexpr int vs = decltype(vslot_c)::value;
+    if constexpr (XO) {
+      // (the empty asm makes the offset a value of THIS basic block: with the zero-extension hoisted to the block of the phase before,
+      // where the same offset served the cursor's loads, instruction selection takes a 64-bit vector add per load instead of the
+      // scalar-base form)
+      unsigned oc = xvp, on = up ? xvc : xvp;   // (an upward march: the cursor row's north face)
+      asm("" : "+v"(oc));
+      asm("" : "+v"(on));
+      mload<T, VEC>(cE[sl], reinterpret_cast<const T *>(xat(xbE, oc)));
+      mload<T, VEC>(cN[sl], reinterpret_cast<const T *>(xat(xbN, on)));
+      mload<T, VEC>(ra[sl], reinterpret_cast<const T *>(xat(xbA, oc)));
+      mload<T, VEC>(Ff[sl], reinterpret_cast<const T *>(xat(xbF, oc)));
+      Zc[sl] = cell_bytes<VEC>(reinterpret_cast<const uint8_t *>(xat(xbZ, oc / (unsigned)sizeof(T))));
+      if constexpr (!FIRST) mload<T, VEC>(V[vs], reinterpret_cast<const T *>(xat(xbV, oc)));
+      return;
+    }
     const bool out_c = cout_prev;
     const long long rc = (long long)(cj_prev * nx);
     if constexpr (FLUX) {
@@ -268,7 +340,9 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
       wv = from_lower_lane0(gC[VEC - 1]);
     }
     // the last level of the last launch is the result  p_0 f + A(b_1) - b_2: A, not 2 A
-    const T two = (last && t == S) ? T(1) : T(2);
+    T two;
+    if constexpr (XO) two = (t == S) ? xtwo : T(2);   // (chosen once per march)
+    else two = (last && t == S) ? T(1) : T(2);
 #pragma unroll
     for (int k = 0; k < VEC; ++k) {
       const T xC = gC[k];
@@ -322,7 +396,8 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
     // the strip's first period: level t starts with phase 2 t - 1 (below).  Flux kinds only: the land-mask / REGULAR kernels lose 3-4 % at
     // full size with the peeled period (config 2: 82 -> 85 us per launch on one box) and gain 3 % on 1/4-degree grids.
     constexpr bool PRO = decltype(pro_c)::value && FLUX;
-    advance();
+    if constexpr (XO) xadvance();
+    else advance();
     load_centre(ic<(ph + D) % R>{}, ic<(ph + D) % RV>{});
     load_u(ic<(ph + D) % RU>{});
     if constexpr (FIRST) {  // the row of f that has just arrived becomes a row of b_n = p_n f (prepared, land out)
@@ -332,7 +407,8 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
         if constexpr (!FLUX) G0[su][k] = weigh ? G0[su][k] * ARu[su][k] : G0[su][k];
-        G0[su][k] = (!has_land || ((Zu[su] >> (8 * k)) & 1u)) ? pn * G0[su][k] : T(0);
+        if constexpr (XO) G0[su][k] = ((Zu[su] >> (8 * k)) & 1u) ? pn * G0[su][k] : T(0);   // (a table is cut from the land bytes: there are some)
+        else G0[su][k] = (!has_land || ((Zu[su] >> (8 * k)) & 1u)) ? pn * G0[su][k] : T(0);
       }
     }
     {  // the f row level 1 uses now: prepare() and land out (once per row; the later levels find it that way in the ring)
@@ -340,7 +416,8 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
 #pragma unroll
       for (int k = 0; k < VEC; ++k) {
         if constexpr (!FLUX) Ff[s1][k] = weigh ? Ff[s1][k] * ARc[s1][k] : Ff[s1][k];
-        Ff[s1][k] = (!has_land || ((Zc[s1] >> (8 * k)) & 1u)) ? Ff[s1][k] : T(0);
+        if constexpr (XO) Ff[s1][k] = ((Zc[s1] >> (8 * k)) & 1u) ? Ff[s1][k] : T(0);
+        else Ff[s1][k] = (!has_land || ((Zc[s1] >> (8 * k)) & 1u)) ? Ff[s1][k] : T(0);
       }
     }
     // The ramp: phase q of a strip (q = 0 at row r_begin = a - S) produces row a - S + q - t of level t, and the strip needs level t from
@@ -399,6 +476,17 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
 #pragma unroll
       for (int k = 0; k < VEC; ++k) FN[t + 1][k] = ((SANI ? msan(own[k]) : own[k]) - (SANI ? msan(oth[k]) : oth[k])) * cNs[k];
     }
+    if constexpr (XO) {   // (f64 flux kinds: no finalize(), no f64 copy of an f32 state)
+      const unsigned q = (unsigned)(r - S - a);   // the store row in march order, from a: the mirror maps [a, b) onto itself
+      if (q < (unsigned)(b - a)) {  // wave-uniform
+        if (keep) mstore<T, VEC>(reinterpret_cast<T *>(xat(xbSu, xsu + colT)), out_u);
+      }
+      if (q + 1u < xhv) {
+        if (keep) mstore<T, VEC>(reinterpret_cast<T *>(xat(xbSv, xsu + xstep + colT)), out_v);
+      }
+      xsu += xstep;
+      return;
+    }
     const int ju = up ? mir - (r - S) : r - S;
     if (ju >= a && ju < b) {  // wave-uniform
       const long long off = boff + (long long)ju * nx;
@@ -430,13 +518,16 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
     }
   };
 
-  advance();
+  if constexpr (XO) xadvance();
+  else advance();
   load_centre(ic<0>{}, ic<0>{});
   load_u(ic<0>{});
-  advance();
+  if constexpr (XO) xadvance();
+  else advance();
   load_centre(ic<1>{}, ic<1>{});
   load_u(ic<1>{});
-  advance();
+  if constexpr (XO) xadvance();
+  else advance();
   load_centre(ic<2>{}, ic<2>{});
   load_u(ic<2>{});
   static_assert(D == 3, "prologue");
@@ -705,7 +796,9 @@ static int launch_ringc_zip_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut
   // (round 7) whole grids with land, a lone field: the pairs cut from the rows of each window that hold anything wet -- the wave slots
   // of all-land tiles go to the wet part, and every strip gets shorter (wet_table, gcmf_ringc_zip.hip)
   const WetTable *tab = nullptr;
-  if (sizeof(T) == 8 && pl->wet_now && !folds) {
+  // (round 9: the table march addresses a plane with 32-bit byte offsets and knows no closed end -- a plane of 4 GiB or more, or a grid
+  // that does not wrap in y, keeps the even cut)
+  if (sizeof(T) == 8 && pl->wet_now && !folds && table_rows_ok(pl->g.rows, pl->g.nx, (long long)sizeof(T), pl->g.south_wrap && pl->g.north_wrap)) {
     int rc = GCMF_OK;
     tab = wet_table(pl, a, cut.march, s, &rc);
     if (rc) return rc;

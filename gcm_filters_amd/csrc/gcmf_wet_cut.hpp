@@ -37,6 +37,22 @@ struct WetCut {
   std::vector<WetUnit> units;
 };
 
+// Round 9: a table march (ringc_march<XO>, gcmf_ringc_impl.hpp) addresses a plane with a uniform base and ONE 32-bit byte offset per lane and
+// row, so every byte of a plane -- rows x nx cells of `cell` bytes; batch and level offsets are part of the base -- must lie below 2^32, and
+// "one row beyond the last" (the march's wrap test) must still be a 32-bit number of its own: rows nx cell < 2^32.  A launch that does not
+// meet this keeps the even cut, as one whose table is refused does.
+inline bool table_rows_fit32(long long rows, long long nx, long long cell) {
+  if (rows < 1 || nx < 1 || cell < 1) return false;
+  const unsigned long long lim = 1ull << 32;
+  if ((unsigned long long)nx > lim / (unsigned long long)cell) return false;
+  const unsigned long long row = (unsigned long long)nx * (unsigned long long)cell;
+  return (unsigned long long)rows <= (lim - 1) / row;   // rows * row <= 2^32 - 1
+}
+// ... and the march wraps its cursor from one end of the grid to the other, nothing else: beyond a closed end (a row slab, a tripolar grid's
+// south) the coefficient rows would have to come from the row of zeros.  No plan that gcmf_apply offers a table to has closed ends today
+// (whole grids without a fold wrap); the launcher asks all the same.
+inline bool table_rows_ok(long long rows, long long nx, long long cell, bool wraps_in_y) { return wraps_in_y && table_rows_fit32(rows, nx, cell); }
+
 namespace wet_detail {
 
 struct Run { int wx, lo, hi; };
