@@ -370,7 +370,7 @@ class Plan:
                    flags: int = 0):
         """A filter bank (gcmf_apply_bank): the rows of `p`, (nbank, n_steps + 1), are polynomials of one degree; out[j, i] = row j
         applied to field i of `src` -- (nfield, ny, nx) and (nbank, nfield, ny, nx) float64 device pointers that do not overlap.
-        Ordinary whole-grid float64 IRREGULAR_WITH_LAND / MOM5U / MOM5T plans with a backward cut (bank_cut); anything else raises
+        Ordinary whole-grid float64 IRREGULAR_WITH_LAND / MOM5U / MOM5T / TRIPOLAR_POP_WITH_LAND plans with a backward cut (bank_cut); anything else raises
         GcmfError(ERR_UNSUPPORTED).  flags: further GCMF_* bits (the library refuses all but GCMF_NO_RESIDENT)."""
         p = np.ascontiguousarray(p, dtype=np.float64)
         if p.ndim != 2:

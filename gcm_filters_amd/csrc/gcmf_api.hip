@@ -1256,13 +1256,13 @@ int gcmf_apply_bank(gcmf_plan *pl, const double *p, int nbank, int n_steps, doub
     return GCMF_ERR_INVALID_ARG;
   }
   const int gt = pl->d.grid_type;
-  const bool kind_ok = gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T;
+  const bool kind_ok = gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T || gt == GCMF_TRIPOLAR_POP_WITH_LAND;
   const char *why = !kind_ok ? "another grid type" : pl->d.dtype != GCMF_F64 ? "an f32 plan" : (pl->d.flags & GCMF_PLAN_SELF_RING) ? "GCMF_PLAN_SELF_RING" :
                     !pl->full ? "a row slab" : pl->stacked ? "a stacked plan (gcmf_plan_create_levels)" : !(flags & GCMF_DEVICE_PTRS) ? "host pointers (GCMF_DEVICE_PTRS is required)" :
                     (flags & GCMF_FORWARD_RECURRENCE) ? "GCMF_FORWARD_RECURRENCE" : (flags & GCMF_MASK_FROM_NAN) ? "GCMF_MASK_FROM_NAN" :
                     (flags & GCMF_FACES_FROM_NAN) ? "GCMF_FACES_FROM_NAN" : (flags & GCMF_OUT_F32) ? "GCMF_OUT_F32" : nullptr;
   if (why) {
-    set_error("gcmf_apply_bank: filter banks run on ordinary whole-grid f64 plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T with device pointers, "
+    set_error("gcmf_apply_bank: filter banks run on ordinary whole-grid f64 plans of IRREGULAR_WITH_LAND, MOM5U, MOM5T and TRIPOLAR_POP_WITH_LAND with device pointers, "
               "backwards, on the plan's own mask and into f64 (%s; grid type %d): call gcmf_apply once per polynomial", why, gt);
     return GCMF_ERR_UNSUPPORTED;
   }

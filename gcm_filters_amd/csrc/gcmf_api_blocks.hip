@@ -80,11 +80,12 @@ int clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, 
   return clenshaw_cut_for(pl, n_steps, depths, max_depths, f32_asked, nbatch, pl && (pl->stacked || pl->bank_n > 0));
 }
 
-// A filter bank (gcmf_apply_bank): the cut of the plain strips -- what a stacked plan of the same grid gets
+// A filter bank (gcmf_apply_bank): the cut of the plain strips -- what a stacked plan of the same grid gets; on TRIPOLAR_POP_WITH_LAND the
+// plain strips below the seam and k_fold_band's per-entry form on its rows, so launches of at most eight levels (clenshaw_cut_for)
 bool bank_plan_ok(const gcmf_plan *pl) {
   const int gt = pl ? pl->d.grid_type : -1;
-  return pl && (gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T) && pl->kind == K_FLUX && pl->d.dtype == GCMF_F64 && pl->full &&
-         !pl->stacked && !pl->g.fold && !pl->mask_per_field;
+  return pl && (gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T || gt == GCMF_TRIPOLAR_POP_WITH_LAND) && pl->kind == K_FLUX &&
+         pl->d.dtype == GCMF_F64 && pl->full && !pl->stacked && !pl->mask_per_field;
 }
 int bank_cut(const gcmf_plan *pl, int n_steps, int64_t nentries, int *depths, int max_depths) {
   if (!bank_plan_ok(pl) || !depths || max_depths < 1 || nentries < 1 || n_steps < 1) return 0;
@@ -106,7 +107,9 @@ static int clenshaw_cut_for(const gcmf_plan *pl, int n_steps, int *depths, int m
   // (f32 state: the flux kinds since round 3, the REGULAR / land-mask kinds since round 4)
   if (!pl->ring || !pl->zero_row || pl->multi_s < 8 || !multi_supported(pl, 8)) return 0;
   if (pl->n_land > 0 && !land_ok(pl, n_steps)) return 0;
-  const bool nines_full = ringc9_ok(pl) || ringc9_fold_ok(pl, nbatch, 0, pl->g.rows), nines = nines_full || ringc9_slab_ok(pl);
+  // (plain_only on a plan with a seam: k_fold_band advances it, eight levels at most -- asked here and not through ringc_cut_in, whose answer
+  // depends on whether a bank call is running now: gcmf_bank_cut must say outside the call what the call will run)
+  const bool nines_full = ringc9_ok(pl) || (!plain_only && ringc9_fold_ok(pl, nbatch, 0, pl->g.rows)), nines = nines_full || ringc9_slab_ok(pl);
   if (!(n_steps >= 10 || (n_steps >= 5 && n_steps <= 8) || (n_steps == 9 && nines))) return 0;
   int smax = pl->ringc_smax;
   if (!smax && nbatch == 1 && !plain_only && nines_full && pl->ringc_zip && (long long)pl->g.rows * pl->g.nx <= 2500000LL && n_steps >= 10) {

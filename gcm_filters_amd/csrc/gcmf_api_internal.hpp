@@ -18,7 +18,7 @@ int dom_collect(gcmf_plan *pl);
 bool land_ok(const gcmf_plan *pl, int n_steps);
 bool ringc9_ok(const gcmf_plan *pl);
 int clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, bool f32_asked = false, int64_t nbatch = 1);   // (nbatch: a lone field on a cache-resident grid may be cut into shallower launches)
-bool bank_plan_ok(const gcmf_plan *pl);   // an ordinary whole-grid f64 plan of the flux kinds without a seam: what gcmf_apply_bank runs on
+bool bank_plan_ok(const gcmf_plan *pl);   // an ordinary whole-grid f64 plan of the four flux-form grid types: what gcmf_apply_bank runs on
 int bank_cut(const gcmf_plan *pl, int n_steps, int64_t nentries, int *depths, int max_depths);   // gcmf_bank_cut
 bool ptr_al16(const void *p);
 int vec_backward_next_depth(const gcmf_plan *pl, int64_t nbatch, int left, int smax);

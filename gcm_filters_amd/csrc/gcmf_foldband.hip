@@ -20,7 +20,9 @@
 //     BACKWARD = k_ringc's march (gcmf_ringc_impl.hpp): b_k = p_k f + 2 A(b_{k+1}) - b_{k+2};
 //   * nan_to_num is the identity on finite data: a workgroup only runs its stencil operands through it from the level on at
 //     which one of its values is not finite (a workgroup-wide OR rides on the level barrier) -- same results, 40 % fewer
-//     instructions on clean data.
+//     instructions on clean data;
+//   * a filter bank (gcmf_apply_bank on TRIPOLAR_POP_WITH_LAND) runs the backward f64 flux form with a polynomial per batch entry, beside
+//     or after the bank's plain strips: k_fold_band<double, double, K_FLUX, true, NT, true> (fold_band_body<..., PB> below).
 //
 // Replaces the S dependent k_scalar_step launches (~10 us each) rounds 1-2 ran on the side stream.
 #include "gcmf_multi_common.hpp"
@@ -49,15 +51,27 @@ template <typename T, typename FB> struct FoldBandP {
   long long bstride;
   double pk[MAX_S];
   double p0, c;
+  // a filter bank (gcmf_apply_bank; the PB form of the backward f64 flux kernel only: no other instantiation reads these) -- MultiP's fields
+  // of these names with MultiP's conventions (gcmf_multi_common.hpp), so that the one reversed table serves k_ringc and this kernel
+  const double *ptab = nullptr;
+  int pstride = 0, poff = 0;
+  int nfield = 1, ent0 = 0;
 };
 
 // NT = 256: the form that runs BESIDE the blocked launch (four tile rows per pass, few registers).  NT = 1024 (round 6): one cell per thread,
 // run AFTER the blocked launch in its stream where that launch is short (1/4-degree grids, the top rank's slab of an 8-way run): alone on
 // the chip the band is a few microseconds, beside a launch that lasts no longer than itself it is the slower of the two and costs a
 // fork / join on top.
-template <typename T, typename FB, int KIND, bool BACK, int NT>
-__global__ __launch_bounds__(NT) void k_fold_band(const FoldBandP<T, FB> P) {
+// PB: a filter bank (gcmf_apply_bank; backward, f64, K_FLUX) -- entry e = P.ent0 + blockIdx.y of the launch is polynomial e / P.nfield on field
+// e % P.nfield: the constant input comes from that field's plane, the states and the result stay the entry's own, and the S + 1 coefficients
+// (a first launch's p_n, then levels 1 .. S) come from row e / nfield of the reversed table ringc_march<..., PB> reads (MultiP::ptab) -- once
+// per workgroup, into LDS behind the tile (they depend on blockIdx.y and kernel arguments only).  A kernel of its own,
+// k_fold_band<T, FB, KIND, BACK, NT, true>: the other instantiations read none of it (as many instructions within eight of their 500 to 900, in
+// another register allocation, compared in the assembly of the two builds).
+template <typename T, typename FB, int KIND, bool BACK, int NT, bool PB>
+__device__ __forceinline__ void fold_band_body(const FoldBandP<T, FB> &P) {
   extern __shared__ __align__(16) unsigned char smem[];
+  static_assert(!PB || (BACK && KIND == K_FLUX && sizeof(T) == 8), "filter banks: the backward evaluation of the f64 flux kinds");
   constexpr bool FLUX = (KIND == K_FLUX);
   constexpr bool FUSED = FLUX || BACK;   // gcmf_recurrence.hpp; the backward evaluation fuses every multiply-add pair
   T *sA = reinterpret_cast<T *>(smem);
@@ -67,6 +81,7 @@ __global__ __launch_bounds__(NT) void k_fold_band(const FoldBandP<T, FB> P) {
   T *sF = sra + (FLUX ? FB_CELLS : 0);           // BACK: the constant input (prepared, land out)
   FB *sFB = reinterpret_cast<FB *>(sF + (BACK ? FB_CELLS : 0));   // forward: running sum (band rows)
   uint8_t *smb = reinterpret_cast<uint8_t *>(sFB + (BACK ? 0 : FB_CELLS));   // K_MASK: mask bytes
+  double *spk = reinterpret_cast<double *>(sFB);                              // PB: spk[t] = the entry's coefficient of level t (1 .. S)
 
   const int tid = threadIdx.x;
   constexpr int RSTEP = NT / (2 * FB_WW);   // tile rows a pass of the workgroup covers
@@ -85,6 +100,17 @@ __global__ __launch_bounds__(NT) void k_fold_band(const FoldBandP<T, FB> P) {
   }
   const long long boff = (long long)blockIdx.y * P.bstride;
   const long long moff = (!FLUX && P.mper) ? boff : 0;
+  long long foff = boff;   // the constant input's plane
+  T pn = (T)P.p0;
+  if constexpr (PB) {   // (workgroup-uniform: blockIdx.y and kernel arguments only)
+    typedef const __attribute__((address_space(4))) double *ctab_t;   // (nothing writes the table while a launch runs)
+    const int ent = P.ent0 + (int)blockIdx.y;
+    const int pol = ent / P.nfield;
+    foff = (long long)(ent - pol * P.nfield) * P.bstride;
+    const long long ro = (long long)pol * P.pstride + P.poff;
+    if (tid >= 1 && tid <= P.S) spk[tid] = P.ptab[ro + tid];   // (visible after the barrier that ends the tile's load)
+    if (P.first) pn = (T)((ctab_t)P.ptab)[ro];
+  }
   const T c = (T)P.c;
   const bool weigh = !FLUX && P.area_weighted;
   const int row_base = rows - ntr;
@@ -107,13 +133,13 @@ __global__ __launch_bounds__(NT) void k_fold_band(const FoldBandP<T, FB> P) {
       smb[cell] = P.mbits[moff + g];
     }
     if constexpr (BACK) {
-      T fv = P.f[boff + g];
+      T fv = P.f[foff + g];
       if (weigh) fv = fv * ar;                    // prepare(): f * area (kernels.py:100-101)
       fv = keep ? fv : T(0);                      // isolated cells stay out of the state (k_land_fix writes their polynomial)
       sF[cell] = fv;
       T x;
       if (P.first) {                              // b_n = p_n f, b_{n+1} = 0
-        x = keep ? (T)P.p0 * fv : T(0);
+        x = keep ? pn * fv : T(0);
         sB[cell] = T(0);
       } else {
         x = P.u0[boff + g];
@@ -143,7 +169,9 @@ __global__ __launch_bounds__(NT) void k_fold_band(const FoldBandP<T, FB> P) {
   auto level = [&](auto sani_c, const int t, const T *cur, T *prv) -> bool {
     constexpr bool SANI = decltype(sani_c)::value;
     auto san = [](T v) { return SANI ? msan(v) : v; };   // kernels.py:175, 300, 472, 566: the stencil sees nan_to_num(field)
-    const T pk = (T)P.pk[t - 1];
+    T pk;
+    if constexpr (PB) pk = (T)spk[t];
+    else pk = (T)P.pk[t - 1];
     const T two = (BACK && P.last && t == S) ? T(1) : T(2);   // the result  p_0 f + A(b_1) - b_2: A, not 2 A
     bool nf = false;
 #pragma unroll 1
@@ -241,6 +269,16 @@ __global__ __launch_bounds__(NT) void k_fold_band(const FoldBandP<T, FB> P) {
 }
 
 template <typename T, typename FB, int KIND, bool BACK, int NT>
+__global__ __launch_bounds__(NT) void k_fold_band(const FoldBandP<T, FB> P) {
+  fold_band_body<T, FB, KIND, BACK, NT, false>(P);
+}
+template <typename T, typename FB, int KIND, bool BACK, int NT, bool PB>
+__global__ __launch_bounds__(NT) void k_fold_band(const FoldBandP<T, FB> P) {
+  static_assert(PB, "an ordinary launch is k_fold_band<T, FB, KIND, BACK, NT>");
+  fold_band_body<T, FB, KIND, BACK, NT, true>(P);
+}
+
+template <typename T, typename FB, int KIND, bool BACK, int NT, bool PB = false>
 static int launch_fb_nt(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
   const Geom &g = pl->g;
   FoldBandP<T, FB> P{};
@@ -283,6 +321,22 @@ static int launch_fb_nt(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
   size_t lds = (size_t)FB_CELLS * sizeof(T) * (2 + (KIND == K_FLUX ? 3 : 0) + (BACK ? 1 : 0)) + (BACK ? 0 : (size_t)FB_CELLS * sizeof(FB)) +
                (KIND == K_FLUX ? 0 : (size_t)FB_CELLS);
   static bool attr_set = false;  // per instantiation
+  if constexpr (PB) {   // a filter bank's launch: the coefficients from the plan's reversed table (launch_ringc_bank_sf sets the same five)
+    P.ptab = pl->bank_rev;
+    P.pstride = (int)pl->bank_stride;
+    P.poff = a.lvl - 1;
+    P.nfield = (int)pl->bank_nfield;
+    P.ent0 = (int)pl->entry0;
+    lds += (size_t)(MAX_S + 1) * sizeof(double);
+    if (!attr_set && lds > 48 * 1024) {
+      GCMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fold_band<T, FB, KIND, BACK, NT, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      attr_set = true;
+    }
+    hipLaunchKernelGGL((k_fold_band<T, FB, KIND, BACK, NT, true>), dim3((unsigned)P.npairs, (unsigned)a.nbatch), dim3(NT), lds, s, P);
+    GCMF_HIP(hipGetLastError());
+    return GCMF_OK;
+  }
   if (!attr_set && lds > 48 * 1024) {
     GCMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fold_band<T, FB, KIND, BACK, NT>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -311,6 +365,13 @@ int launch_fold_band(gcmf_plan *pl, const MultiArgs &a, bool backward, hipStream
     return GCMF_ERR_UNSUPPORTED;
   }
   const bool f64 = pl->d.dtype == GCMF_F64, flux = pl->kind == K_FLUX;
+  if (pl->bank_n > 0) {   // inside gcmf_apply_bank: every entry its own polynomial (beside or after launch_ringc_bank's strips)
+    if (!backward || !f64 || !flux || pl->stacked || !pl->bank_rev || a.lvl < 1 || (size_t)(a.lvl - 1 + a.S) >= pl->bank_stride) {
+      set_error("k_fold_band (filter bank): not a backward launch of an ordinary f64 flux plan inside gcmf_apply_bank");
+      return GCMF_ERR_INVALID_ARG;
+    }
+    return wide ? launch_fb_nt<double, double, K_FLUX, true, 1024, true>(pl, a, s) : launch_fb_nt<double, double, K_FLUX, true, 256, true>(pl, a, s);
+  }
   if (backward) {
     if (f64) return flux ? launch_fb<double, double, K_FLUX, true>(pl, a, s, wide) : launch_fb<double, double, K_MASK, true>(pl, a, s, wide);
     return flux ? launch_fb<float, float, K_FLUX, true>(pl, a, s, wide) : launch_fb<float, float, K_MASK, true>(pl, a, s, wide);

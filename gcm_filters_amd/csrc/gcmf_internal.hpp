@@ -243,12 +243,12 @@ struct gcmf_plan {
   double *dev_p = nullptr;   // p[0..n_steps] of the last filter, for k_land_fix
   size_t dev_p_n = 0;
   std::vector<double> host_p;
-  // A FILTER BANK (gcmf_apply_bank; ordinary whole-grid f64 plans of the flux kinds without a seam): for the duration of such a call (the plan's mutex
+  // A FILTER BANK (gcmf_apply_bank; ordinary whole-grid f64 plans of the four flux-form grid types): for the duration of such a call (the plan's mutex
   // is held) bank_n polynomials of one degree are applied to bank_nfield fields -- entry e of the call is polynomial e / bank_nfield on
   // field e % bank_nfield, entry0 the first entry of the launch that runs now -- by the plain strips of the backward evaluation alone
-  // (ringc_march<..., PB>, k_land_fix<..., PB>), which read the polynomials from two grow-only tables of bank_stride doubles per row: bank_rev
-  // reversed (MultiP::ptab) and bank_fwd as given; bank_host is what both hold (bank_fwd's order).  The lock-free queries may see the
-  // call's values, as with mask_per_field.
+  // (ringc_march<..., PB>, k_land_fix<..., PB>; on TRIPOLAR_POP_WITH_LAND with k_fold_band<..., PB> on the seam's rows), which read the
+  // polynomials from two grow-only tables of bank_stride doubles per row: bank_rev reversed (MultiP::ptab, FoldBandP::ptab) and bank_fwd as
+  // given; bank_host is what both hold (bank_fwd's order).  The lock-free queries may see the call's values, as with mask_per_field.
   int bank_n = 0;
   int64_t bank_nfield = 1;
   double *bank_rev = nullptr, *bank_fwd = nullptr;

@@ -86,7 +86,8 @@ struct RingcCutIn {
   bool band_beside;      // k_fold_band runs BESIDE this launch (its waves must fit on the SIMDs next to these: no zip, no early exit)
   bool mask_per_field;   // GCMF_MASK_FROM_NAN: never packed
   int strip_rows, ringc_xe_rows, ringc_zip, zip_fold, pack_batch;   // the plan's options of these names
-  bool stacked = false;  // a stacked plan (gcmf_plan_create_levels): whole strips per entry in whole ring periods -- never zipped, packed or with early exits
+  bool stacked = false;  // a stacked plan (gcmf_plan_create_levels) or a filter bank (gcmf_apply_bank): whole strips per entry in whole ring periods --
+                         // never zipped (nor at the tripole seam: k_fold_band keeps it), packed or with early exits
 };
 
 struct RingcCut {
@@ -203,8 +204,9 @@ inline RingcCut ringc_cut(const RingcCutIn &in) {
   };
   if (in.seam) {
     // The tripole seam inside the launch (round 6): the f64 flux kind, a lane's two cells on one side of the row's centre, no packed batch
-    if (in.ringc_zip && in.zip_fold && in.f64 && flux && in.strip_rows <= 0 && S >= 5 && S <= 9 && (in.nx % 4) == 0 && in.nx >= 256 && nrows >= 24 &&
-        in.batch <= 64) {
+    // (stacked: never zipped -- a filter bank on a tripolar plan keeps k_fold_band, whose per-entry form advances the seam's rows)
+    if (!in.stacked && in.ringc_zip && in.zip_fold && in.f64 && flux && in.strip_rows <= 0 && S >= 5 && S <= 9 && (in.nx % 4) == 0 && in.nx >= 256 &&
+        nrows >= 24 && in.batch <= 64) {
       const Fold f = fold(in.nx, c.nwx, c.WI, in.batch, nrows, S);
       bool take = in.batch <= 1 || !in.pack_batch;
       if (!take && f.npmax >= 1) {

@@ -521,10 +521,18 @@ class Filter:
         return (u_filtered, v_filtered)
 
 
-def _bank_by_default(nbank: int, ny: int, nx: int) -> bool:
+def _bank_by_default(nbank: int, ny: int, nx: int, grid_type=None) -> bool:
     """Whether FilterBank takes the one-batch route where the library offers it and GCMF_FILTER_BANK does not say: wherever
     tools/measure_filter_bank.py measured it at least as fast as the loop over the scales beyond both spreads (README, "Filter banks")."""
+    if grid_type == GridType.TRIPOLAR_POP_WITH_LAND:
+        # measured (tools/measure_filter_bank.py --pop; README "One field at many scales"): 2 .. 32 scales on 384 x 320, 1080 x 1440 and
+        # 2400 x 3600, 56 and 63 steps -- the bank won every row beyond both spreads (20 % .. 92 % less time).  Between those rows the
+        # default goes by cells x scales; outside the measured range the loop stays the default (GCMF_FILTER_BANK=1 still asks for the bank)
+        return _POP_BANK_RANGE[0] <= int(nbank) * int(ny) * int(nx) <= _POP_BANK_RANGE[1]
     return True
+
+
+_POP_BANK_RANGE = (2 * 384 * 320, 32 * 2400 * 3600)      # cells x scales: the smallest and the largest measured row
 
 
 class FilterBank:
@@ -532,8 +540,9 @@ class FilterBank:
     ``dx_min``, grid, and ONE polynomial degree -- applied in one call (not in the reference, whose users loop over ``Filter`` objects).
 
     ``s_max`` does not depend on the filter scale, so the operator of every scale is the same and only the Chebyshev coefficients
-    differ: on float64 ``IRREGULAR_WITH_LAND`` / ``MOM5U`` / ``MOM5T`` grids the scales run as ONE batch of the backward evaluation with
-    a polynomial per entry (``gcmf_apply_bank``); everything else runs ``filters[j]`` one after the other.  Either way
+    differ: on float64 ``IRREGULAR_WITH_LAND`` / ``MOM5U`` / ``MOM5T`` / ``TRIPOLAR_POP_WITH_LAND`` grids the scales run as ONE batch of the
+    backward evaluation with a polynomial per entry (``gcmf_apply_bank``; on the tripolar grid the plain strips below the seam and
+    ``k_fold_band``'s per-entry form on its rows); everything else runs ``filters[j]`` one after the other.  Either way
     ``bank.apply(f)[j]`` is what ``bank.filters[j].apply(f)`` returns.
 
     Parameters
@@ -554,9 +563,10 @@ class FilterBank:
     filter_specs : list of FilterSpec
         Their FilterSpecs: the same ``n_steps``, ``s_max`` and ``dx_min_sq``, different ``p``
     last_route : {"bank", "loop", None}
-        Which route the last application took.  ``"bank"``: float64 data on the three grid types above with 2-D grid variables,
+        Which route the last application took.  ``"bank"``: float64 data on the four grid types above with 2-D grid variables,
         ``evaluation != "reference"``, more than one scale and a backward cut for the polynomial (``Plan.bank_cut``); ``"loop"``:
-        everything else.  ``GCMF_FILTER_BANK=0`` forces the loop, ``=1`` the bank wherever it is on offer.  At most
+        everything else -- and ``TRIPOLAR_POP_WITH_LAND`` outside the measured range of cells x scales (2 scales of 384 x 320 up to 32 of
+        2400 x 3600, ``_bank_by_default``).  ``GCMF_FILTER_BANK=0`` forces the loop, ``=1`` the bank wherever it is on offer.  At most
         ``GCMF_BANK_ENTRIES`` (64) entries -- scales x 2-D slices -- go into one library call, which bounds the device memory of a
         sweep: longer ones are cut over the scales, and over the leading axes of the field where those alone exceed the bound.
     """
@@ -623,7 +633,7 @@ class FilterBank:
                     and not issubclass(self.Laplacian, BaseVectorLaplacian))
         if eligible and want is None:
             shape = tuple(getattr(field, "shape", ()))
-            eligible = len(shape) >= 2 and _bank_by_default(len(self.filters), int(shape[-2]), int(shape[-1]))
+            eligible = len(shape) >= 2 and _bank_by_default(len(self.filters), int(shape[-2]), int(shape[-1]), self.grid_type)
         if eligible:
             with plan_cache_mode(self.plan_cache):
                 out = self._memo.get(args)._run_bank(field, self.filter_specs)

@@ -61,8 +61,9 @@ GAP_FOLD_GRID_TYPES = STACKED_GRID_TYPES
 STACK_LEVELS_ABOVE = 64
 
 # ... and the ones whose FILTER BANKS -- several polynomials of one degree on the same fields (FilterBank, gcmf_apply_bank) -- run as one
-# batch with a polynomial per entry; float64, 2-D grid variables and the default (backward) evaluation only
-BANK_GRID_TYPES = STACKED_GRID_TYPES
+# batch with a polynomial per entry; float64, 2-D grid variables and the default (backward) evaluation only.  TRIPOLAR_POP_WITH_LAND is one
+# of them (the plain strips below the tripole seam, k_fold_band's per-entry form on its rows) although it stacks no levels
+BANK_GRID_TYPES = STACKED_GRID_TYPES + (GridType.TRIPOLAR_POP_WITH_LAND,)
 # the most entries (polynomials x fields) of one gcmf_apply_bank call: a memory bound, not a tuned number -- an entry costs its output
 # plane plus the four state planes of the work buffer (GCMF_BANK_ENTRIES)
 BANK_ENTRIES = 64
@@ -785,6 +786,8 @@ class _DeviceLaplacian:
         """FilterBank's one-batch route: the polynomials of `specs` (one degree, one s_max) on every 2-D slice of `field` through
         gcmf_apply_bank; the result has shape (len(specs),) + field.shape and, slice by slice, the bits of _run with each spec.  None
         where the library has no bank for this Laplacian, data or polynomial (the caller then runs the specs one after the other).
+        The Laplacians of BANK_GRID_TYPES have one; what the polynomial is cut into is the library's answer (plan.bank_cut: launches of
+        5 .. 9 levels, 5 .. 8 on TRIPOLAR_POP_WITH_LAND, whose seam rows k_fold_band advances beside or after every strip launch).
         At most GCMF_BANK_ENTRIES entries per call: a longer sweep is cut over the polynomials, and over the fields where they alone
         exceed the bound; every call writes straight into the one output array.  A host array goes up through torch."""
         if self._glead is not None or self._NCOMP != 1 or self.GRID_TYPE not in BANK_GRID_TYPES or not self._planes:

@@ -231,22 +231,26 @@ int gcmf_apply(gcmf_plan *plan, const double *p, int n_steps, double c, const vo
  *     out[j * nfield + i] = the polynomial p[j * (n_steps + 1) .. (j + 1) * (n_steps + 1)) applied to in[i]      (j < nbank, i < nfield)
  * `p`: nbank x (n_steps + 1) host doubles, row-major.  `in`: (nfield, ny, nx) f64, `out`: (nbank, nfield, ny, nx) f64, device pointers
  * (GCMF_DEVICE_PTRS is required), which must not overlap.  `stream` as for gcmf_apply with device pointers.
- *   Scope: ordinary (not stacked) f64 plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T that cover the whole grid (no row slab, no
- *   GCMF_PLAN_SELF_RING), and a polynomial for which gcmf_bank_cut offers a cut -- anything else returns GCMF_ERR_UNSUPPORTED and names
+ *   Scope: ordinary (not stacked) f64 plans of IRREGULAR_WITH_LAND, MOM5U, MOM5T and TRIPOLAR_POP_WITH_LAND that cover the whole grid (no
+ *   row slab, no GCMF_PLAN_SELF_RING), and a polynomial for which gcmf_bank_cut offers a cut -- anything else returns GCMF_ERR_UNSUPPORTED and names
  *   the function and the limit: host pointers, an f32 plan, another grid type, a stacked plan, GCMF_FORWARD_RECURRENCE,
  *   GCMF_MASK_FROM_NAN, GCMF_FACES_FROM_NAN, GCMF_OUT_F32, fewer than five steps, nx not a multiple of 4 on a grid with land,
  *   GCMF_CLENSHAW=0.  GCMF_ERR_INVALID_ARG: nbank < 1, n_steps < 1, a null pointer, `in` overlapping `out`.  nfield = 0: GCMF_OK.
  *   The call runs the backward evaluation's plain strips with the nbank * nfield entries as the batch (k_ringc, one workgroup column per
  *   entry, every entry reading the coefficients of its own polynomial from a table on the device and the input plane of its own field)
  *   and k_land_fix in the same form; never the on-chip kernel, "single_launch", the packed walk, the zipped strips or the wet-row tables.
+ *   On a plan with the tripole seam (TRIPOLAR_POP_WITH_LAND) the strips stop S rows below the seam and k_fold_band, in the same per-entry
+ *   form and reading the same table, advances those rows beside or after EVERY strip launch (option "band_seq_cells" decides which, as for
+ *   gcmf_apply; gcmf_last_timing counts both launches); k_fold_band stops at eight levels, so the launches of such a plan run 5 .. 8.
  *   More than 32768 entries are cut into consecutive launches.  out[j, i] has the bits of
  *   gcmf_apply(plan, p_j, ..., in_i, nbatch = 1, GCMF_NO_RESIDENT) -- the backward result does not depend on how the levels or the
  *   strips are cut -- NaN, +-inf and land cells included.  The two coefficient tables live in the plan (grow-only, freed by
  *   gcmf_plan_destroy) and are uploaded only when `p` differs from the previous call's, after the stream has drained.
  *   gcmf_last_timing, gcmf_last_kernel and gcmf_plan_last_path (GCMF_PATH_STRIPS) work as after gcmf_apply; gcmf_last_kernel names the
  *   ordinary kernel (the launches are an instantiation of their own of it), gcmf_last_kernel_geometry appends " bank=<nbank>".
- * gcmf_bank_cut: the launch depths (5 .. 9 levels each) gcmf_apply_bank uses for a polynomial of n_steps steps and nentries = nbank *
- * nfield entries, written to depths[0 .. return value); 0 = a bank is not on offer for this plan / polynomial.
+ * gcmf_bank_cut: the launch depths (5 .. 9 levels each; 5 .. 8 on a plan with the tripole seam) gcmf_apply_bank uses for a polynomial of
+ * n_steps steps and nentries = nbank * nfield entries, written to depths[0 .. return value); 0 = a bank is not on offer for this plan /
+ * polynomial.  The answer is the same inside and outside a bank call.
  */
 extern int gcmf_apply_bank(gcmf_plan *plan, const double *p, int nbank, int n_steps, double c, const void *in, void *out, int64_t nfield,
                            uint32_t flags, void *stream);
