@@ -41,6 +41,8 @@ EXPORTS = [
 EXPORTS_LEVELS = ["gcmf_plan_create_levels", "gcmf_plan_levels"]
 # ... and of filter banks (gcmf_apply_bank): likewise
 EXPORTS_BANK = ["gcmf_apply_bank", "gcmf_bank_cut"]
+# ... and of filter banks on gappy fields (gcmf_apply_bank_gaps): likewise
+EXPORTS_BANK_GAPS = ["gcmf_apply_bank_gaps"]
 PATH_NAMES = {0: None, 1: "resident", 2: "strips", 3: "resident-lock-busy", 4: "resident-disabled"}
 RESIDENT_STATES = {0: "ok", 1: "lock-busy", 2: "disabled", 3: "off"}
 PLAN_SELF_RING, PLAN_SKIP_KAPPA_ONE = 0x1, 0x2
@@ -120,6 +122,8 @@ def load() -> C.CDLL:
         lib.gcmf_apply.restype = C.c_int
         lib.gcmf_apply_bank.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double, vp, vp, C.c_int64, C.c_uint32, vp]
         lib.gcmf_apply_bank.restype = C.c_int
+        lib.gcmf_apply_bank_gaps.argtypes = lib.gcmf_apply_bank.argtypes
+        lib.gcmf_apply_bank_gaps.restype = C.c_int
         lib.gcmf_bank_cut.argtypes = [vp, C.c_int, C.c_int64, C.POINTER(C.c_int), C.c_int]
         lib.gcmf_bank_cut.restype = C.c_int
         lib.gcmf_laplacian.argtypes = [vp, vpp, vpp, C.c_int64, C.c_uint32, vp]
@@ -367,17 +371,20 @@ class Plan:
                                 _ptr_array(ins), _ptr_array(outs), int(nbatch), flags, C.c_void_p(stream or None)))
 
     def apply_bank(self, p: np.ndarray, c: float, src: int, out: int, nfield: int, *, device_ptrs: bool = True, stream: int = 0,
-                   flags: int = 0):
+                   flags: int = 0, faces_from_nan: bool = False):
         """A filter bank (gcmf_apply_bank): the rows of `p`, (nbank, n_steps + 1), are polynomials of one degree; out[j, i] = row j
         applied to field i of `src` -- (nfield, ny, nx) and (nbank, nfield, ny, nx) float64 device pointers that do not overlap.
         Ordinary whole-grid float64 IRREGULAR_WITH_LAND / MOM5U / MOM5T / TRIPOLAR_POP_WITH_LAND plans with a backward cut (bank_cut); anything else raises
-        GcmfError(ERR_UNSUPPORTED).  flags: further GCMF_* bits (the library refuses all but GCMF_NO_RESIDENT)."""
+        GcmfError(ERR_UNSUPPORTED).  flags: further GCMF_* bits (the library refuses all but GCMF_NO_RESIDENT).
+        faces_from_nan: the bank on gappy fields (gcmf_apply_bank_gaps; IRREGULAR_WITH_LAND / MOM5U / MOM5T) -- field i is filtered with
+        wet_mask * [field i is not NaN] at every scale, its face coefficients folded once per field inside the call."""
         p = np.ascontiguousarray(p, dtype=np.float64)
         if p.ndim != 2:
             raise ValueError(f"apply_bank: p must be (nbank, n_steps + 1), not {p.shape}")
-        check(load().gcmf_apply_bank(self._h, p.ctypes.data_as(C.POINTER(C.c_double)), p.shape[0], p.shape[1] - 1, float(c),
-                                     C.c_void_p(src or None), C.c_void_p(out or None), int(nfield),
-                                     (DEVICE_PTRS if device_ptrs else 0) | int(flags), C.c_void_p(stream or None)))
+        fn = load().gcmf_apply_bank_gaps if faces_from_nan else load().gcmf_apply_bank
+        check(fn(self._h, p.ctypes.data_as(C.POINTER(C.c_double)), p.shape[0], p.shape[1] - 1, float(c),
+                 C.c_void_p(src or None), C.c_void_p(out or None), int(nfield),
+                 (DEVICE_PTRS if device_ptrs else 0) | int(flags), C.c_void_p(stream or None)))
 
     def bank_cut(self, n_steps: int, nentries: int = 1):
         """Launch depths gcmf_apply_bank uses for polynomials of n_steps steps and nbank * nfield = nentries entries ([] = no bank on

@@ -101,7 +101,8 @@ static int launch_ringc(gcmf_plan *pl, const MultiArgs &m, const RingcCut &cut, 
     case K_REG: return launch_ringc_reg(pl, m, cut, s);
     case K_MASK: return launch_ringc_maskz(pl, m, cut, s);
     case K_FLUX:
-      if (pl->bank_n > 0) return launch_ringc_bank(pl, m, cut, s);   // (gcmf_apply_bank: always the plain strips, ringc_cut)
+      // (gcmf_apply_bank, and gcmf_apply_bank_gaps on a plan that looks stacked meanwhile: always the plain strips, ringc_cut)
+      if (pl->bank_n > 0) return pl->stacked ? launch_ringc_bank_gaps(pl, m, cut, s) : launch_ringc_bank(pl, m, cut, s);
       if (pl->stacked) return launch_ringc_levels(pl, m, cut, s);   // (always the plain strips: ringc_cut)
       if (cut.xe) return launch_ringc_flux_slab(pl, m, cut, s);   // (k_ringcs, or k_ringcp's early-exit form)
       if (m.S == 9) return launch_ringc_flux9(pl, m, cut, s);
@@ -532,7 +533,8 @@ struct GapFaces {
   const uint8_t *lbits;
   int64_t n_land, nlev, entry0;
   bool stacked;
-  GapFaces(gcmf_plan *p, const double *cE, const double *cN, const double *ra, const uint8_t *bits, int64_t nbatch)
+  // keep_entry0 (gcmf_apply_bank_gaps: the levels are the call's FIELDS, nbatch of them, and the launch's first entry is entry0 of the call)
+  GapFaces(gcmf_plan *p, const double *cE, const double *cN, const double *ra, const uint8_t *bits, int64_t nbatch, bool keep_entry0 = false)
       : pl(p), lbits(p->lbits), n_land(p->n_land), nlev(p->nlev), entry0(p->entry0), stacked(p->stacked) {
     for (int k = 0; k < 3; ++k) coef[k] = pl->g.coef[k];
     pl->g.coef[0] = cE; pl->g.coef[1] = cN; pl->g.coef[2] = ra;
@@ -540,7 +542,7 @@ struct GapFaces {
     pl->n_land = std::max<int64_t>(1, n_land);
     pl->stacked = true;
     pl->nlev = nbatch;
-    pl->entry0 = 0;
+    if (!keep_entry0) pl->entry0 = 0;
   }
   ~GapFaces() {
     for (int k = 0; k < 3; ++k) pl->g.coef[k] = coef[k];
@@ -847,7 +849,8 @@ static int run_schedule(ApplyCtx &x, uint32_t flags, bool use_multi, bool use_vm
       rc = sched_backward_scalar(x, depths, n_clen, was_clean);
     if (rc || pl->n_land == 0) return rc;
     // the isolated cells' own polynomial (forward recurrence, as the reference computes it)
-    if (pl->bank_n > 0) return launch_land_fix_bank(pl, x.din[0], x.dout[0], x.n_steps, x.c, x.nbatch, x.s);   // (every entry its own)
+    // (every entry its own; gcmf_apply_bank_gaps: on the land bytes of its own field too -- the launcher looks at pl->stacked)
+    if (pl->bank_n > 0) return launch_land_fix_bank(pl, x.din[0], x.dout[0], x.n_steps, x.c, x.nbatch, x.s);
     return land_fix_tail(pl, x.p, x.n_steps, x.c, x.din[0], x.dout[0], x.fb32, x.nbatch, x.s);
   }
   if (use_multi) return sched_forward_scalar(x);
@@ -954,7 +957,11 @@ static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double 
   const size_t oM = per; if (from_nan) per += align_up(ncell, 256);   // the entries' own mask bytes
   // GCMF_FACES_FROM_NAN (run_whole has checked the plan and cut the batch to the scratch bound): the entries' own cE, cN, ra and land bytes
   const bool faces = flags & GCMF_FACES_FROM_NAN;
-  const size_t szG = align_up(ncell * 8 + 256, 256), szL = align_up(ncell + 256, 256);   // (padded as precompute_levels pads a stacked plan's)
+  // (inside gcmf_apply_bank_gaps: the FIELDS' own planes, bank_nfield of them whatever the launch's entries)
+  const bool bank_faces = faces && pl->bank_n > 0;
+  const int64_t nfold = bank_faces ? pl->bank_nfield : nbatch;
+  const size_t nface = (size_t)nfold * pl->d.ny * pl->d.nx;
+  const size_t szG = align_up(nface * 8 + 256, 256), szL = align_up(nface + 256, 256);   // (padded as precompute_levels pads a stacked plan's)
   const size_t oG = per; if (faces) per += 3 * szG + szL;
   int rc = ensure_work(pl, per * pl->ncomp);
   if (rc || (rc = wait_for_work(pl, x.s))) return rc;
@@ -992,15 +999,20 @@ static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double 
     double *cEb = (double *)(w + oG), *cNb = (double *)(w + oG + szG), *rab = (double *)(w + oG + 2 * szG);
     uint8_t *bits = (uint8_t *)(w + oG + 3 * szG);
     const double *cE = (const double *)pl->g.coef[0], *cN = (const double *)pl->g.coef[1], *ra = (const double *)pl->g.coef[2];
-    GapFaces own(pl, cEb, cNb, rab, bits, nbatch);
+    GapFaces own(pl, cEb, cNb, rab, bits, nfold, bank_faces);
     int depths[1024];   // (asked with the guard in place: the answer run_schedule will get)
     if (!use_multi || clenshaw_cut(pl, n_steps, depths, 1024, false, nbatch) <= 0) {
       set_error("%s; for this plan and a polynomial of %d steps the stacked strips offer no backward cut (gcmf_clenshaw_cut_batch: fewer than "
-                "five steps, nx not a multiple of 4, GCMF_CLENSHAW=0 ...): filter with a plan built from wet_mask * [not NaN]", FACES_WHERE, n_steps);
+                "five steps, nx not a multiple of 4, GCMF_CLENSHAW=0 ...): filter with a plan built from wet_mask * [not NaN]",
+                bank_faces ? "gcmf_apply_bank_gaps" : FACES_WHERE, n_steps);
       return GCMF_ERR_UNSUPPORTED;
     }
-    if ((rc = launch_gap_fold(pl, cE, cN, ra, x.din[0], cEb, cNb, rab, bits, nbatch, x.s))) return rc;
-    ++x.launches;
+    // (a bank: one fold per FIELD -- a later launch of the same call that finds the same fields folded at the same place folds nothing)
+    if (!(bank_faces && pl->gap_fold_at == (const void *)cEb && pl->gap_fold_in == x.din[0] && pl->gap_fold_n == nfold)) {
+      if ((rc = launch_gap_fold(pl, cE, cN, ra, x.din[0], cEb, cNb, rab, bits, nfold, x.s))) return rc;
+      ++x.launches;
+      if (bank_faces) { pl->gap_fold_at = cEb; pl->gap_fold_in = x.din[0]; pl->gap_fold_n = nfold; }
+    }
     if ((rc = run_schedule(x, flags, use_multi, use_vmulti))) return rc;
     return finish_call(x, on_dev, out, ncell * fbs, timing, timed);
   }
@@ -1308,6 +1320,116 @@ int gcmf_apply_bank(gcmf_plan *pl, const double *p, int nbank, int n_steps, doub
     if ((rc = run_whole_locked(pl, p, n_steps, c, in1, out1, nb, (flags & GCMF_DEVICE_PTRS) | GCMF_NO_RESIDENT, stream, false, true))) return rc;
     ms_total += pl->last_ms;
     launches += pl->last_launches;
+  }
+  pl->last_ms = ms_total;
+  pl->last_launches = launches;
+  return GCMF_OK;
+}
+
+// A filter bank on gappy fields: gcmf_apply_bank's launches on the planes GCMF_FACES_FROM_NAN folds -- once per FIELD.  While a launch runs
+// the plan carries both guards: the bank's (bank_n, bank_nfield, entry0; here) and GapFaces with nlev = the launch's fields
+// (run_whole_locked), and launch_ringc / run_schedule pick the forms that know both axes.
+int gcmf_apply_bank_gaps(gcmf_plan *pl, const double *p, int nbank, int n_steps, double c, const void *in, void *out, int64_t nfield,
+                         uint32_t flags, void *stream) {
+  if (!pl || !p || !in || !out) {
+    set_error("gcmf_apply_bank_gaps: null argument");
+    return GCMF_ERR_INVALID_ARG;
+  }
+  if (nbank < 1 || n_steps < 1 || nfield < 0) {
+    set_error("gcmf_apply_bank_gaps: %d polynomials of %d steps on %lld fields (at least one polynomial of at least one step)", nbank, n_steps, (long long)nfield);
+    return GCMF_ERR_INVALID_ARG;
+  }
+  const int gt = pl->d.grid_type;
+  const bool kind_ok = gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T;
+  const char *why = gt == GCMF_TRIPOLAR_POP_WITH_LAND ? "TRIPOLAR_POP_WITH_LAND, whose gap fold is not offered" : !kind_ok ? "another grid type" :
+                    pl->d.dtype != GCMF_F64 ? "an f32 plan" : (pl->d.flags & GCMF_PLAN_SELF_RING) ? "GCMF_PLAN_SELF_RING" : !pl->full ? "a row slab" :
+                    pl->stacked ? "a stacked plan (gcmf_plan_create_levels)" : !(flags & GCMF_DEVICE_PTRS) ? "host pointers (GCMF_DEVICE_PTRS is required)" :
+                    (flags & GCMF_FORWARD_RECURRENCE) ? "GCMF_FORWARD_RECURRENCE" : (flags & GCMF_MASK_FROM_NAN) ? "GCMF_MASK_FROM_NAN" :
+                    (flags & GCMF_OUT_F32) ? "GCMF_OUT_F32" : nullptr;
+  if (why) {
+    set_error("gcmf_apply_bank_gaps: filter banks on gappy fields run on ordinary whole-grid f64 plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T with device "
+              "pointers, backwards and into f64 (%s; grid type %d): call gcmf_apply with GCMF_FACES_FROM_NAN once per polynomial", why, gt);
+    return GCMF_ERR_UNSUPPORTED;
+  }
+  const size_t cell = (size_t)pl->d.ny * pl->d.nx;
+  if ((int64_t)nbank * nfield > (int64_t)2000000000) {
+    set_error("gcmf_apply_bank_gaps: %d polynomials x %lld fields: at most 2e9 entries per call", nbank, (long long)nfield);
+    return GCMF_ERR_INVALID_ARG;
+  }
+  const int64_t nent = (int64_t)nbank * nfield;
+  {
+    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (size_t)nfield * cell * 8, o0 = (uintptr_t)out, o1 = o0 + (size_t)nent * cell * 8;
+    if ((nfield > 0 && i0 < o1 && o0 < i1) || in == out) {   // the fold, every launch and k_land_fix read the input
+      set_error("gcmf_apply_bank_gaps: `out` must not overlap `in` (filtering in place is not supported)");
+      return GCMF_ERR_INVALID_ARG;
+    }
+  }
+  int depths[1024];
+  // (the folded planes always have land -- the gaps -- so what a plan without land may skip is needed here: land_ok)
+  if ((pl->d.nx % 4) != 0 || !pl->zero_land || n_steps >= 4096 || bank_cut(pl, n_steps, std::max<int64_t>(1, nent), depths, 1024) <= 0) {
+    set_error("gcmf_apply_bank_gaps: for this plan and a polynomial of %d steps the plain strips offer no backward cut (gcmf_bank_cut returns 0: fewer "
+              "than five steps, GCMF_CLENSHAW=0 ...; or nx = %lld is not a multiple of 4, 4096 steps or more, GCMF_ZERO_LAND=0): call gcmf_apply with "
+              "GCMF_FACES_FROM_NAN once per polynomial", n_steps, (long long)pl->d.nx);
+    return GCMF_ERR_UNSUPPORTED;
+  }
+  if (nfield == 0) return GCMF_OK;
+  std::lock_guard<std::mutex> lk(pl->mu);
+  GCMF_HIP(hipSetDevice(pl->d.device));
+  int rc = ensure_bank_tables(pl, p, nbank, n_steps, (hipStream_t)stream);
+  if (rc) return rc;
+  struct Bank {   // (put back however the call leaves)
+    gcmf_plan *pl;
+    double *rev, *fwd;
+    ~Bank() {
+      pl->bank_n = 0; pl->bank_nfield = 1; pl->entry0 = 0;
+      pl->bank_rev = rev; pl->bank_fwd = fwd;
+      pl->gap_fold_at = pl->gap_fold_in = nullptr; pl->gap_fold_n = 0;
+    }
+  } guard{pl, pl->bank_rev, pl->bank_fwd};
+  pl->gap_fold_at = pl->gap_fold_in = nullptr;
+  pl->gap_fold_n = 0;
+  const uint32_t rflags = GCMF_DEVICE_PTRS | GCMF_NO_RESIDENT | GCMF_FACES_FROM_NAN;
+  // the fields one launch may carry: their own planes (25 bytes per cell and field) at or under option "gap_scratch_mb", at least one
+  const long long bound = (long long)std::max(0, pl->gap_scratch_mb) << 20, per_field = 25LL * pl->d.ny * pl->d.nx;
+  const int64_t run_nf = std::max<int64_t>(1, std::min<int64_t>(MAX_LAUNCH_BATCH, bound / per_field));
+  float ms_total = 0.f;
+  int launches = 0;
+  if (nfield <= run_nf) {
+    // All fields at once: the entries as gcmf_apply_bank cuts them.  A launch that starts at entry e0 of the call has entry0 = e0, so the
+    // plan's lev0 = entry0 % nlev = e0 % nfield (ringc_params; nlev = nfield under GapFaces, which keeps entry0 here) and the kernel's level
+    // (lev0 + y) % nlev = (e0 % nfield + y) % nfield = (e0 + y) % nfield: the field of entry e0 + y, also when e0 = k * MAX_LAUNCH_BATCH is
+    // no multiple of nfield.  k_land_fix takes the field from ent0 = entry0 itself.  Every such launch finds its work layout at another
+    // place (its batch differs from the previous one's or the fields are folded already), so the fold is repeated only where it must be.
+    pl->bank_n = nbank;
+    pl->bank_nfield = nfield;
+    for (int64_t e0 = 0; e0 < nent; e0 += MAX_LAUNCH_BATCH) {
+      const int64_t nb = std::min<int64_t>(nent - e0, MAX_LAUNCH_BATCH);
+      const void *in1[2] = {in, nullptr};
+      void *out1[2] = {(char *)out + (size_t)e0 * cell * 8, nullptr};
+      pl->entry0 = e0;
+      if ((rc = run_whole_locked(pl, p, n_steps, c, in1, out1, nb, rflags, stream, false, true))) return rc;
+      ms_total += pl->last_ms;
+      launches += pl->last_launches;
+    }
+  } else {
+    // The fields in runs that fit the bound; per run and polynomial one bank of ONE polynomial -- the table's row base, `in` and `out` moved
+    // here, on the host -- over the run's fields: the same kernels on the same operands, and the run is folded once (gap_fold_*: the
+    // launches of a run have one work layout).
+    for (int64_t f0 = 0; f0 < nfield; f0 += run_nf) {
+      const int64_t nf = std::min<int64_t>(nfield - f0, run_nf);
+      pl->bank_n = 1;
+      pl->bank_nfield = nf;
+      pl->entry0 = 0;
+      for (int j = 0; j < nbank; ++j) {
+        pl->bank_rev = guard.rev + (size_t)j * pl->bank_stride;
+        pl->bank_fwd = guard.fwd + (size_t)j * pl->bank_stride;
+        const void *in1[2] = {(const char *)in + (size_t)f0 * cell * 8, nullptr};
+        void *out1[2] = {(char *)out + ((size_t)j * nfield + f0) * cell * 8, nullptr};
+        if ((rc = run_whole_locked(pl, p + (size_t)j * pl->bank_stride, n_steps, c, in1, out1, nf, rflags, stream, false, true))) return rc;
+        ms_total += pl->last_ms;
+        launches += pl->last_launches;
+      }
+    }
   }
   pl->last_ms = ms_total;
   pl->last_launches = launches;

@@ -254,6 +254,13 @@ struct gcmf_plan {
   double *bank_rev = nullptr, *bank_fwd = nullptr;
   size_t bank_cap = 0, bank_stride = 0;   // doubles each table holds; doubles per row
   std::vector<double> bank_host;
+  // A filter bank on GAPPY fields (gcmf_apply_bank_gaps; the three flux-form grid types without a seam): while a launch runs the plan carries
+  // BOTH guards -- GapFaces with nlev = bank_nfield (one folded level per FIELD, entry0 kept: lev0 = entry0 % nlev is the field of the launch's
+  // first entry) and the bank's bank_n / bank_nfield / entry0 -- and launch_ringc / run_schedule take the forms that know both axes
+  // (launch_ringc_bank_gaps, k_land_fix<.., LV, PB>).  The fold is per field, so consecutive launches of one call that find the same fields
+  // folded at the same place in the work buffer (gap_fold_*; cleared when the call begins and leaves) do not fold again.
+  const void *gap_fold_in = nullptr, *gap_fold_at = nullptr;
+  int64_t gap_fold_n = 0;
   std::mutex mu;
 };
 
@@ -296,6 +303,7 @@ int launch_ringc_flux(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hi
 int launch_ringc_flux9(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // nine levels: whole f64 flux grids without a seam (gcmf_ringc_flux9.hip)
 int launch_ringc_levels(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // a stacked plan's plain strips (gcmf_ringc_levels.hip)
 int launch_ringc_bank(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // a filter bank's plain strips (gcmf_ringc_bank.hip)
+int launch_ringc_bank_gaps(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // ... over per-field planes (gcmf_apply_bank_gaps; gcmf_ringc_bank_gaps.hip)
 int launch_ringc_flux_slab(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // no seam's band beside, short strips: early exits (k_ringcs)
 int launch_ringc_flux_slab_f32(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
 int launch_ringc_zip(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // f64 flux plans: pairs of strips zipped at a shared seam, fold strips at the tripole seam (k_ringcz, gcmf_ringc_zip.hip)

@@ -15,6 +15,8 @@ namespace gcmf {
 // PB: a filter bank (gcmf_apply_bank) -- blockIdx.y is the launch's entry, entry e = ent0 + blockIdx.y is row e / nfield of the table p
 // (n_steps + 1 doubles per row) on field e % nfield of `in`, its result the launch's plane blockIdx.y of `out`; per_field = nfield,
 // ntotal = ncell (a workgroup stays inside one entry: one polynomial in its LDS), lbits the plan's one plane.  An instantiation of its own.
+// LV and PB: a filter bank over per-field planes (gcmf_apply_bank_gaps) -- PB's form with the land bytes of the entry's own FIELD, plane
+// e % nfield of lbits (a gap is land in its own field's plane: it comes out NaN, the input's own value).
 template <typename T, typename FB, bool FUSED, bool LV = false, bool PB = false>
 __global__ __launch_bounds__(256) void k_land_fix(const T *in, FB *out, const uint8_t *lbits, const T *area,
                                                   const double *p, int n_steps, double c_, long long ncell,
@@ -25,6 +27,7 @@ __global__ __launch_bounds__(256) void k_land_fix(const T *in, FB *out, const ui
     p += (long long)pol * (n_steps + 1);
     in += (long long)(e - pol * per_field) * ncell;
     out += (long long)blockIdx.y * ncell;
+    if constexpr (LV) lbits += (long long)(e - pol * per_field) * ncell;
   }
   for (int k = threadIdx.x; k <= n_steps; k += blockDim.x) sp[k] = p[k];
   __syncthreads();
@@ -34,8 +37,8 @@ __global__ __launch_bounds__(256) void k_land_fix(const T *in, FB *out, const ui
   for (long long q4 = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * 4; q4 < ntotal; q4 += (long long)gridDim.x * blockDim.x * 4) {
     const long long cell = q4 % ncell;
     unsigned m;
-    if constexpr (LV) m = *reinterpret_cast<const unsigned *>(lbits + (((per_field >> 16) + q4 / ncell) % (per_field & 0xFFFF)) * ncell + cell);
-    else if constexpr (PB) m = *reinterpret_cast<const unsigned *>(lbits + q4);
+    if constexpr (PB) m = *reinterpret_cast<const unsigned *>(lbits + q4);
+    else if constexpr (LV) m = *reinterpret_cast<const unsigned *>(lbits + (((per_field >> 16) + q4 / ncell) % (per_field & 0xFFFF)) * ncell + cell);
     else m = *reinterpret_cast<const unsigned *>(lbits + (per_field ? q4 : cell));   // (per_field: every entry its own plane of bytes)
     if ((m & 0x01010101u) == 0x01010101u) continue;
     T xm2[4], xm1[4];
@@ -153,9 +156,10 @@ static int launch_lf(gcmf_plan *pl, const void *in, void *out, const double *dp,
 }
 
 int launch_land_fix_bank(gcmf_plan *pl, const void *in, void *out, int n_steps, double c, int64_t nbatch, hipStream_t s) {
-  if (pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || pl->stacked || pl->area_weighted || pl->bank_n < 1 || !pl->bank_fwd ||
+  // (a plan that looks stacked: gcmf_apply_bank_gaps, one plane of land bytes per field)
+  if (pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || (pl->stacked && pl->nlev != pl->bank_nfield) || pl->area_weighted || pl->bank_n < 1 || !pl->bank_fwd ||
       pl->bank_stride != (size_t)n_steps + 1 || nbatch < 1 || nbatch > 65535 || (pl->d.nx % 4) != 0) {
-    set_error("k_land_fix (filter bank): not an ordinary f64 flux plan inside gcmf_apply_bank");
+    set_error("k_land_fix (filter bank): not an ordinary f64 flux plan inside gcmf_apply_bank / gcmf_apply_bank_gaps");
     return GCMF_ERR_INVALID_ARG;
   }
   const long long ncell = (long long)pl->rows_alloc * pl->d.nx;
@@ -163,8 +167,12 @@ int launch_land_fix_bank(gcmf_plan *pl, const void *in, void *out, int n_steps, 
   if (nb > 32768) nb = 32768;
   dim3 block(256), grid((unsigned)nb, (unsigned)nbatch);
   const size_t lds = ((size_t)n_steps + 1) * sizeof(double);
-  hipLaunchKernelGGL((k_land_fix<double, double, true, false, true>), grid, block, lds, s, (const double *)in, (double *)out, pl->lbits, (const double *)nullptr,
-                     pl->bank_fwd, n_steps, c, ncell, ncell, (int)pl->bank_nfield, (int)pl->entry0);
+  if (pl->stacked)
+    hipLaunchKernelGGL((k_land_fix<double, double, true, true, true>), grid, block, lds, s, (const double *)in, (double *)out, pl->lbits, (const double *)nullptr,
+                       pl->bank_fwd, n_steps, c, ncell, ncell, (int)pl->bank_nfield, (int)pl->entry0);
+  else
+    hipLaunchKernelGGL((k_land_fix<double, double, true, false, true>), grid, block, lds, s, (const double *)in, (double *)out, pl->lbits, (const double *)nullptr,
+                       pl->bank_fwd, n_steps, c, ncell, ncell, (int)pl->bank_nfield, (int)pl->entry0);
   GCMF_HIP(hipGetLastError());
   return GCMF_OK;
 }

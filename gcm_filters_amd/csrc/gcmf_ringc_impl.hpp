@@ -69,6 +69,9 @@ template <bool ZIP> constexpr bool ringc_ramp_on(int t, int ph) { return ZIP ? (
 // own, and the coefficients of the launch's levels come from row e / nfield of a table in device memory (MultiP::ptab) instead of from the
 // kernel arguments -- wave-uniform addresses read once per march through the constant address space (scalar loads into scalar registers,
 // where the kernel arguments' P.pk[] live too).  Like PF, LV and XO an instantiation of its own.
+// PB and LV TOGETHER: a filter bank over per-field planes (gcmf_apply_bank_gaps) -- the launcher sets nlev = nfield and lev0 = ent0 % nfield,
+// so LV's level (lev0 + blockIdx.y) % nlev = (ent0 + blockIdx.y) % nfield is PB's field index: entry e marches with row e / nfield of the table
+// on the input plane, the coefficient planes and the land bytes of field e % nfield.  Both halves as they are; an instantiation of its own.
 template <typename T, int KIND, int S, bool FIRST, bool SANI, bool XE = false, bool ZIP = false, bool PF = false, bool LV = false, bool XO = false,
           bool PB = false>
 __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx, const int a, const int b, const long long boff, const bool odd,
@@ -84,7 +87,7 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
   static_assert(!ZIP || FLUX, "the seam exchange is the flux kinds' (a carried face flux per level)");
   static_assert(!LV || (FLUX && !ZIP && !PF), "stacked plans: the flux kinds' plain strips");
   static_assert(!XO || ZIP, "a window origin per pair: k_ringcz's table launches");
-  static_assert(!PB || (FLUX && sizeof(T) == 8 && !ZIP && !XE && !PF && !LV), "filter banks: the f64 flux kinds' plain strips of an ordinary plan");
+  static_assert(!PB || (FLUX && sizeof(T) == 8 && !ZIP && !XE && !PF), "filter banks: the f64 flux kinds' plain strips");
   constexpr bool WATCH = (KIND != K_REG) && !SANI;  // K_REG has no nan_to_num in the reference: NaN spreads by plain arithmetic
   constexpr bool FUSED = true;   // nothing here is bit-identical with numpy anyway: every multiply-add pair is one fma
 
@@ -625,14 +628,16 @@ __device__ __forceinline__ void ringc_walk(const MultiP<T, T> &P, const int wid)
 // PF and LV TOGETHER (neither means anything beside the other: a plane of mask bytes per entry is the land-mask kinds', a level axis the flux
 // kinds') name the filter bank's form, ringc_march<PB>: the kernel keeps its six template arguments, and with them the names of all its
 // other instantiations
+// PF ALONE on the flux kinds (which have no mask bytes) names the bank over per-field planes, ringc_march<PB, LV> (gcmf_apply_bank_gaps)
 template <typename T, int KIND, int S, bool FIRST, bool PF = false, bool LV = false>
 __global__ __launch_bounds__(256, 1) void k_ringc(const MultiP<T, T> P) {
   int bx = blockIdx.x;
   if (P.xcd_per > 0 && bx < 8 * P.xcd_per) bx = (bx & 7) * P.xcd_per + (bx >> 3);
   const int wid = bx * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if (wid >= P.nwaves) return;
-  constexpr bool PB = PF && LV;
-  ringc_walk<T, KIND, S, FIRST, false, false, PF && !PB, LV && !PB, PB>(P, wid);
+  constexpr bool PBL = (KIND == K_FLUX) && PF && !LV;
+  constexpr bool PB = (PF && LV) || PBL;
+  ringc_walk<T, KIND, S, FIRST, false, false, PF && !PB, (LV && !PB) || PBL, PB>(P, wid);
 }
 
 // ... and for packed batches (ringc_walk<PACK>): XE = the early-exit form of the flux kinds (k_ringcs)
@@ -925,6 +930,31 @@ static int launch_ringc_bank_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCu
   GCMF_HIP(hipGetLastError());
   note_kernel(pl, std::string("gcmf::k_ringc<double, ") + std::to_string((int)K_FLUX) + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
               launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " bank=" + std::to_string(pl->bank_n));
+  return GCMF_OK;
+}
+
+// a filter bank over per-field planes (gcmf_apply_bank_gaps: the plan looks stacked, one level per field, while the bank runs):
+// k_ringc<double, K_FLUX, S, FIRST, true, false>; reported under the ordinary kernel's name with " levels=<nfield> bank=<nbank>" behind the geometry
+template <int S, bool FIRST>
+static int launch_ringc_bank_gaps_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+  if (cut.form != RINGC_PLAIN || cut.xe || pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || !pl->stacked || pl->bank_n < 1 || !pl->bank_rev ||
+      pl->nlev != pl->bank_nfield || pl->g.fold || a.lvl < 1 || (size_t)(a.lvl - 1 + S) >= pl->bank_stride) {
+    set_error("k_ringc (filter bank over per-field planes): the cut is not the plain strips of an f64 flux plan without a seam inside gcmf_apply_bank_gaps");
+    return GCMF_ERR_INVALID_ARG;
+  }
+  MultiP<double, double> P;
+  ringc_params(P, pl, a, cut);   // (lev0 = entry0 % nlev: the field of the launch's first entry)
+  P.ptab = pl->bank_rev;
+  P.pstride = (int)pl->bank_stride;
+  P.poff = a.lvl - 1;
+  P.nfield = (int)pl->bank_nfield;
+  P.ent0 = (int)pl->entry0;
+  const int nrows = a.row_hi - a.row_lo;
+  dim3 block(256), grid(cut.grid_x, cut.grid_y);
+  hipLaunchKernelGGL((k_ringc<double, K_FLUX, S, FIRST, true, false>), grid, block, 0, s, P);
+  GCMF_HIP(hipGetLastError());
+  note_kernel(pl, std::string("gcmf::k_ringc<double, ") + std::to_string((int)K_FLUX) + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
+              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " levels=" + std::to_string((long long)pl->nlev) + " bank=" + std::to_string(pl->bank_n));
   return GCMF_OK;
 }
 

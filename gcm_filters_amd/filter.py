@@ -195,6 +195,20 @@ def _create_filter_func(filter_spec: FilterSpec, Laplacian, evaluation: str = "a
     return filter_func
 
 
+def _check_nan_mask(nan_mask, grid_type):
+    """Filter's (and FilterBank's) check of ``nan_mask`` against the grid type."""
+    if isinstance(nan_mask, str):
+        if nan_mask != "auto":
+            raise ValueError(f'nan_mask must be False, True or "auto", not {nan_mask!r}')
+        if grid_type not in NAN_MASK_GRID_TYPES + GAP_FOLD_GRID_TYPES:
+            raise ValueError(f'nan_mask="auto" needs one of the grid types '
+                             f"{', '.join(g.name for g in NAN_MASK_GRID_TYPES + GAP_FOLD_GRID_TYPES)}, "
+                             f"not {getattr(grid_type, 'name', grid_type)}")
+    elif nan_mask and grid_type not in NAN_MASK_GRID_TYPES:
+        raise ValueError(f"nan_mask=True needs one of the grid types {', '.join(g.name for g in NAN_MASK_GRID_TYPES)}, "
+                         f"not {getattr(grid_type, 'name', grid_type)}")
+
+
 def _create_filter_func_vec(filter_spec: FilterSpec, Laplacian, evaluation: str = "auto", plan_cache=None):
     """Returns ``filter_func_vec(u, v, *grid_args) -> (u_filtered, v_filtered)``."""
     forward = _forward_only(evaluation)
@@ -355,16 +369,7 @@ class Filter:
         _forward_only(self.evaluation)   # ValueError for anything else
         if self.plan_cache is not None and self.plan_cache not in PLAN_CACHE_MODES:
             raise ValueError(f"plan_cache must be one of {PLAN_CACHE_MODES} or None, not {self.plan_cache!r}")
-        if isinstance(self.nan_mask, str):
-            if self.nan_mask != "auto":
-                raise ValueError(f'nan_mask must be False, True or "auto", not {self.nan_mask!r}')
-            if self.grid_type not in NAN_MASK_GRID_TYPES + GAP_FOLD_GRID_TYPES:
-                raise ValueError(f'nan_mask="auto" needs one of the grid types '
-                                 f"{', '.join(g.name for g in NAN_MASK_GRID_TYPES + GAP_FOLD_GRID_TYPES)}, "
-                                 f"not {getattr(self.grid_type, 'name', self.grid_type)}")
-        elif self.nan_mask and self.grid_type not in NAN_MASK_GRID_TYPES:
-            raise ValueError(f"nan_mask=True needs one of the grid types {', '.join(g.name for g in NAN_MASK_GRID_TYPES)}, "
-                             f"not {getattr(self.grid_type, 'name', self.grid_type)}")
+        _check_nan_mask(self.nan_mask, self.grid_type)
         self._reject_bad_arguments()
         self.n_steps = self._choose_n_steps()
         self.filter_spec = _compute_filter_spec(self.filter_scale, self.dx_min, self.filter_shape, self.transition_width,
@@ -532,6 +537,10 @@ def _bank_by_default(nbank: int, ny: int, nx: int, grid_type=None) -> bool:
     return True
 
 
+# FilterBank(nan_mask="auto") on the flux-form kinds: whether the one-batch route (gcmf_apply_bank_gaps) is the default, by the rule of
+# DESIGN.md 6 -- only where it was measured faster than the loop beyond both spreads (tools/measure_filter_bank.py --gaps)
+_GAPS_BANK_BY_DEFAULT = True
+
 _POP_BANK_RANGE = (2 * 384 * 320, 32 * 2400 * 3600)      # cells x scales: the smallest and the largest measured row
 
 
@@ -554,6 +563,11 @@ class FilterBank:
         instead (with ``Filter``'s warning when it is below that largest default)
     dx_min, filter_shape, transition_width, ndim, grid_type, grid_vars, evaluation, plan_cache
         As for ``Filter``, validated as ``Filter`` validates them
+    nan_mask : bool or "auto", keyword only
+        As for ``Filter`` (same values, same grid types, same messages), handed to every ``filters[j]``: every 2-D slice is filtered with
+        ``wet_mask * notnull(slice)`` at every scale.  ``"auto"`` on float64 ``IRREGULAR_WITH_LAND`` / ``MOM5U`` / ``MOM5T`` has a one-batch
+        route of its own (``gcmf_apply_bank_gaps``: the slices' face coefficients folded once per slice, not once per scale and slice;
+        needs ``nx % 4 == 0``); ``True`` / ``"auto"`` on the three land-mask kinds run the filters one after the other.
 
     Attributes
     ----------
@@ -566,16 +580,16 @@ class FilterBank:
         Which route the last application took.  ``"bank"``: float64 data on the four grid types above with 2-D grid variables,
         ``evaluation != "reference"``, more than one scale and a backward cut for the polynomial (``Plan.bank_cut``); ``"loop"``:
         everything else -- and ``TRIPOLAR_POP_WITH_LAND`` outside the measured range of cells x scales (2 scales of 384 x 320 up to 32 of
-        2400 x 3600, ``_bank_by_default``).  ``GCMF_FILTER_BANK=0`` forces the loop, ``=1`` the bank wherever it is on offer.  At most
+        2400 x 3600, ``_bank_by_default``) and whatever ``nan_mask`` sends there.  ``GCMF_FILTER_BANK=0`` forces the loop, ``=1`` the bank wherever it is on offer.  At most
         ``GCMF_BANK_ENTRIES`` (64) entries -- scales x 2-D slices -- go into one library call, which bounds the device memory of a
         sweep: longer ones are cut over the scales, and over the leading axes of the field where those alone exceed the bound.
     """
 
     def __init__(self, filter_scales, dx_min, filter_shape=FilterShape.GAUSSIAN, transition_width=np.pi, ndim=2, n_steps=0,
-                 grid_type=GridType.REGULAR, grid_vars=None, *, evaluation="auto", plan_cache=None):
+                 grid_type=GridType.REGULAR, grid_vars=None, *, evaluation="auto", plan_cache=None, nan_mask=False):
         self.dx_min, self.filter_shape, self.transition_width, self.ndim = dx_min, filter_shape, transition_width, ndim
         self.grid_type, self.grid_vars = grid_type, dict(grid_vars or {})
-        self.evaluation, self.plan_cache = evaluation, plan_cache
+        self.evaluation, self.plan_cache, self.nan_mask = evaluation, plan_cache, nan_mask
         self.Laplacian = ALL_KERNELS[grid_type]
         try:
             scales = [float(s) for s in filter_scales]
@@ -591,6 +605,7 @@ class FilterBank:
         _forward_only(evaluation)
         if plan_cache is not None and plan_cache not in PLAN_CACHE_MODES:
             raise ValueError(f"plan_cache must be one of {PLAN_CACHE_MODES} or None, not {plan_cache!r}")
+        _check_nan_mask(nan_mask, grid_type)
         Filter._reject_bad_arguments(types.SimpleNamespace(Laplacian=self.Laplacian, dx_min=dx_min, transition_width=transition_width,
                                                            ndim=ndim, n_steps=n_steps))
         asked = int(n_steps)
@@ -605,7 +620,7 @@ class FilterBank:
             warnings.filterwarnings("ignore", message="You have set n_steps below the default")
             self.filters = [Filter(filter_scale=s, dx_min=dx_min, filter_shape=filter_shape, transition_width=transition_width, ndim=ndim,
                                    n_steps=self.n_steps, grid_type=grid_type, grid_vars=self.grid_vars, evaluation=evaluation,
-                                   plan_cache=plan_cache) for s in scales]
+                                   plan_cache=plan_cache, nan_mask=nan_mask) for s in scales]
         self.filter_specs = [f.filter_spec for f in self.filters]
         self.last_route = None
         self._memo = _LaplacianMemo(self.Laplacian)
@@ -631,12 +646,19 @@ class FilterBank:
         want = self._wants_bank()
         eligible = (len(self.filters) > 1 and self.evaluation != "reference" and want is not False
                     and not issubclass(self.Laplacian, BaseVectorLaplacian))
+        # nan_mask: the batch exists for "auto" on the flux-form kinds (gcmf_apply_bank_gaps: the faces folded once per slice); the
+        # land-mask kinds, True or "auto", run the filters -- which carry nan_mask -- one after the other
+        faces = self.nan_mask == "auto" and self.grid_type in GAP_FOLD_GRID_TYPES
+        if self.nan_mask and not faces:
+            eligible = False
+        if eligible and faces and want is None:
+            eligible = _GAPS_BANK_BY_DEFAULT
         if eligible and want is None:
             shape = tuple(getattr(field, "shape", ()))
             eligible = len(shape) >= 2 and _bank_by_default(len(self.filters), int(shape[-2]), int(shape[-1]), self.grid_type)
         if eligible:
             with plan_cache_mode(self.plan_cache):
-                out = self._memo.get(args)._run_bank(field, self.filter_specs)
+                out = self._memo.get(args)._run_bank(field, self.filter_specs, faces_from_nan=faces)
             if out is not None:
                 self.last_route = "bank"
                 self.last_path = kernels_last_path()

@@ -782,15 +782,19 @@ class _DeviceLaplacian:
                 return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32)
         return outs
 
-    def _run_bank(self, field, specs):
+    def _run_bank(self, field, specs, faces_from_nan: bool = False):
         """FilterBank's one-batch route: the polynomials of `specs` (one degree, one s_max) on every 2-D slice of `field` through
         gcmf_apply_bank; the result has shape (len(specs),) + field.shape and, slice by slice, the bits of _run with each spec.  None
         where the library has no bank for this Laplacian, data or polynomial (the caller then runs the specs one after the other).
         The Laplacians of BANK_GRID_TYPES have one; what the polynomial is cut into is the library's answer (plan.bank_cut: launches of
         5 .. 9 levels, 5 .. 8 on TRIPOLAR_POP_WITH_LAND, whose seam rows k_fold_band advances beside or after every strip launch).
         At most GCMF_BANK_ENTRIES entries per call: a longer sweep is cut over the polynomials, and over the fields where they alone
-        exceed the bound; every call writes straight into the one output array.  A host array goes up through torch."""
+        exceed the bound; every call writes straight into the one output array.  A host array goes up through torch.
+        faces_from_nan: every slice with its own gaps, wet_mask * [slice is not NaN], at every scale (FilterBank(nan_mask="auto"),
+        gcmf_apply_bank_gaps: the face coefficients folded once per slice and call); GAP_FOLD_GRID_TYPES with nx % 4 == 0, None otherwise."""
         if self._glead is not None or self._NCOMP != 1 or self.GRID_TYPE not in BANK_GRID_TYPES or not self._planes:
+            return None
+        if faces_from_nan and self.GRID_TYPE not in GAP_FOLD_GRID_TYPES:
             return None
         given = field
         f = _unwrap(field)
@@ -803,6 +807,8 @@ class _DeviceLaplacian:
         ny, nx = shape[-2:]
         nfield = int(np.prod(shape[:-2], dtype=np.int64)) if len(shape) > 2 else 1
         nbank, n_steps = len(specs), int(specs[0].n_steps)
+        if faces_from_nan and nx % 4:
+            return None
         gpu = _on_gpu(f)
         dev = f.device.index if gpu else current_device()
         plan = self._plan(_lib.F64, (ny, nx), dev)
@@ -837,7 +843,8 @@ class _DeviceLaplacian:
         try:
             for j0, j1, i0, i1 in chunks:
                 dst = out4[j0:j1, i0:i1] if gpu else torch.empty((j1 - j0, i1 - i0, ny, nx), dtype=torch.float64, device=src.device)
-                plan.apply_bank(P[j0:j1], c, src3[i0:i1].data_ptr(), dst.data_ptr(), i1 - i0, stream=cur.cuda_stream)
+                plan.apply_bank(P[j0:j1], c, src3[i0:i1].data_ptr(), dst.data_ptr(), i1 - i0, stream=cur.cuda_stream,
+                                faces_from_nan=faces_from_nan)
                 if not gpu:
                     out4[j0:j1, i0:i1].copy_(dst)   # (synchronises)
             _note_path(plan.last_path(), plan.device)

@@ -250,10 +250,29 @@ int gcmf_apply(gcmf_plan *plan, const double *p, int n_steps, double c, const vo
  *   ordinary kernel (the launches are an instantiation of their own of it), gcmf_last_kernel_geometry appends " bank=<nbank>".
  * gcmf_bank_cut: the launch depths (5 .. 9 levels each; 5 .. 8 on a plan with the tripole seam) gcmf_apply_bank uses for a polynomial of
  * n_steps steps and nentries = nbank * nfield entries, written to depths[0 .. return value); 0 = a bank is not on offer for this plan /
- * polynomial.  The answer is the same inside and outside a bank call.
+ * polynomial.  The answer is the same inside and outside a bank call, and it is gcmf_apply_bank_gaps' cut too.
+ *
+ * gcmf_apply_bank_gaps: a filter bank on GAPPY fields -- gcmf_apply_bank with GCMF_FACES_FROM_NAN's meaning, same arguments and layout:
+ *     out[j * nfield + i] has the bits of gcmf_apply(plan, p_j, ..., in_i, nbatch = 1, GCMF_FACES_FROM_NAN | GCMF_DEVICE_PTRS)
+ * -- field i filtered with wet_mask * [in_i is not NaN] at every one of the nbank scales; NaN, +-inf and land cells included (a gap is
+ * land in its own field's mask, so it comes out NaN).  The face coefficients and land bytes are folded ONCE per field (k_pre_isolated's
+ * gap form, as for GCMF_FACES_FROM_NAN), not once per entry: 25 bytes per cell and FIELD in the plan's work buffer, bounded by option
+ * "gap_scratch_mb"; when nfield fields need more, the fields are cut into runs that fit (at least one field each) and every polynomial is
+ * served for each run -- same bits.  The launches are the bank's plain strips with the level axis of a stacked plan: entry e reads row
+ * e / nfield of the coefficient table and the input plane, the folded planes and the land bytes of field e % nfield (k_ringc and
+ * k_land_fix, instantiations of their own again).
+ *   Scope: ordinary whole-grid f64 plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T, device pointers (`flags` must hold GCMF_DEVICE_PTRS),
+ *   `in` and `out` not overlapping, a polynomial for which gcmf_bank_cut offers a cut (which needs nx to be a multiple of 4).
+ *   GCMF_ERR_UNSUPPORTED, naming the function and the limit: TRIPOLAR_POP_WITH_LAND or any other grid type, an f32 plan, a stacked plan,
+ *   a row slab, GCMF_PLAN_SELF_RING, host pointers, GCMF_FORWARD_RECURRENCE, GCMF_MASK_FROM_NAN, GCMF_OUT_F32, no cut.
+ *   GCMF_ERR_INVALID_ARG as for gcmf_apply_bank.  nfield = 0: GCMF_OK.  GCMF_FACES_FROM_NAN in `flags` is accepted and implied;
+ *   gcmf_apply_bank itself keeps refusing both NaN flags.  gcmf_last_kernel names the ordinary kernel,
+ *   gcmf_last_kernel_geometry appends " levels=<fields of the launch> bank=<polynomials of the launch>".
  */
 extern int gcmf_apply_bank(gcmf_plan *plan, const double *p, int nbank, int n_steps, double c, const void *in, void *out, int64_t nfield,
                            uint32_t flags, void *stream);
+extern int gcmf_apply_bank_gaps(gcmf_plan *plan, const double *p, int nbank, int n_steps, double c, const void *in, void *out, int64_t nfield,
+                                uint32_t flags, void *stream);
 extern int gcmf_bank_cut(const gcmf_plan *plan, int n_steps, int64_t nentries, int *depths, int max_depths);
 
 /* One application of the Laplacian: `ALL_KERNELS[grid_type](**grid_vars)(field)` (kernels.py
@@ -514,7 +533,8 @@ int gcmf_set_tuning(gcmf_plan *plan, int rows_per_wave, int xcd_remap, int multi
  * (one byte per cell) to the host, synchronises the caller's stream and uploads the tables with a blocking copy -- once per plan and
  * launch depth, but not asynchronous and not legal inside a stream capture: capture after one warm-up call, or set 0),
  * "gap_scratch_mb" N (GCMF_FACES_FROM_NAN: the most scratch, in MiB, the per-entry planes of one launch may take; default 4096; a batch
- * whose planes need more is cut into consecutive launches of at least one entry; same bits).  Unknown names: GCMF_ERR_INVALID_ARG. */
+ * whose planes need more is cut into consecutive launches of at least one entry; same bits; gcmf_apply_bank_gaps: per field, not per
+ * entry, and the FIELDS are cut into runs).  Unknown names: GCMF_ERR_INVALID_ARG. */
 int gcmf_set_option(gcmf_plan *plan, const char *name, int value);
 
 /* Last error text of the calling thread (never NULL). */

@@ -9,11 +9,15 @@ kernel on a small grid) -- so the rows are measured at 56 steps (seven launches 
   (a) FilterBank.apply with GCMF_FILTER_BANK=1 (last_route "bank");
   (b) [f.apply(field) for f in bank.filters], plans cached: a lone field each, on whatever the library runs a lone field on (zipped strips,
       wet-row tables).
+Gappy fields (--gaps), IRREGULAR_WITH_LAND: N = 1 and 4 device-resident fields with distinct gaps (~16 % of the cells, as
+tools/measure_gap_fold.py draws them) at M scales, 63 steps:
+  (a) FilterBank(nan_mask="auto").apply with GCMF_FILTER_BANK=1 (gcmf_apply_bank_gaps: N folds, one batch of M N entries);
+  (b) [f.apply(fields) for f in bank.filters], each Filter(nan_mask="auto"), plans cached: M flagged calls of N entries, M N folds.
 The routes ALTERNATE inside each of five blocks; a block times `reps` applications (on small grids as many more as fill a quarter of a
 second) between two device synchronisations (wall clock: the
 loop's cost is partly the host's); median of the five blocks, spread = (max - min) / median.  The tool compares the outputs of (a) and (b)
 bit for bit and says so.
-    python tools/measure_filter_bank.py [--pop] [applications per block] [M ...]"""
+    python tools/measure_filter_bank.py [--pop | --gaps] [applications per block] [M ...]"""
 import os
 import statistics
 import sys
@@ -29,7 +33,8 @@ from gcm_filters_amd import FilterBank, FilterShape, GridType, _lib, testing as 
 from gcm_filters_amd.kernels import ALL_KERNELS, clear_plan_cache  # noqa: E402
 
 POP = "--pop" in sys.argv[1:]
-ARGV = [a for a in sys.argv[1:] if a != "--pop"]
+GAPS = "--gaps" in sys.argv[1:]
+ARGV = [a for a in sys.argv[1:] if a not in ("--pop", "--gaps")]
 KIND = "TRIPOLAR_POP_WITH_LAND" if POP else "IRREGULAR_WITH_LAND"
 REPS = int(ARGV[0]) if ARGV else 3
 MS = [int(a) for a in ARGV[1:]] or [4, 8, 16]
@@ -59,16 +64,37 @@ def alternate(routes, reps=REPS, nblocks=5):
     return {k: (statistics.median(v), (max(v) - min(v)) / statistics.median(v), v) for k, v in ms.items()}
 
 
-def report(shape, M, n_steps=0):
-    """n_steps = 0: the bank's own degree"""
+def gappy(shape, nb):
+    """nb fields with distinct gaps, ~16 % of the cells (tools/measure_gap_fold.py)."""
+    rng = np.random.Generator(np.random.PCG64(2025))
+    out = np.empty((nb,) + shape)
+    for b in range(nb):
+        f = T.random_field(shape, 100 + b)
+        f[rng.random(shape) < 0.15] = np.nan
+        for _ in range(6):
+            j0, i0 = int(rng.integers(1, shape[0] - 1)), int(rng.integers(0, shape[1] - 1))
+            f[j0:j0 + int(rng.integers(shape[0] // 120 + 1, shape[0] // 12 + 2)), i0:i0 + int(rng.integers(shape[1] // 180 + 1, shape[1] // 12 + 2))] = np.nan
+        out[b] = f
+    return out
+
+
+def report(shape, M, n_steps=0, nfield=0):
+    """n_steps = 0: the bank's own degree; nfield > 0: that many gappy fields, each filtered under its own gaps"""
     gv = T.scalar_grid_vars(KIND, shape)
     gv["wet_mask"] = T.island_mask(shape, 7)     # (row 0 is land: what the tripolar kinds ask for)
     dx = T.grid_dx_min(KIND, gv)
     scales = [float(s) * dx for s in np.geomspace(4.0, 16.0, M)]
     with warnings.catch_warnings():
         warnings.simplefilter("ignore")          # ("n_steps below the default": 56 steps are chosen for their launch cut)
-        bank = FilterBank(filter_scales=scales, dx_min=dx, filter_shape=FilterShape.TAPER, n_steps=n_steps, grid_type=GridType[KIND], grid_vars=gv)
-    field = torch.from_numpy(np.random.Generator(np.random.PCG64(11)).random(shape)).cuda()
+        bank = FilterBank(filter_scales=scales, dx_min=dx, filter_shape=FilterShape.TAPER, n_steps=n_steps, grid_type=GridType[KIND], grid_vars=gv,
+                          nan_mask="auto" if nfield else False)
+    if nfield:
+        host = gappy(shape, nfield)
+        field = torch.from_numpy(host).cuda()
+        print(f"--- gaps {np.isnan(host).mean():.3f} of the cells, {nfield} field(s), nan_mask=\"auto\"")
+        del host
+    else:
+        field = torch.from_numpy(np.random.Generator(np.random.PCG64(11)).random(shape)).cuda()
     print(f"--- {KIND} {shape} f64, {M} scales {scales[0] / dx:.1f} .. {scales[-1] / dx:.1f} dx, n_steps {bank.n_steps}, wet fraction "
           f"{gv['wet_mask'].mean():.3f}, build {_lib.load().gcmf_build_id().decode()[:12]}", flush=True)
 
@@ -85,7 +111,7 @@ def report(shape, M, n_steps=0):
     plan = ALL_KERNELS[GridType[KIND]](**gv)._plan(_lib.F64, tuple(shape), field.device.index)
     a = banked()
     assert bank.last_route == "bank", bank.last_route
-    ran_a = f"cut {plan.bank_cut(bank.n_steps, M)}, ran {plan.last_kernel()} {plan.last_kernel_geometry()}"
+    ran_a = f"cut {plan.bank_cut(bank.n_steps, M * max(1, nfield))}, ran {plan.last_kernel()} {plan.last_kernel_geometry()}"
     b = torch.stack(looped())
     ran_b = f"cut {plan.clenshaw_cut(bank.n_steps, 1)}, path {plan.last_path()}, ran {plan.last_kernel()} {plan.last_kernel_geometry()}"
     torch.cuda.synchronize()
@@ -94,7 +120,7 @@ def report(shape, M, n_steps=0):
     del a, b
     routes = {"(a) FilterBank, one batch": banked, "(b) loop over the scales": looped}
     res = alternate(routes)
-    cells = shape[0] * shape[1] * bank.n_steps * M
+    cells = shape[0] * shape[1] * bank.n_steps * M * max(1, nfield)
     for k, (med, spread, blocks) in res.items():
         print(f"{k:28s} {med:9.3f} ms = {med / M:7.3f} ms per scale = {cells / med * 1e-6:6.1f} G cells.steps/s   spread {100 * spread:4.1f} %   "
               f"blocks {' '.join(f'{x:.3f}' for x in blocks)}", flush=True)
@@ -108,7 +134,12 @@ def report(shape, M, n_steps=0):
 
 
 ok = True
-if POP:
+if GAPS:
+    for shape in (T.BASELINE_SHAPE, (1080, 1440)):
+        for nfield in (1, 4):
+            for M in MS:
+                ok = report(tuple(shape), M, 63, nfield) and ok
+elif POP:
     for shape in (T.BASELINE_SHAPE, (1080, 1440), (384, 320)):
         for n_steps in (56, 63):
             for M in MS:
