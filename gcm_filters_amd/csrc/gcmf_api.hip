@@ -94,26 +94,26 @@ static void host_unregister(const void *p) {
 // Tripolar grids: the fold couples column i of the top row with column nx-1-i, i.e. with a DIFFERENT wave of the
 // strip-marching kernel, which therefore stops S rows below the seam; the top S rows ("band") are advanced by k_fold_band.
 // backward: the launcher of the form ringc_cut chose for this launch (gcmf_ringc_cut.hpp has the policy and its measurements)
-static int launch_ringc(gcmf_plan *pl, const MultiArgs &m, const RingcCut &cut, hipStream_t s) {
+static int launch_ringc(gcmf_plan *pl, const CallView &cv, const MultiArgs &m, const RingcCut &cut, hipStream_t s) {
   if (cut.form == RINGC_NONE) return GCMF_OK;
-  if (cut.form == RINGC_ZIP || cut.form == RINGC_ZIP_FOLD) return launch_ringc_zip(pl, m, cut, s);
+  if (cut.form == RINGC_ZIP || cut.form == RINGC_ZIP_FOLD) return launch_ringc_zip(pl, cv, m, cut, s);
   switch (pl->kind) {
-    case K_REG: return launch_ringc_reg(pl, m, cut, s);
-    case K_MASK: return launch_ringc_maskz(pl, m, cut, s);
+    case K_REG: return launch_ringc_reg(pl, cv, m, cut, s);
+    case K_MASK: return launch_ringc_maskz(pl, cv, m, cut, s);
     case K_FLUX:
-      // (gcmf_apply_bank, and gcmf_apply_bank_gaps on a plan that looks stacked meanwhile: always the plain strips, ringc_cut)
-      if (pl->bank_n > 0) return pl->stacked ? launch_ringc_bank_gaps(pl, m, cut, s) : launch_ringc_bank(pl, m, cut, s);
-      if (pl->stacked) return launch_ringc_levels(pl, m, cut, s);   // (always the plain strips: ringc_cut)
-      if (cut.xe) return launch_ringc_flux_slab(pl, m, cut, s);   // (k_ringcs, or k_ringcp's early-exit form)
-      if (m.S == 9) return launch_ringc_flux9(pl, m, cut, s);
-      return launch_ringc_flux(pl, m, cut, s);
+      // (gcmf_apply_bank, and gcmf_apply_bank_gaps whose view is stacked, one level per field: always the plain strips, ringc_cut)
+      if (cv.bank_n > 0) return cv.stacked ? launch_ringc_bank_gaps(pl, cv, m, cut, s) : launch_ringc_bank(pl, cv, m, cut, s);
+      if (cv.stacked) return launch_ringc_levels(pl, cv, m, cut, s);   // (always the plain strips: ringc_cut)
+      if (cut.xe) return launch_ringc_flux_slab(pl, cv, m, cut, s);   // (k_ringcs, or k_ringcp's early-exit form)
+      if (m.S == 9) return launch_ringc_flux9(pl, cv, m, cut, s);
+      return launch_ringc_flux(pl, cv, m, cut, s);
     default: break;
   }
   set_error("k_ringc: plan is not a scalar kind");
   return GCMF_ERR_INVALID_ARG;
 }
 
-int advance_multi(gcmf_plan *pl, const MultiArgs &m, hipStream_t s, int *launches, bool backward) {
+int advance_multi(gcmf_plan *pl, const CallView &cv, const MultiArgs &m, hipStream_t s, int *launches, bool backward) {
   const Geom &g = pl->g;
   const int rows = g.rows, S = m.S;
   const bool band = g.fold && m.row_hi == rows;
@@ -121,7 +121,7 @@ int advance_multi(gcmf_plan *pl, const MultiArgs &m, hipStream_t s, int *launche
   RingcCut cut{};
   auto blocked = [&](const MultiArgs &a) -> int {   // (between the dominant kernel's timing events)
     int r;
-    if ((r = dom_begin(pl, s)) || (r = backward ? launch_ringc(pl, a, cut, s) : launch_scalar_multi(pl, a, s)) || (r = dom_end(pl, s))) return r;
+    if ((r = dom_begin(pl, s)) || (r = backward ? launch_ringc(pl, cv, a, cut, s) : launch_scalar_multi(pl, cv, a, s)) || (r = dom_end(pl, s))) return r;
     if (launches) ++*launches;
     return GCMF_OK;
   };
@@ -131,7 +131,7 @@ int advance_multi(gcmf_plan *pl, const MultiArgs &m, hipStream_t s, int *launche
   const bool seq = band && pl->band_seq_cells > 0 && (long long)m.nbatch * (m.row_hi - m.row_lo) * g.nx <= pl->band_seq_cells;
   // how the strips of a backward launch are cut: decided once, here (on the seam's plan: of the rows k_fold_band leaves, or -- round 6 --
   // the seam's rows inside the launch: strips that start at the seam, zipped with their mirror windows)
-  if (backward) cut = ringc_cut(ringc_cut_in(pl, m.row_hi - m.row_lo, band, m.nbatch, S, band && !seq));
+  if (backward) cut = ringc_cut(ringc_cut_in(pl, cv, m.row_hi - m.row_lo, band, m.nbatch, S, band && !seq));
   if (!band || cut.form == RINGC_ZIP_FOLD) return blocked(m);
   const int blo = rows - S;  // first band row
   // k_fold_band reads rows [rows - 2S, rows) of the input planes (valid: the caller's ghost zone covers [row_lo - S, ...)) and owns
@@ -150,7 +150,7 @@ int advance_multi(gcmf_plan *pl, const MultiArgs &m, hipStream_t s, int *launche
   // the other writes (the band reads rows >= rows - 2S of the input planes, the two write disjoint rows of the output planes).
   if (seq) {
     if (mm.row_hi > mm.row_lo && (rc = blocked(mm))) return rc;
-    if ((rc = launch_fold_band(pl, m, backward, s, true))) return rc;
+    if ((rc = launch_fold_band(pl, cv, m, backward, s, true))) return rc;
     if (launches) ++*launches;
     return GCMF_OK;
   }
@@ -165,7 +165,7 @@ int advance_multi(gcmf_plan *pl, const MultiArgs &m, hipStream_t s, int *launche
   }
   GCMF_HIP(hipEventRecord(pl->ev_fork, s));
   GCMF_HIP(hipStreamWaitEvent(pl->side, pl->ev_fork, 0));
-  if ((rc = launch_fold_band(pl, m, backward, pl->side))) return rc;
+  if ((rc = launch_fold_band(pl, cv, m, backward, pl->side))) return rc;
   if (launches) ++*launches;
   GCMF_HIP(hipEventRecord(pl->ev_join, pl->side));
   if (mm.row_hi > mm.row_lo && (rc = blocked(mm))) return rc;
@@ -173,8 +173,8 @@ int advance_multi(gcmf_plan *pl, const MultiArgs &m, hipStream_t s, int *launche
   return GCMF_OK;
 }
 
-int step_dispatch(gcmf_plan *pl, const StepArgs &a, hipStream_t s) {
-  return pl->ncomp == 1 ? launch_scalar_step(pl, a, s) : launch_vector_step(pl, a, s);
+int step_dispatch(gcmf_plan *pl, const CallView &cv, const StepArgs &a, hipStream_t s) {
+  return pl->ncomp == 1 ? launch_scalar_step(pl, cv, a, s) : launch_vector_step(pl, a, s);   // (the vector kinds have no view but the plan's own)
 }
 
 // p[0..n_steps] on the device for k_land_fix; uploaded only when it changed (a pageable upload stalls the host behind
@@ -199,11 +199,11 @@ static int ensure_dev_p(gcmf_plan *pl, const double *p, int n_steps, hipStream_t
 
 // The land-fix tail of a filter whose launches kept the isolated (land) cells out of their state: their own polynomial, from the
 // untouched input `in` into `out` (k_land_fix)
-int land_fix_tail(gcmf_plan *pl, const double *p, int n_steps, double c, const void *in, void *out, bool fb32, int64_t nbatch,
-                  hipStream_t s) {
+int land_fix_tail(gcmf_plan *pl, const CallView &cv, const double *p, int n_steps, double c, const void *in, void *out, bool fb32,
+                  int64_t nbatch, hipStream_t s) {
   int rc = ensure_dev_p(pl, p, n_steps, s);
   if (rc) return rc;
-  return launch_land_fix(pl, in, out, pl->dev_p, n_steps, c, fb32 ? 1 : 0, nbatch, s);
+  return launch_land_fix(pl, cv, in, out, pl->dev_p, n_steps, c, fb32 ? 1 : 0, nbatch, s);
 }
 // Stages the raw grid planes on the device (temporaries, unless they are there already), folds them into the plan (precompute), frees
 // the temporaries; scalar plans also get a row of zeros for k_ring.
@@ -488,9 +488,11 @@ int gcmf_plan_rows(const gcmf_plan *pl, int64_t *rows_alloc, int64_t *first_owne
 static const int64_t MAX_LAUNCH_BATCH = 32768;  // batch entries per launch (gridDim.y of the scalar kernels)
 
 // What the evaluation schedules of one gcmf_apply / gcmf_laplacian call share: the stream, the caller's fields (on the device), the work
-// planes of every component (F2: the second fbar plane of the scalar blocked schedule), the polynomial and the launch count.
+// planes of every component (F2: the second fbar plane of the scalar blocked schedule), the polynomial and the launch count; cv: the
+// grid and the entry layout as this call sees them (gcmf_internal.hpp).
 struct ApplyCtx {
   gcmf_plan *pl;
+  CallView cv;
   hipStream_t s;
   const void *din[2];
   void *dout[2], *A[2], *B[2], *Cb[2], *Db[2], *F[2], *F2, *Pp[2];
@@ -501,59 +503,10 @@ struct ApplyCtx {
   bool fb32;
 };
 
-// GCMF_MASK_FROM_NAN: while one call runs (the plan's mutex is held) the launchers find the call's own mask bytes -- one plane per batch
-// entry, in the work buffer -- where they look for the plan's, and a land count that says "has land" (the plan's number does not apply
-// to the entries' masks).  The plan's own bytes are never written; its pointers are put back when the call leaves.
-struct FieldMasks {
-  gcmf_plan *pl;
-  const uint8_t *mbits, *lbits;
-  int64_t n_land;
-  FieldMasks(gcmf_plan *p, const uint8_t *bits) : pl(p), mbits(p->g.mbits), lbits(p->lbits), n_land(p->n_land) {
-    pl->g.mbits = pl->lbits = bits;
-    pl->n_land = std::max<int64_t>(1, n_land);
-    pl->mask_per_field = 1;
-  }
-  ~FieldMasks() {
-    pl->g.mbits = mbits;
-    pl->lbits = lbits;
-    pl->n_land = n_land;
-    pl->mask_per_field = 0;
-  }
-  FieldMasks(const FieldMasks &) = delete;
-  FieldMasks &operator=(const FieldMasks &) = delete;
-};
-
-// GCMF_FACES_FROM_NAN: while one launch of such a call runs (the plan's mutex is held) the plan looks like a STACKED plan whose levels
-// are the launch's entries -- coefficient planes and land bytes in the work buffer, folded from the plan's own planes and each entry's
-// NaNs (launch_gap_fold) -- so the launches are exactly a stacked plan's: launch_ringc_levels and the level form of k_land_fix.  The
-// plan's own planes are never written; everything is put back however the call leaves.
-struct GapFaces {
-  gcmf_plan *pl;
-  const void *coef[3];
-  const uint8_t *lbits;
-  int64_t n_land, nlev, entry0;
-  bool stacked;
-  // keep_entry0 (gcmf_apply_bank_gaps: the levels are the call's FIELDS, nbatch of them, and the launch's first entry is entry0 of the call)
-  GapFaces(gcmf_plan *p, const double *cE, const double *cN, const double *ra, const uint8_t *bits, int64_t nbatch, bool keep_entry0 = false)
-      : pl(p), lbits(p->lbits), n_land(p->n_land), nlev(p->nlev), entry0(p->entry0), stacked(p->stacked) {
-    for (int k = 0; k < 3; ++k) coef[k] = pl->g.coef[k];
-    pl->g.coef[0] = cE; pl->g.coef[1] = cN; pl->g.coef[2] = ra;
-    pl->lbits = bits;
-    pl->n_land = std::max<int64_t>(1, n_land);
-    pl->stacked = true;
-    pl->nlev = nbatch;
-    if (!keep_entry0) pl->entry0 = 0;
-  }
-  ~GapFaces() {
-    for (int k = 0; k < 3; ++k) pl->g.coef[k] = coef[k];
-    pl->lbits = lbits;
-    pl->n_land = n_land;
-    pl->stacked = stacked;
-    pl->nlev = nlev;
-    pl->entry0 = entry0;
-  }
-  GapFaces(const GapFaces &) = delete;
-  GapFaces &operator=(const GapFaces &) = delete;
+// gcmf_apply_bank_gaps folds once per FIELD: what its launches have folded already, and where in the work buffer
+struct GapFold {
+  const void *in = nullptr, *at = nullptr;
+  int64_t n = 0;
 };
 
 static const char *const FACES_WHERE = "GCMF_FACES_FROM_NAN is a gcmf_apply flag for whole-grid f64 ordinary plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T";
@@ -562,7 +515,7 @@ static int lapl_step(ApplyCtx &x) {
   StepArgs a{};
   for (int k = 0; k < x.pl->ncomp; ++k) { a.t1[k] = x.din[k]; a.t0[k] = x.dout[k]; a.fb_out[k] = nullptr; }
   a.mode = STEP_LAPL; a.nbatch = x.nbatch; a.row_lo = 0; a.row_hi = x.rows;
-  const int rc = step_dispatch(x.pl, a, x.s);
+  const int rc = step_dispatch(x.pl, x.cv, a, x.s);
   if (!rc) ++x.launches;
   return rc;
 }
@@ -615,19 +568,16 @@ static int sched_backward_scalar(ApplyCtx &x, const int *depths, int n_clen, boo
   const void *u = nullptr, *v = nullptr;
   int rc;
   gcmf_plan *pl = x.pl;
-  struct WetNow {   // (cleared however the schedule leaves)
-    gcmf_plan *pl;
-    ~WetNow() { pl->wet_now = false; }
-  } wet_guard{pl};
-  pl->wet_now = pl->wet_rows > 0 && x.nbatch == 1 && !pl->mask_per_field && !pl->stacked && !pl->bank_n && pl->full && !pl->g.fold && pl->kind == K_FLUX &&
-                pl->d.dtype == GCMF_F64 && pl->n_land > 0 && pl->pool_bytes > 0;
-  pl->pool_clean = pl->wet_now && was_clean;
+  CallView &cv = x.cv;
+  cv.wet_now = pl->wet_rows > 0 && x.nbatch == 1 && !cv.mask_per_field && !cv.stacked && !cv.bank_n && pl->full && !pl->g.fold && pl->kind == K_FLUX &&
+               pl->d.dtype == GCMF_F64 && cv.n_land > 0 && pl->pool_bytes > 0;
+  pl->pool_clean = cv.wet_now && was_clean;
   for (int q = 0, lvl = 1; q < n_clen; lvl += depths[q++]) {
     void *fr[2];
     free_planes(pool, 1, u, v, fr);
     MultiArgs m = backward_args(x.p, x.n_steps, x.c, lvl, depths[q], u, v, fr, x.din[0], x.dout[0]);
     m.fb_is_f32 = x.fb32; m.nbatch = x.nbatch; m.row_lo = 0; m.row_hi = x.rows;
-    if ((rc = advance_multi(x.pl, m, x.s, &x.launches, true))) return rc;   // (+ the tripole band on tripolar plans)
+    if ((rc = advance_multi(pl, cv, m, x.s, &x.launches, true))) return rc;   // (+ the tripole band on tripolar plans)
     u = fr[0]; v = fr[1];
   }
   return GCMF_OK;
@@ -642,7 +592,7 @@ static int sched_forward_scalar(ApplyCtx &x) {
   const int n_steps = x.n_steps;
   // flux kinds only: the land-mask kernels have a NaN-only mode that already makes NaN on land free, there the two extra passes
   // would only cost
-  const bool zero_land = land_ok(pl, n_steps);  // n_steps < 4096: k_land_fix keeps p in LDS
+  const bool zero_land = land_ok(pl, x.cv, n_steps);  // n_steps < 4096: k_land_fix keeps p in LDS
   void *pool[4] = {x.A[0], x.B[0], x.Cb[0], x.Db[0]};
   void *Fcur = x.F[0], *Fnext = x.F2;   // fbar ping-pongs between two planes (see oF2)
   const void *u = x.din[0], *v = nullptr;
@@ -661,14 +611,14 @@ static int sched_forward_scalar(ApplyCtx &x) {
       m.first = (k == 1); m.last = is_last; m.S = S; m.fb_is_f32 = x.fb32;
       m.land_zero = land_zeroed ? 1 : 0;
       // the first launch may drop land on load if k_land_fix restores it at the end (not for a one-launch filter)
-      m.ring_first = (k == 1 && !is_last && (zero_land || pl->n_land == 0)) ? 1 : 0;
+      m.ring_first = (k == 1 && !is_last && (zero_land || x.cv.n_land == 0)) ? 1 : 0;
       for (int t = 0; t < S; ++t) m.pk[t] = p[k + t];
       m.p0 = p[0]; m.c = x.c; m.nbatch = x.nbatch; m.row_lo = 0; m.row_hi = x.rows;
-      if ((rc = advance_multi(pl, m, x.s, &x.launches))) return rc;
+      if ((rc = advance_multi(pl, x.cv, m, x.s, &x.launches))) return rc;
       u = fr[0]; v = fr[1];
       if (k == 1 && zero_land && !is_last) {  // keep the isolated cells out of the state from here on
-        if (!ring_supported(pl, m)) {
-          if ((rc = launch_zero_land(pl, fr[0], fr[1], x.nbatch, x.s))) return rc;
+        if (!ring_supported(pl, x.cv, m)) {
+          if ((rc = launch_zero_land(pl, x.cv, fr[0], fr[1], x.nbatch, x.s))) return rc;
         }   // (k_ring's first launch and k_fold_band took the land as zero while they loaded the field)
         land_zeroed = true;
       }
@@ -684,14 +634,14 @@ static int sched_forward_scalar(ApplyCtx &x) {
         src = x.Pp[0];
       }
       a1.t1[0] = src; a1.t2[0] = v; a1.t0[0] = fr[0]; a1.fb_in[0] = Fcur; a1.fb_out[0] = is_last ? x.dout[0] : Fcur;
-      if ((rc = step_dispatch(pl, a1, x.s))) return rc;
+      if ((rc = step_dispatch(pl, x.cv, a1, x.s))) return rc;
       ++x.launches;
       v = src; u = fr[0];
     }
     k += S;
   }
   if (land_zeroed)  // the isolated cells' own polynomial, from the caller's untouched input
-    return land_fix_tail(pl, p, n_steps, x.c, x.din[0], x.dout[0], x.fb32, x.nbatch, x.s);
+    return land_fix_tail(pl, x.cv, p, n_steps, x.c, x.din[0], x.dout[0], x.fb32, x.nbatch, x.s);
   return GCMF_OK;
 }
 
@@ -763,7 +713,7 @@ static int sched_forward_vec(ApplyCtx &x) {
       for (int q = 0; q < 2; ++q) {
         a1.t1[q] = u[q]; a1.t2[q] = v[q]; a1.t0[q] = fr[q]; a1.fb_in[q] = x.F[q]; a1.fb_out[q] = x.dout[q];
       }
-      if ((rc = step_dispatch(pl, a1, x.s))) return rc;
+      if ((rc = step_dispatch(pl, x.cv, a1, x.s))) return rc;
       k += 1;
     }
     ++x.launches;
@@ -797,7 +747,7 @@ static int sched_single_steps(ApplyCtx &x) {
       a.fb_in[q] = x.F[q];
       a.fb_out[q] = (k == n_steps) ? x.dout[q] : x.F[q];
     }
-    if ((rc = step_dispatch(pl, a, x.s))) return rc;
+    if ((rc = step_dispatch(pl, x.cv, a, x.s))) return rc;
     ++x.launches;
   }
   return GCMF_OK;
@@ -807,10 +757,11 @@ static int sched_single_steps(ApplyCtx &x) {
 // offer (the work layout has their planes).
 static int run_schedule(ApplyCtx &x, uint32_t flags, bool use_multi, bool use_vmulti) {
   gcmf_plan *pl = x.pl;
+  const CallView &cv = x.cv;
   int depths[1024];
   const bool fwd_only = flags & GCMF_FORWARD_RECURRENCE;   // the caller wants the reference's forward recurrence / accumulation
   const bool back_f32 = pl->clenshaw_f32 || (flags & GCMF_BACKWARD_F32);   // f32 B-grid / scalar state backwards: only when asked for
-  const int n_clen = (use_multi && !fwd_only) ? clenshaw_cut(pl, x.n_steps, depths, 1024, back_f32, x.nbatch) : 0;
+  const int n_clen = (use_multi && !fwd_only) ? clenshaw_cut(pl, cv, x.n_steps, depths, 1024, back_f32, x.nbatch) : 0;
   if (pl->res_lo) {   // the LAST call of this plan ran on the chip: did one of ITS launches time out?  (told once, to the plan whose
     //                   output was poisoned -- never to an unrelated plan; the process runs the strip-marching launches from now on)
     const unsigned lo = pl->res_lo, hi = pl->res_hi;
@@ -826,13 +777,14 @@ static int run_schedule(ApplyCtx &x, uint32_t flags, bool use_multi, bool use_vm
   pl->pool_clean = false;
   bool resident = false;
   int path = GCMF_PATH_STRIPS;
-  if (pl->stacked && n_clen <= 0) {   // (run_whole has refused GCMF_FORWARD_RECURRENCE)
+  if (cv.stacked && n_clen <= 0) {   // (run_whole has refused GCMF_FORWARD_RECURRENCE)
     set_error("gcmf_apply: a stacked plan (gcmf_plan_create_levels) runs the backward evaluation only, which is not on offer for this plan "
               "and a polynomial of %d steps (gcmf_clenshaw_cut_batch returns 0): build one plan per level", x.n_steps);
     return GCMF_ERR_UNSUPPORTED;
   }
   // (the on-chip kernel reads the plan's own mask, and one level's planes)
-  if (n_clen > 0 && x.nbatch == 1 && !(flags & GCMF_NO_RESIDENT) && !pl->mask_per_field && !pl->stacked && !pl->bank_n) {
+  const bool own = !cv.mask_per_field && !cv.stacked && !cv.bank_n;
+  if (n_clen > 0 && x.nbatch == 1 && !(flags & GCMF_NO_RESIDENT) && own) {
     int why = GCMF_RESIDENT_OFF;
     resident = resident_supported(pl, 0, x.rows, std::min(x.n_steps, 64), x.n_steps, &why);   // (small whole grids; GCMF_RESIDENT=1: whatever fits)
     if (!resident && why == GCMF_RESIDENT_LOCK_BUSY) path = GCMF_PATH_STRIPS_LOCK_BUSY;
@@ -845,13 +797,13 @@ static int run_schedule(ApplyCtx &x, uint32_t flags, bool use_multi, bool use_vm
     int rc = GCMF_OK;
     if (resident)
       rc = sched_resident(x);
-    else if ((flags & GCMF_NO_RESIDENT) || pl->mask_per_field || pl->stacked || pl->bank_n || ringc_one_depth(pl, x.n_steps, x.nbatch) <= 0 || !sched_single_launch(x))
+    else if ((flags & GCMF_NO_RESIDENT) || !own || ringc_one_depth(pl, x.n_steps, x.nbatch) <= 0 || !sched_single_launch(x))
       rc = sched_backward_scalar(x, depths, n_clen, was_clean);
-    if (rc || pl->n_land == 0) return rc;
+    if (rc || cv.n_land == 0) return rc;
     // the isolated cells' own polynomial (forward recurrence, as the reference computes it)
-    // (every entry its own; gcmf_apply_bank_gaps: on the land bytes of its own field too -- the launcher looks at pl->stacked)
-    if (pl->bank_n > 0) return launch_land_fix_bank(pl, x.din[0], x.dout[0], x.n_steps, x.c, x.nbatch, x.s);
-    return land_fix_tail(pl, x.p, x.n_steps, x.c, x.din[0], x.dout[0], x.fb32, x.nbatch, x.s);
+    // (every entry its own; gcmf_apply_bank_gaps: on the land bytes of its own field too -- the launcher looks at cv.stacked)
+    if (cv.bank_n > 0) return launch_land_fix_bank(pl, cv, x.din[0], x.dout[0], x.n_steps, x.c, x.nbatch, x.s);
+    return land_fix_tail(pl, cv, x.p, x.n_steps, x.c, x.din[0], x.dout[0], x.fb32, x.nbatch, x.s);
   }
   if (use_multi) return sched_forward_scalar(x);
   const bool vec_backward = (pl->kind == K_CGRID && pl->clenshaw >= 1) ||
@@ -918,14 +870,16 @@ static int finish_call(ApplyCtx &x, bool on_dev, void *const *out, size_t out_by
   return GCMF_OK;
 }
 
-// Shared driver of gcmf_apply and gcmf_laplacian; the plan's mutex is held and the device is current.
+// Shared driver of gcmf_apply, the banks and gcmf_laplacian: ONE launch's worth of entries; the plan's mutex is held and the device is current.
+// base: the view the caller runs on -- the plan's own, with entry0 = the first entry of this launch within the call and, inside a bank,
+// the bank's fields and table rows; the flags put the call's own mask bytes or folded planes into it.  fold: gcmf_apply_bank_gaps' memo.
 // `timed` = false: the caller (the pipelined host path) brackets the launches with the timing events itself.
-static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double c, const void *const *in,
-                            void *const *out, int64_t nbatch, uint32_t flags, void *stream, bool lapl_only,
-                            bool timed) {
+static int run_whole_locked(gcmf_plan *pl, const CallView &base, GapFold *fold, const double *p, int n_steps, double c, const void *const *in,
+                            void *const *out, int64_t nbatch, uint32_t flags, void *stream, bool lapl_only, bool timed) {
   const bool on_dev = flags & GCMF_DEVICE_PTRS;
   ApplyCtx x{};
   x.pl = pl;
+  x.cv = base;
   // device pointers: run on exactly the caller's stream (NULL = the HIP default stream) so the work is
   // ordered with the caller's own kernels; host pointers: the plan's private stream unless one is given
   x.s = (on_dev || stream) ? (hipStream_t)stream : pl->stream;
@@ -958,8 +912,8 @@ static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double 
   // GCMF_FACES_FROM_NAN (run_whole has checked the plan and cut the batch to the scratch bound): the entries' own cE, cN, ra and land bytes
   const bool faces = flags & GCMF_FACES_FROM_NAN;
   // (inside gcmf_apply_bank_gaps: the FIELDS' own planes, bank_nfield of them whatever the launch's entries)
-  const bool bank_faces = faces && pl->bank_n > 0;
-  const int64_t nfold = bank_faces ? pl->bank_nfield : nbatch;
+  const bool bank_faces = faces && base.bank_n > 0;
+  const int64_t nfold = bank_faces ? base.bank_nfield : nbatch;
   const size_t nface = (size_t)nfold * pl->d.ny * pl->d.nx;
   const size_t szG = align_up(nface * 8 + 256, 256), szL = align_up(nface + 256, 256);   // (padded as precompute_levels pads a stacked plan's)
   const size_t oG = per; if (faces) per += 3 * szG + szL;
@@ -987,34 +941,39 @@ static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double 
   }
   const bool timing = pl->timing && timed;
   if (timing) GCMF_HIP(hipEventRecord(pl->ev0, x.s));
-  if (from_nan) {
+  CallView &cv = x.cv;
+  if (from_nan) {   // the call's own mask bytes where the launchers look for the plan's; the plan's land count does not apply to them
     uint8_t *bits = (uint8_t *)(w + oM);
     if ((rc = launch_field_masks(pl, pl->g.mbits, x.din[0], bits, nbatch, x.s))) return rc;
     ++x.launches;
-    FieldMasks own(pl, bits);
-    if ((rc = run_schedule(x, flags, use_multi, use_vmulti))) return rc;
-    return finish_call(x, on_dev, out, ncell * fbs, timing, timed);
+    cv.mbits = cv.lbits = bits;
+    cv.n_land = std::max<int64_t>(1, pl->n_land);
+    cv.mask_per_field = 1;
   }
-  if (faces) {
+  if (faces) {   // the view of a stacked plan whose levels are this launch's entries (a bank: its fields, entry0 kept -- see apply_bank)
     double *cEb = (double *)(w + oG), *cNb = (double *)(w + oG + szG), *rab = (double *)(w + oG + 2 * szG);
     uint8_t *bits = (uint8_t *)(w + oG + 3 * szG);
-    const double *cE = (const double *)pl->g.coef[0], *cN = (const double *)pl->g.coef[1], *ra = (const double *)pl->g.coef[2];
-    GapFaces own(pl, cEb, cNb, rab, bits, nfold, bank_faces);
-    int depths[1024];   // (asked with the guard in place: the answer run_schedule will get)
-    if (!use_multi || clenshaw_cut(pl, n_steps, depths, 1024, false, nbatch) <= 0) {
+    cv.coef[0] = cEb; cv.coef[1] = cNb; cv.coef[2] = rab;
+    cv.lbits = bits;
+    cv.n_land = std::max<int64_t>(1, pl->n_land);
+    cv.stacked = true;
+    cv.nlev = nfold;
+    if (!bank_faces) cv.entry0 = 0;
+    int depths[1024];   // (asked of the call's view: the answer run_schedule will get)
+    if (!use_multi || clenshaw_cut(pl, cv, n_steps, depths, 1024, false, nbatch) <= 0) {
       set_error("%s; for this plan and a polynomial of %d steps the stacked strips offer no backward cut (gcmf_clenshaw_cut_batch: fewer than "
                 "five steps, nx not a multiple of 4, GCMF_CLENSHAW=0 ...): filter with a plan built from wet_mask * [not NaN]",
                 bank_faces ? "gcmf_apply_bank_gaps" : FACES_WHERE, n_steps);
       return GCMF_ERR_UNSUPPORTED;
     }
     // (a bank: one fold per FIELD -- a later launch of the same call that finds the same fields folded at the same place folds nothing)
-    if (!(bank_faces && pl->gap_fold_at == (const void *)cEb && pl->gap_fold_in == x.din[0] && pl->gap_fold_n == nfold)) {
-      if ((rc = launch_gap_fold(pl, cE, cN, ra, x.din[0], cEb, cNb, rab, bits, nfold, x.s))) return rc;
+    if (!(fold && fold->at == (const void *)cEb && fold->in == x.din[0] && fold->n == nfold)) {
+      if ((rc = launch_gap_fold(pl, (const double *)pl->g.coef[0], (const double *)pl->g.coef[1], (const double *)pl->g.coef[2], x.din[0], cEb, cNb,
+                                rab, bits, nfold, x.s)))
+        return rc;
       ++x.launches;
-      if (bank_faces) { pl->gap_fold_at = cEb; pl->gap_fold_in = x.din[0]; pl->gap_fold_n = nfold; }
+      if (fold) *fold = GapFold{x.din[0], cEb, nfold};
     }
-    if ((rc = run_schedule(x, flags, use_multi, use_vmulti))) return rc;
-    return finish_call(x, on_dev, out, ncell * fbs, timing, timed);
   }
   if ((rc = lapl_only ? lapl_step(x) : run_schedule(x, flags, use_multi, use_vmulti))) return rc;
   return finish_call(x, on_dev, out, ncell * fbs, timing, timed);
@@ -1024,7 +983,7 @@ static int run_whole_locked(gcmf_plan *pl, const double *p, int n_steps, double 
 // staging slots in HBM -- upload of chunk k+1 and download of chunk k-1 run on their own streams while chunk k is
 // filtered ("overlap H2D of chunk k+1 with compute of chunk k").  The host issues upload(k+1) and the
 // launches of chunk k+1 BEFORE download(k), so that a blocking download into pageable memory still overlaps with compute.
-static int run_host_pipelined(gcmf_plan *pl, const double *p, int n_steps, double c, const void *const *in,
+static int run_host_pipelined(gcmf_plan *pl, CallView cv, const double *p, int n_steps, double c, const void *const *in,
                               void *const *out, int64_t nbatch, uint32_t flags, void *stream, bool lapl_only,
                               int64_t chunk_nb) {
   const int nc = pl->ncomp;
@@ -1073,8 +1032,8 @@ static int run_host_pipelined(gcmf_plan *pl, const double *p, int n_steps, doubl
     if (ch == 0 && pl->timing) GCMF_HIP(hipEventRecord(pl->ev0, s_cmp));
     const void *din[2] = {In(slot, 0), nc > 1 ? In(slot, 1) : nullptr};
     void *dout[2] = {Out(slot, 0), nc > 1 ? Out(slot, 1) : nullptr};
-    pl->entry0 = ch * chunk_nb;   // (stacked plans: the chunk's entry b is entry ch * chunk_nb + b of the call)
-    int r = run_whole_locked(pl, p, n_steps, c, din, dout, nb, dflags, (void *)s_cmp, lapl_only, false);
+    cv.entry0 = ch * chunk_nb;   // (stacked plans: the chunk's entry b is entry ch * chunk_nb + b of the call)
+    int r = run_whole_locked(pl, cv, nullptr, p, n_steps, c, din, dout, nb, dflags, (void *)s_cmp, lapl_only, false);
     if (r) return r;
     if (ch == nchunks - 1 && pl->timing) GCMF_HIP(hipEventRecord(pl->ev1, s_cmp));
     GCMF_HIP(hipEventRecord(pl->ev_cmp[slot], s_cmp));
@@ -1121,6 +1080,46 @@ static int run_host_pipelined(gcmf_plan *pl, const double *p, int n_steps, doubl
   }
   if ((rc = finish(GCMF_OK))) return rc;
   if (pl->timing) GCMF_HIP(hipEventElapsedTime(&pl->last_ms, pl->ev0, pl->ev1));
+  return GCMF_OK;
+}
+
+// GCMF_FACES_FROM_NAN: the entries (a bank: the fields) one launch may carry -- their own planes (25 bytes per cell and entry) at or under
+// option "gap_scratch_mb", at least one
+static int64_t gap_launch_entries(const gcmf_plan *pl) {
+  const long long bound = (long long)std::max(0, pl->gap_scratch_mb) << 20, per_entry = 25LL * pl->d.ny * pl->d.nx;
+  return std::max<int64_t>(1, std::min<int64_t>(MAX_LAUNCH_BATCH, bound / per_entry));
+}
+
+// What the launches of one call add up to: gcmf_last_ms and gcmf_last_launches report the call
+struct Tally {
+  float ms = 0.f;
+  int launches = 0;
+  int leave(gcmf_plan *pl) const {
+    pl->last_ms = ms;
+    pl->last_launches = launches;
+    return GCMF_OK;
+  }
+};
+
+// nent entries in consecutive launches of at most launch_nb: launch k starts in_stride / out_stride bytes x its first entry into every
+// component of `in` / `out` (in_stride 0: a bank, whose every launch reads all the fields) and an entry keeps its place in the call through
+// the view's entry0, which counts on from cv.entry0.
+static int run_launches(gcmf_plan *pl, CallView cv, GapFold *fold, const double *p, int n_steps, double c, const void *const *in, size_t in_stride,
+                        void *const *out, size_t out_stride, int64_t nent, int64_t launch_nb, uint32_t flags, void *stream, bool lapl_only, Tally &t) {
+  const int64_t first = cv.entry0;
+  for (int64_t e0 = 0; e0 < nent; e0 += launch_nb) {
+    const void *in2[2] = {nullptr, nullptr};
+    void *out2[2] = {nullptr, nullptr};
+    for (int k = 0; k < pl->ncomp; ++k) {
+      in2[k] = (const char *)in[k] + (size_t)e0 * in_stride;
+      out2[k] = (char *)out[k] + (size_t)e0 * out_stride;
+    }
+    cv.entry0 = first + e0;
+    const int rc = run_whole_locked(pl, cv, fold, p, n_steps, c, in2, out2, std::min(nent - e0, launch_nb), flags, stream, lapl_only, true);
+    if (rc) return rc;
+    t.ms += pl->last_ms;
+    t.launches += pl->last_launches;
+  }
   return GCMF_OK;
 }
 
@@ -1181,45 +1180,21 @@ static int run_whole(gcmf_plan *pl, const double *p, int n_steps, double c, cons
   if (nbatch == 0) return GCMF_OK;
   std::lock_guard<std::mutex> lk(pl->mu);
   GCMF_HIP(hipSetDevice(pl->d.device));
-  pl->entry0 = 0;
-  // the most entries one launch takes: the scalar kernels index the batch with gridDim.y (<= 65535); GCMF_FACES_FROM_NAN: as many as
-  // keep the entries' own planes (25 bytes per cell and entry) at or under option "gap_scratch_mb", at least one
-  int64_t launch_nb = MAX_LAUNCH_BATCH;
-  if (flags & GCMF_FACES_FROM_NAN) {
-    const long long bound = (long long)std::max(0, pl->gap_scratch_mb) << 20, per_entry = 25LL * pl->d.ny * pl->d.nx;
-    launch_nb = std::max<int64_t>(1, std::min<int64_t>(MAX_LAUNCH_BATCH, bound / per_entry));
-  }
+  // the most entries one launch takes: the scalar kernels index the batch with gridDim.y (<= 65535)
+  const int64_t launch_nb = (flags & GCMF_FACES_FROM_NAN) ? gap_launch_entries(pl) : MAX_LAUNCH_BATCH;
   if (!(flags & GCMF_DEVICE_PTRS) && nbatch > 1 && pl->host_chunk_bytes > 0) {
     const size_t entry = (size_t)pl->d.ny * pl->d.nx * dtype_size(pl->d.dtype);
     int64_t chunk_nb = (int64_t)(pl->host_chunk_bytes / entry);
     if (chunk_nb < 1) chunk_nb = 1;
     if (chunk_nb > launch_nb) chunk_nb = launch_nb;
-    if (chunk_nb < nbatch) return run_host_pipelined(pl, p, n_steps, c, in, out, nbatch, flags, stream, lapl_only, chunk_nb);
+    if (chunk_nb < nbatch) return run_host_pipelined(pl, own_view(pl), p, n_steps, c, in, out, nbatch, flags, stream, lapl_only, chunk_nb);
   }
-  if (nbatch <= launch_nb)
-    return run_whole_locked(pl, p, n_steps, c, in, out, nbatch, flags, stream, lapl_only, true);
-  // very long batches of small fields, and batches whose per-entry planes exceed the scratch bound: consecutive launches
+  // (more than one launch: very long batches of small fields, and batches whose per-entry planes exceed the scratch bound)
   const size_t cell = (size_t)pl->d.ny * pl->d.nx, ts = dtype_size(pl->d.dtype);
   const size_t fbs = lapl_only ? ts : ((pl->d.dtype == GCMF_F32 && !(flags & GCMF_OUT_F32)) ? 8 : ts);
-  float ms_total = 0.f;
-  int launches = 0;
-  for (int64_t b0 = 0; b0 < nbatch; b0 += launch_nb) {
-    const int64_t nb = nbatch - b0 < launch_nb ? nbatch - b0 : launch_nb;
-    const void *in2[2] = {nullptr, nullptr};
-    void *out2[2] = {nullptr, nullptr};
-    for (int k = 0; k < pl->ncomp; ++k) {
-      in2[k] = (const char *)in[k] + (size_t)b0 * cell * ts;
-      out2[k] = (char *)out[k] + (size_t)b0 * cell * fbs;
-    }
-    pl->entry0 = b0;
-    int rc = run_whole_locked(pl, p, n_steps, c, in2, out2, nb, flags, stream, lapl_only, true);
-    if (rc) return rc;
-    ms_total += pl->last_ms;
-    launches += pl->last_launches;
-  }
-  pl->last_ms = ms_total;
-  pl->last_launches = launches;
-  return GCMF_OK;
+  Tally t;
+  const int rc = run_launches(pl, own_view(pl), nullptr, p, n_steps, c, in, cell * ts, out, cell * fbs, nbatch, launch_nb, flags, stream, lapl_only, t);
+  return rc ? rc : t.leave(pl);
 }
 
 int gcmf_apply(gcmf_plan *pl, const double *p, int n_steps, double c, const void *const *in, void *const *out,
@@ -1257,119 +1232,58 @@ static int ensure_bank_tables(gcmf_plan *pl, const double *p, int nbank, int n_s
   return GCMF_OK;
 }
 
-int gcmf_apply_bank(gcmf_plan *pl, const double *p, int nbank, int n_steps, double c, const void *in, void *out, int64_t nfield,
-                    uint32_t flags, void *stream) {
+// gcmf_apply_bank and (gaps) gcmf_apply_bank_gaps: the same call but for the grid types, one flag and the fold.
+// On gappy fields the launches run on the planes GCMF_FACES_FROM_NAN folds, once per FIELD: the view carries the bank AND, from
+// run_whole_locked, a level axis of one level per field, and launch_ringc / run_schedule pick the forms that know both.
+static int apply_bank(const char *who, bool gaps, gcmf_plan *pl, const double *p, int nbank, int n_steps, double c, const void *in, void *out,
+                      int64_t nfield, uint32_t flags, void *stream) {
   if (!pl || !p || !in || !out) {
-    set_error("gcmf_apply_bank: null argument");
+    set_error("%s: null argument", who);
     return GCMF_ERR_INVALID_ARG;
   }
   if (nbank < 1 || n_steps < 1 || nfield < 0) {
-    set_error("gcmf_apply_bank: %d polynomials of %d steps on %lld fields (at least one polynomial of at least one step)", nbank, n_steps, (long long)nfield);
+    set_error("%s: %d polynomials of %d steps on %lld fields (at least one polynomial of at least one step)", who, nbank, n_steps, (long long)nfield);
     return GCMF_ERR_INVALID_ARG;
   }
   const int gt = pl->d.grid_type;
-  const bool kind_ok = gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T || gt == GCMF_TRIPOLAR_POP_WITH_LAND;
-  const char *why = !kind_ok ? "another grid type" : pl->d.dtype != GCMF_F64 ? "an f32 plan" : (pl->d.flags & GCMF_PLAN_SELF_RING) ? "GCMF_PLAN_SELF_RING" :
-                    !pl->full ? "a row slab" : pl->stacked ? "a stacked plan (gcmf_plan_create_levels)" : !(flags & GCMF_DEVICE_PTRS) ? "host pointers (GCMF_DEVICE_PTRS is required)" :
-                    (flags & GCMF_FORWARD_RECURRENCE) ? "GCMF_FORWARD_RECURRENCE" : (flags & GCMF_MASK_FROM_NAN) ? "GCMF_MASK_FROM_NAN" :
-                    (flags & GCMF_FACES_FROM_NAN) ? "GCMF_FACES_FROM_NAN" : (flags & GCMF_OUT_F32) ? "GCMF_OUT_F32" : nullptr;
-  if (why) {
-    set_error("gcmf_apply_bank: filter banks run on ordinary whole-grid f64 plans of IRREGULAR_WITH_LAND, MOM5U, MOM5T and TRIPOLAR_POP_WITH_LAND with device pointers, "
-              "backwards, on the plan's own mask and into f64 (%s; grid type %d): call gcmf_apply once per polynomial", why, gt);
-    return GCMF_ERR_UNSUPPORTED;
-  }
-  const size_t cell = (size_t)pl->d.ny * pl->d.nx;
-  if ((int64_t)nbank * nfield > (int64_t)2000000000) {
-    set_error("gcmf_apply_bank: %d polynomials x %lld fields: at most 2e9 entries per call", nbank, (long long)nfield);
-    return GCMF_ERR_INVALID_ARG;
-  }
-  const int64_t nent = (int64_t)nbank * nfield;
-  {
-    const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (size_t)nfield * cell * 8, o0 = (uintptr_t)out, o1 = o0 + (size_t)nent * cell * 8;
-    if ((nfield > 0 && i0 < o1 && o0 < i1) || in == out) {   // every launch and k_land_fix read the input
-      set_error("gcmf_apply_bank: `out` must not overlap `in` (filtering in place is not supported)");
-      return GCMF_ERR_INVALID_ARG;
-    }
-  }
-  int depths[1024];
-  if (bank_cut(pl, n_steps, std::max<int64_t>(1, nent), depths, 1024) <= 0) {
-    set_error("gcmf_apply_bank: for this plan and a polynomial of %d steps the plain strips offer no backward cut (gcmf_bank_cut returns 0: fewer "
-              "than five steps, nx = %lld not a multiple of 4 on a grid with land, GCMF_CLENSHAW=0 ...): call gcmf_apply once per polynomial",
-              n_steps, (long long)pl->d.nx);
-    return GCMF_ERR_UNSUPPORTED;
-  }
-  if (nfield == 0) return GCMF_OK;
-  std::lock_guard<std::mutex> lk(pl->mu);
-  GCMF_HIP(hipSetDevice(pl->d.device));
-  int rc = ensure_bank_tables(pl, p, nbank, n_steps, (hipStream_t)stream);
-  if (rc) return rc;
-  struct Bank {   // (put back however the call leaves)
-    gcmf_plan *pl;
-    ~Bank() { pl->bank_n = 0; pl->bank_nfield = 1; pl->entry0 = 0; }
-  } guard{pl};
-  pl->bank_n = nbank;
-  pl->bank_nfield = nfield;
-  float ms_total = 0.f;
-  int launches = 0;
-  for (int64_t e0 = 0; e0 < nent; e0 += MAX_LAUNCH_BATCH) {   // (consecutive launches: an entry keeps its place through entry0)
-    const int64_t nb = std::min<int64_t>(nent - e0, MAX_LAUNCH_BATCH);
-    const void *in1[2] = {in, nullptr};
-    void *out1[2] = {(char *)out + (size_t)e0 * cell * 8, nullptr};
-    pl->entry0 = e0;
-    // (p: the schedule reads the polynomial's degree only -- the launches and k_land_fix take the coefficients from the tables)
-    if ((rc = run_whole_locked(pl, p, n_steps, c, in1, out1, nb, (flags & GCMF_DEVICE_PTRS) | GCMF_NO_RESIDENT, stream, false, true))) return rc;
-    ms_total += pl->last_ms;
-    launches += pl->last_launches;
-  }
-  pl->last_ms = ms_total;
-  pl->last_launches = launches;
-  return GCMF_OK;
-}
-
-// A filter bank on gappy fields: gcmf_apply_bank's launches on the planes GCMF_FACES_FROM_NAN folds -- once per FIELD.  While a launch runs
-// the plan carries both guards: the bank's (bank_n, bank_nfield, entry0; here) and GapFaces with nlev = the launch's fields
-// (run_whole_locked), and launch_ringc / run_schedule pick the forms that know both axes.
-int gcmf_apply_bank_gaps(gcmf_plan *pl, const double *p, int nbank, int n_steps, double c, const void *in, void *out, int64_t nfield,
-                         uint32_t flags, void *stream) {
-  if (!pl || !p || !in || !out) {
-    set_error("gcmf_apply_bank_gaps: null argument");
-    return GCMF_ERR_INVALID_ARG;
-  }
-  if (nbank < 1 || n_steps < 1 || nfield < 0) {
-    set_error("gcmf_apply_bank_gaps: %d polynomials of %d steps on %lld fields (at least one polynomial of at least one step)", nbank, n_steps, (long long)nfield);
-    return GCMF_ERR_INVALID_ARG;
-  }
-  const int gt = pl->d.grid_type;
-  const bool kind_ok = gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T;
-  const char *why = gt == GCMF_TRIPOLAR_POP_WITH_LAND ? "TRIPOLAR_POP_WITH_LAND, whose gap fold is not offered" : !kind_ok ? "another grid type" :
+  const bool pop = gt == GCMF_TRIPOLAR_POP_WITH_LAND, kind_ok = gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T || pop;
+  const char *why = (gaps && pop) ? "TRIPOLAR_POP_WITH_LAND, whose gap fold is not offered" : !kind_ok ? "another grid type" :
                     pl->d.dtype != GCMF_F64 ? "an f32 plan" : (pl->d.flags & GCMF_PLAN_SELF_RING) ? "GCMF_PLAN_SELF_RING" : !pl->full ? "a row slab" :
                     pl->stacked ? "a stacked plan (gcmf_plan_create_levels)" : !(flags & GCMF_DEVICE_PTRS) ? "host pointers (GCMF_DEVICE_PTRS is required)" :
                     (flags & GCMF_FORWARD_RECURRENCE) ? "GCMF_FORWARD_RECURRENCE" : (flags & GCMF_MASK_FROM_NAN) ? "GCMF_MASK_FROM_NAN" :
-                    (flags & GCMF_OUT_F32) ? "GCMF_OUT_F32" : nullptr;
+                    (!gaps && (flags & GCMF_FACES_FROM_NAN)) ? "GCMF_FACES_FROM_NAN" : (flags & GCMF_OUT_F32) ? "GCMF_OUT_F32" : nullptr;
   if (why) {
-    set_error("gcmf_apply_bank_gaps: filter banks on gappy fields run on ordinary whole-grid f64 plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T with device "
-              "pointers, backwards and into f64 (%s; grid type %d): call gcmf_apply with GCMF_FACES_FROM_NAN once per polynomial", why, gt);
+    set_error(gaps ? "%s: filter banks on gappy fields run on ordinary whole-grid f64 plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T with device "
+                     "pointers, backwards and into f64 (%s; grid type %d): call gcmf_apply with GCMF_FACES_FROM_NAN once per polynomial"
+                   : "%s: filter banks run on ordinary whole-grid f64 plans of IRREGULAR_WITH_LAND, MOM5U, MOM5T and TRIPOLAR_POP_WITH_LAND with device pointers, "
+                     "backwards, on the plan's own mask and into f64 (%s; grid type %d): call gcmf_apply once per polynomial",
+              who, why, gt);
     return GCMF_ERR_UNSUPPORTED;
   }
   const size_t cell = (size_t)pl->d.ny * pl->d.nx;
   if ((int64_t)nbank * nfield > (int64_t)2000000000) {
-    set_error("gcmf_apply_bank_gaps: %d polynomials x %lld fields: at most 2e9 entries per call", nbank, (long long)nfield);
+    set_error("%s: %d polynomials x %lld fields: at most 2e9 entries per call", who, nbank, (long long)nfield);
     return GCMF_ERR_INVALID_ARG;
   }
   const int64_t nent = (int64_t)nbank * nfield;
   {
     const uintptr_t i0 = (uintptr_t)in, i1 = i0 + (size_t)nfield * cell * 8, o0 = (uintptr_t)out, o1 = o0 + (size_t)nent * cell * 8;
-    if ((nfield > 0 && i0 < o1 && o0 < i1) || in == out) {   // the fold, every launch and k_land_fix read the input
-      set_error("gcmf_apply_bank_gaps: `out` must not overlap `in` (filtering in place is not supported)");
+    if ((nfield > 0 && i0 < o1 && o0 < i1) || in == out) {   // (the fold,) every launch and k_land_fix read the input
+      set_error("%s: `out` must not overlap `in` (filtering in place is not supported)", who);
       return GCMF_ERR_INVALID_ARG;
     }
   }
   int depths[1024];
-  // (the folded planes always have land -- the gaps -- so what a plan without land may skip is needed here: land_ok)
-  if ((pl->d.nx % 4) != 0 || !pl->zero_land || n_steps >= 4096 || bank_cut(pl, n_steps, std::max<int64_t>(1, nent), depths, 1024) <= 0) {
-    set_error("gcmf_apply_bank_gaps: for this plan and a polynomial of %d steps the plain strips offer no backward cut (gcmf_bank_cut returns 0: fewer "
-              "than five steps, GCMF_CLENSHAW=0 ...; or nx = %lld is not a multiple of 4, 4096 steps or more, GCMF_ZERO_LAND=0): call gcmf_apply with "
-              "GCMF_FACES_FROM_NAN once per polynomial", n_steps, (long long)pl->d.nx);
+  // (gaps: the folded planes always have land -- the gaps -- so what a plan without land may skip is needed here: land_ok)
+  if ((gaps && ((pl->d.nx % 4) != 0 || !pl->zero_land || n_steps >= 4096)) || bank_cut(pl, own_view(pl), n_steps, std::max<int64_t>(1, nent), depths, 1024) <= 0) {
+    if (gaps)
+      set_error("%s: for this plan and a polynomial of %d steps the plain strips offer no backward cut (gcmf_bank_cut returns 0: fewer "
+                "than five steps, GCMF_CLENSHAW=0 ...; or nx = %lld is not a multiple of 4, 4096 steps or more, GCMF_ZERO_LAND=0): call gcmf_apply with "
+                "GCMF_FACES_FROM_NAN once per polynomial", who, n_steps, (long long)pl->d.nx);
+    else
+      set_error("%s: for this plan and a polynomial of %d steps the plain strips offer no backward cut (gcmf_bank_cut returns 0: fewer "
+                "than five steps, nx = %lld not a multiple of 4 on a grid with land, GCMF_CLENSHAW=0 ...): call gcmf_apply once per polynomial",
+                who, n_steps, (long long)pl->d.nx);
     return GCMF_ERR_UNSUPPORTED;
   }
   if (nfield == 0) return GCMF_OK;
@@ -1377,63 +1291,52 @@ int gcmf_apply_bank_gaps(gcmf_plan *pl, const double *p, int nbank, int n_steps,
   GCMF_HIP(hipSetDevice(pl->d.device));
   int rc = ensure_bank_tables(pl, p, nbank, n_steps, (hipStream_t)stream);
   if (rc) return rc;
-  struct Bank {   // (put back however the call leaves)
-    gcmf_plan *pl;
-    double *rev, *fwd;
-    ~Bank() {
-      pl->bank_n = 0; pl->bank_nfield = 1; pl->entry0 = 0;
-      pl->bank_rev = rev; pl->bank_fwd = fwd;
-      pl->gap_fold_at = pl->gap_fold_in = nullptr; pl->gap_fold_n = 0;
-    }
-  } guard{pl, pl->bank_rev, pl->bank_fwd};
-  pl->gap_fold_at = pl->gap_fold_in = nullptr;
-  pl->gap_fold_n = 0;
-  const uint32_t rflags = GCMF_DEVICE_PTRS | GCMF_NO_RESIDENT | GCMF_FACES_FROM_NAN;
-  // the fields one launch may carry: their own planes (25 bytes per cell and field) at or under option "gap_scratch_mb", at least one
-  const long long bound = (long long)std::max(0, pl->gap_scratch_mb) << 20, per_field = 25LL * pl->d.ny * pl->d.nx;
-  const int64_t run_nf = std::max<int64_t>(1, std::min<int64_t>(MAX_LAUNCH_BATCH, bound / per_field));
-  float ms_total = 0.f;
-  int launches = 0;
+  const uint32_t rflags = GCMF_DEVICE_PTRS | GCMF_NO_RESIDENT | (gaps ? GCMF_FACES_FROM_NAN : 0u);
+  const void *in1[2] = {in, nullptr};
+  void *out1[2] = {out, nullptr};
+  CallView cv = own_view(pl);
+  cv.bank_rev = pl->bank_rev; cv.bank_fwd = pl->bank_fwd; cv.bank_stride = pl->bank_stride;
+  GapFold fold;   // (this call's: the fields folded by its earlier launches)
+  Tally t;
+  const int64_t run_nf = gaps ? gap_launch_entries(pl) : nfield;
   if (nfield <= run_nf) {
-    // All fields at once: the entries as gcmf_apply_bank cuts them.  A launch that starts at entry e0 of the call has entry0 = e0, so the
-    // plan's lev0 = entry0 % nlev = e0 % nfield (ringc_params; nlev = nfield under GapFaces, which keeps entry0 here) and the kernel's level
-    // (lev0 + y) % nlev = (e0 % nfield + y) % nfield = (e0 + y) % nfield: the field of entry e0 + y, also when e0 = k * MAX_LAUNCH_BATCH is
-    // no multiple of nfield.  k_land_fix takes the field from ent0 = entry0 itself.  Every such launch finds its work layout at another
-    // place (its batch differs from the previous one's or the fields are folded already), so the fold is repeated only where it must be.
-    pl->bank_n = nbank;
-    pl->bank_nfield = nfield;
-    for (int64_t e0 = 0; e0 < nent; e0 += MAX_LAUNCH_BATCH) {
-      const int64_t nb = std::min<int64_t>(nent - e0, MAX_LAUNCH_BATCH);
-      const void *in1[2] = {in, nullptr};
-      void *out1[2] = {(char *)out + (size_t)e0 * cell * 8, nullptr};
-      pl->entry0 = e0;
-      if ((rc = run_whole_locked(pl, p, n_steps, c, in1, out1, nb, rflags, stream, false, true))) return rc;
-      ms_total += pl->last_ms;
-      launches += pl->last_launches;
-    }
-  } else {
-    // The fields in runs that fit the bound; per run and polynomial one bank of ONE polynomial -- the table's row base, `in` and `out` moved
-    // here, on the host -- over the run's fields: the same kernels on the same operands, and the run is folded once (gap_fold_*: the
-    // launches of a run have one work layout).
-    for (int64_t f0 = 0; f0 < nfield; f0 += run_nf) {
-      const int64_t nf = std::min<int64_t>(nfield - f0, run_nf);
-      pl->bank_n = 1;
-      pl->bank_nfield = nf;
-      pl->entry0 = 0;
-      for (int j = 0; j < nbank; ++j) {
-        pl->bank_rev = guard.rev + (size_t)j * pl->bank_stride;
-        pl->bank_fwd = guard.fwd + (size_t)j * pl->bank_stride;
-        const void *in1[2] = {(const char *)in + (size_t)f0 * cell * 8, nullptr};
-        void *out1[2] = {(char *)out + ((size_t)j * nfield + f0) * cell * 8, nullptr};
-        if ((rc = run_whole_locked(pl, p + (size_t)j * pl->bank_stride, n_steps, c, in1, out1, nf, rflags, stream, false, true))) return rc;
-        ms_total += pl->last_ms;
-        launches += pl->last_launches;
-      }
+    // All fields at once, the entries in consecutive launches: an entry keeps its place through entry0.  On gappy fields the view's level
+    // axis has nlev = nfield levels and keeps the launch's entry0 = e0, so lev0 = e0 % nfield (ringc_params) and the kernel's level
+    // (lev0 + y) % nlev = (e0 + y) % nfield: the field of entry e0 + y, also when e0 = k * MAX_LAUNCH_BATCH is no multiple of nfield;
+    // k_land_fix takes the field from ent0 = entry0 itself.  Every such launch finds its work layout at another place (its batch differs
+    // from the previous one's or the fields are folded already), so the fold is repeated only where it must be.
+    // (p: the schedule reads the polynomial's degree only -- the launches and k_land_fix take the coefficients from the tables)
+    cv.bank_n = nbank;
+    cv.bank_nfield = nfield;
+    rc = run_launches(pl, cv, gaps ? &fold : nullptr, p, n_steps, c, in1, 0, out1, cell * 8, nent, MAX_LAUNCH_BATCH, rflags, stream, false, t);
+    return rc ? rc : t.leave(pl);
+  }
+  // Gappy fields beyond the scratch bound: the fields in runs that fit it; per run and polynomial one bank of ONE polynomial -- the table's
+  // row base, `in` and `out` moved here, on the host -- over the run's fields: the same kernels on the same operands, and the run is folded
+  // once (the launches of a run have one work layout).
+  for (int64_t f0 = 0; f0 < nfield; f0 += run_nf) {
+    const int64_t nf = std::min<int64_t>(nfield - f0, run_nf);
+    cv.bank_n = 1;
+    cv.bank_nfield = nf;
+    in1[0] = (const char *)in + (size_t)f0 * cell * 8;
+    for (int j = 0; j < nbank; ++j) {
+      cv.bank_rev = pl->bank_rev + (size_t)j * pl->bank_stride;
+      cv.bank_fwd = pl->bank_fwd + (size_t)j * pl->bank_stride;
+      out1[0] = (char *)out + ((size_t)j * nfield + f0) * cell * 8;
+      if ((rc = run_launches(pl, cv, &fold, p + (size_t)j * pl->bank_stride, n_steps, c, in1, 0, out1, cell * 8, nf, nf, rflags, stream, false, t))) return rc;
     }
   }
-  pl->last_ms = ms_total;
-  pl->last_launches = launches;
-  return GCMF_OK;
+  return t.leave(pl);
+}
+
+int gcmf_apply_bank(gcmf_plan *pl, const double *p, int nbank, int n_steps, double c, const void *in, void *out, int64_t nfield,
+                    uint32_t flags, void *stream) {
+  return apply_bank("gcmf_apply_bank", false, pl, p, nbank, n_steps, c, in, out, nfield, flags, stream);
+}
+
+int gcmf_apply_bank_gaps(gcmf_plan *pl, const double *p, int nbank, int n_steps, double c, const void *in, void *out, int64_t nfield,
+                         uint32_t flags, void *stream) {
+  return apply_bank("gcmf_apply_bank_gaps", true, pl, p, nbank, n_steps, c, in, out, nfield, flags, stream);
 }
 
 int gcmf_laplacian(gcmf_plan *pl, const void *const *in, void *const *out, int64_t nbatch, uint32_t flags,

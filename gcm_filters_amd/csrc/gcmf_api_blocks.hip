@@ -9,8 +9,8 @@
 
 namespace gcmf {
 
-bool land_ok(const gcmf_plan *pl, int n_steps) {
-  return pl && (pl->kind == K_FLUX || pl->kind == K_MASK) && pl->zero_land && pl->lbits && pl->n_land > 0 && (pl->d.nx % 4) == 0 && n_steps < 4096;
+bool land_ok(const gcmf_plan *pl, const CallView &cv, int n_steps) {
+  return pl && (pl->kind == K_FLUX || pl->kind == K_MASK) && pl->zero_land && cv.lbits && cv.n_land > 0 && (pl->d.nx % 4) == 0 && n_steps < 4096;
 }
 
 // The building blocks and the slab drivers read the plan's own mask: GCMF_MASK_FROM_NAN is gcmf_apply's alone
@@ -42,9 +42,9 @@ bool ringc9_ok(const gcmf_plan *pl) {
 // ... and whole tripolar f64 flux grids whose launches advance the seam themselves (k_ringcz's fold strips, round 6): no k_fold_band (which
 // stops at eight levels) is involved then.  Depends on the launch's batch and rows: a packed batch, more than 64 fields or rows that stop
 // short of the seam keep the band.
-static bool ringc9_fold_ok(const gcmf_plan *pl, int64_t nbatch, int64_t row_lo, int64_t row_hi) {
+static bool ringc9_fold_ok(const gcmf_plan *pl, const CallView &cv, int64_t nbatch, int64_t row_lo, int64_t row_hi) {
   if (!(pl && pl->ringc9 && pl->kind == K_FLUX && pl->d.dtype == GCMF_F64 && pl->full && pl->g.fold && pl->g.rows >= 64)) return false;
-  return ringc_cut(ringc_cut_in(pl, (int)(row_hi - row_lo), row_hi == pl->g.rows, nbatch, 9, false)).form == RINGC_ZIP_FOLD;
+  return ringc_cut(ringc_cut_in(pl, cv, (int)(row_hi - row_lo), row_hi == pl->g.rows, nbatch, 9, false)).form == RINGC_ZIP_FOLD;
 }
 
 // ... and ROW SLABS of f64 flux grids without a tripole seam, when the slab's owner says so (option "slab_nines": SlabFilter sets it on every
@@ -59,7 +59,7 @@ static bool ringc9_slab_ok(const gcmf_plan *pl) {
 // every depth clenshaw_cut offers for a batch passes it on the plan's whole rows.
 const char *clenshaw_depth_refused(const gcmf_plan *pl, int S, bool first, int64_t nbatch, int64_t row_lo, int64_t row_hi) {
   if (S < 5 || S > 9) return "a launch of the backward evaluation runs 5..9 levels";
-  if (S == 9 && !ringc9_ok(pl) && !ringc9_slab_ok(pl) && !ringc9_fold_ok(pl, nbatch, row_lo, row_hi)) {
+  if (S == 9 && !ringc9_ok(pl) && !ringc9_slab_ok(pl) && !ringc9_fold_ok(pl, own_view(pl), nbatch, row_lo, row_hi)) {
     if (pl->g.fold && pl->full)
       return "nine levels on a tripolar plan need the seam advanced inside the launch (k_ringcz's fold strips: rows up to the seam, at "
              "most 64 fields, a batch the launcher would not pack); k_fold_band stops at eight";
@@ -75,25 +75,25 @@ const char *clenshaw_depth_refused(const gcmf_plan *pl, int S, bool first, int64
 // launches run at memcpy rate and gain the plane they no longer move (config 3: +10 %); 2: every scalar kind (the land-mask
 // kernel is bound by its instruction stream and gains nothing: 93 -> 92-95 us per launch).  Needs the isolated cells fixed up
 // by k_land_fix when there is land (land_ok).
-static int clenshaw_cut_for(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, bool f32_asked, int64_t nbatch, bool plain_only);
-int clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, bool f32_asked, int64_t nbatch) {
-  return clenshaw_cut_for(pl, n_steps, depths, max_depths, f32_asked, nbatch, pl && (pl->stacked || pl->bank_n > 0));
+static int clenshaw_cut_for(const gcmf_plan *pl, const CallView &cv, int n_steps, int *depths, int max_depths, bool f32_asked, int64_t nbatch, bool plain_only);
+int clenshaw_cut(const gcmf_plan *pl, const CallView &cv, int n_steps, int *depths, int max_depths, bool f32_asked, int64_t nbatch) {
+  return clenshaw_cut_for(pl, cv, n_steps, depths, max_depths, f32_asked, nbatch, cv.stacked || cv.bank_n > 0);
 }
 
 // A filter bank (gcmf_apply_bank): the cut of the plain strips -- what a stacked plan of the same grid gets; on TRIPOLAR_POP_WITH_LAND the
 // plain strips below the seam and k_fold_band's per-entry form on its rows, so launches of at most eight levels (clenshaw_cut_for)
-bool bank_plan_ok(const gcmf_plan *pl) {
+bool bank_plan_ok(const gcmf_plan *pl, const CallView &cv) {
   const int gt = pl ? pl->d.grid_type : -1;
   return pl && (gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T || gt == GCMF_TRIPOLAR_POP_WITH_LAND) && pl->kind == K_FLUX &&
-         pl->d.dtype == GCMF_F64 && pl->full && !pl->stacked && !pl->mask_per_field;
+         pl->d.dtype == GCMF_F64 && pl->full && !cv.stacked && !cv.mask_per_field;
 }
-int bank_cut(const gcmf_plan *pl, int n_steps, int64_t nentries, int *depths, int max_depths) {
-  if (!bank_plan_ok(pl) || !depths || max_depths < 1 || nentries < 1 || n_steps < 1) return 0;
-  return clenshaw_cut_for(pl, n_steps, depths, max_depths, false, nentries, true);
+int bank_cut(const gcmf_plan *pl, const CallView &cv, int n_steps, int64_t nentries, int *depths, int max_depths) {
+  if (!bank_plan_ok(pl, cv) || !depths || max_depths < 1 || nentries < 1 || n_steps < 1) return 0;
+  return clenshaw_cut_for(pl, cv, n_steps, depths, max_depths, false, nentries, true);
 }
 
 // plain_only: the launches are the plain strips whatever the batch (stacked plans, filter banks)
-static int clenshaw_cut_for(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, bool f32_asked, int64_t nbatch, bool plain_only) {
+static int clenshaw_cut_for(const gcmf_plan *pl, const CallView &cv, int n_steps, int *depths, int max_depths, bool f32_asked, int64_t nbatch, bool plain_only) {
   if (!pl || pl->ncomp != 1 || !(pl->clenshaw >= 2 || (pl->clenshaw == 1 && pl->kind == K_FLUX))) return 0;
   // f32 state (round 5): only when asked for (plan option clenshaw_f32 / GCMF_BACKWARD_F32 per call).  Summed backwards in f32 the
   // polynomial is 15-45 x further from f64 arithmetic than the reference's own f32 path (f32 T_k, f64 running sum; measured:
@@ -106,10 +106,10 @@ static int clenshaw_cut_for(const gcmf_plan *pl, int n_steps, int *depths, int m
   // GCMF_FORWARD_RECURRENCE keep the reference's f64 running sum)
   // (f32 state: the flux kinds since round 3, the REGULAR / land-mask kinds since round 4)
   if (!pl->ring || !pl->zero_row || pl->multi_s < 8 || !multi_supported(pl, 8)) return 0;
-  if (pl->n_land > 0 && !land_ok(pl, n_steps)) return 0;
+  if (cv.n_land > 0 && !land_ok(pl, cv, n_steps)) return 0;
   // (plain_only on a plan with a seam: k_fold_band advances it, eight levels at most -- asked here and not through ringc_cut_in, whose answer
-  // depends on whether a bank call is running now: gcmf_bank_cut must say outside the call what the call will run)
-  const bool nines_full = ringc9_ok(pl) || (!plain_only && ringc9_fold_ok(pl, nbatch, 0, pl->g.rows)), nines = nines_full || ringc9_slab_ok(pl);
+  // depends on the view: gcmf_bank_cut says for the plan's own view what the bank call will run)
+  const bool nines_full = ringc9_ok(pl) || (!plain_only && ringc9_fold_ok(pl, cv, nbatch, 0, pl->g.rows)), nines = nines_full || ringc9_slab_ok(pl);
   if (!(n_steps >= 10 || (n_steps >= 5 && n_steps <= 8) || (n_steps == 9 && nines))) return 0;
   int smax = pl->ringc_smax;
   if (!smax && nbatch == 1 && !plain_only && nines_full && pl->ringc_zip && (long long)pl->g.rows * pl->g.nx <= 2500000LL && n_steps >= 10) {
@@ -120,7 +120,7 @@ static int clenshaw_cut_for(const gcmf_plan *pl, int n_steps, int *depths, int m
     double best = 0.0;
     for (int S = 9; S >= 7; --S) {
       // (the even zipped cut of a lone field over all the plan's rows, whatever the plan's strip_rows and seam)
-      RingcCutIn in = ringc_cut_in(pl, pl->g.rows, false, 1, S, false);
+      RingcCutIn in = ringc_cut_in(pl, cv, pl->g.rows, false, 1, S, false);
       in.strip_rows = 0;
       const long long march = ringc_cut(in).zip_march;
       const int L = (n_steps + S - 1) / S;
@@ -217,7 +217,7 @@ int gcmf_cheb_step(gcmf_plan *pl, const void *const *t1, const void *const *t2, 
   a.nbatch = nbatch;
   a.row_lo = (int)row_lo;
   a.row_hi = (int)row_hi;
-  return step_dispatch(pl, a, (hipStream_t)stream);
+  return step_dispatch(pl, own_view(pl), a, (hipStream_t)stream);
 }
 
 int gcmf_multi_supported(const gcmf_plan *pl, int S) { return (pl && multi_supported(pl, S)) ? 1 : 0; }
@@ -225,16 +225,16 @@ int gcmf_multi_supported(const gcmf_plan *pl, int S) { return (pl && multi_suppo
 
 int gcmf_clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_depths) {
   if (!pl || !depths || max_depths < 1) return 0;
-  return clenshaw_cut(pl, n_steps, depths, max_depths);
+  return clenshaw_cut(pl, own_view(pl), n_steps, depths, max_depths);
 }
 
 int gcmf_clenshaw_cut_batch(const gcmf_plan *pl, int n_steps, int64_t nbatch, int *depths, int max_depths) {
   if (!pl || !depths || max_depths < 1 || nbatch < 1) return 0;
-  return clenshaw_cut(pl, n_steps, depths, max_depths, false, nbatch);
+  return clenshaw_cut(pl, own_view(pl), n_steps, depths, max_depths, false, nbatch);
 }
 
 int gcmf_bank_cut(const gcmf_plan *pl, int n_steps, int64_t nentries, int *depths, int max_depths) {
-  return bank_cut(pl, n_steps, nentries, depths, max_depths);
+  return pl ? bank_cut(pl, own_view(pl), n_steps, nentries, depths, max_depths) : 0;
 }
 
 int gcmf_cheb_multi(gcmf_plan *pl, const void *u, const void *v, void *uo, void *vo, const void *fbar_in,
@@ -248,7 +248,7 @@ int gcmf_cheb_multi(gcmf_plan *pl, const void *u, const void *v, void *uo, void 
     const bool first = mode & GCMF_STEP_FIRST, last = mode & GCMF_STEP_LAST;
     int probe[2];
     // (is the backward evaluation on offer for this plan at all: a 10-level polynomial can always be cut, [5, 5])
-    if (pl->ncomp != 1 || !pl->ring || !pl->zero_row || clenshaw_cut(pl, 10, probe, 2, false, 2) != 2) {
+    if (pl->ncomp != 1 || !pl->ring || !pl->zero_row || clenshaw_cut(pl, own_view(pl), 10, probe, 2, false, 2) != 2) {
       set_error("gcmf_cheb_multi: the backward evaluation is not available for this plan");
       return GCMF_ERR_UNSUPPORTED;
     }
@@ -269,7 +269,7 @@ int gcmf_cheb_multi(gcmf_plan *pl, const void *u, const void *v, void *uo, void 
     for (int t = 0; t < S; ++t) m.pk[t] = pk[t];
     m.p0 = p0; m.c = c; m.S = S; m.first = first; m.last = last; m.nbatch = nbatch; m.row_lo = (int)row_lo; m.row_hi = (int)row_hi;
     m.fb_is_f32 = (pl->d.dtype == GCMF_F32 && (flags & GCMF_OUT_F32)) ? 1 : 0;   // f32 state: the result is f64 unless asked otherwise
-    return advance_multi(pl, m, (hipStream_t)stream, nullptr, true);
+    return advance_multi(pl, own_view(pl), m, (hipStream_t)stream, nullptr, true);
   }
   if (!pl || !u || !fbar_out || !pk) {
     set_error("gcmf_cheb_multi: null argument");
@@ -299,7 +299,7 @@ int gcmf_cheb_multi(gcmf_plan *pl, const void *u, const void *v, void *uo, void 
   m.nbatch = nbatch; m.row_lo = (int)row_lo; m.row_hi = (int)row_hi;
   m.land_zero = (mode & GCMF_STEP_LAND_ZERO) ? 1 : 0;
   m.ring_first = (first && !last && (mode & GCMF_STEP_LAND_FIXED)) ? 1 : 0;
-  return advance_multi(pl, m, (hipStream_t)stream, nullptr);
+  return advance_multi(pl, own_view(pl), m, (hipStream_t)stream, nullptr);
 }
 
 int gcmf_resident_supported(const gcmf_plan *pl, int64_t row_lo, int64_t row_hi, int L) {
@@ -382,15 +382,15 @@ int gcmf_cheb_multi_vec(gcmf_plan *pl, const void *const *u, const void *const *
 }
 
 
-int gcmf_has_land(const gcmf_plan *pl) { return land_ok(pl, 0) ? 1 : 0; }
+int gcmf_has_land(const gcmf_plan *pl) { return (pl && land_ok(pl, own_view(pl), 0)) ? 1 : 0; }
 
 int gcmf_zero_land(gcmf_plan *pl, void *const *a, void *const *b, int64_t nbatch, void *stream) {
   if (refuse_stacked(pl, "gcmf_zero_land")) return GCMF_ERR_UNSUPPORTED;
   if (!pl || !a || !b || !a[0] || !b[0] || nbatch < 1) return GCMF_ERR_INVALID_ARG;
-  if (!land_ok(pl, 0)) return GCMF_ERR_UNSUPPORTED;
+  if (!land_ok(pl, own_view(pl), 0)) return GCMF_ERR_UNSUPPORTED;
   std::lock_guard<std::mutex> lk(pl->mu);
   GCMF_HIP(hipSetDevice(pl->d.device));
-  return launch_zero_land(pl, a[0], b[0], nbatch, (hipStream_t)stream);
+  return launch_zero_land(pl, own_view(pl), a[0], b[0], nbatch, (hipStream_t)stream);
 }
 
 int gcmf_land_fix(gcmf_plan *pl, const double *p, int n_steps, double c, const void *const *in, void *const *out,
@@ -398,11 +398,11 @@ int gcmf_land_fix(gcmf_plan *pl, const double *p, int n_steps, double c, const v
   if (refuse_mask_from_nan(flags, "gcmf_land_fix")) return GCMF_ERR_UNSUPPORTED;
   if (refuse_stacked(pl, "gcmf_land_fix")) return GCMF_ERR_UNSUPPORTED;
   if (!pl || !p || !in || !out || !in[0] || !out[0] || n_steps < 1 || nbatch < 1) return GCMF_ERR_INVALID_ARG;
-  if (!land_ok(pl, n_steps)) return GCMF_ERR_UNSUPPORTED;
+  if (!land_ok(pl, own_view(pl), n_steps)) return GCMF_ERR_UNSUPPORTED;
   std::lock_guard<std::mutex> lk(pl->mu);
   GCMF_HIP(hipSetDevice(pl->d.device));
   const bool fb32 = pl->d.dtype == GCMF_F32 && (flags & GCMF_OUT_F32);
-  return land_fix_tail(pl, p, n_steps, c, in[0], out[0], fb32, nbatch, (hipStream_t)stream);
+  return land_fix_tail(pl, own_view(pl), p, n_steps, c, in[0], out[0], fb32, nbatch, (hipStream_t)stream);
 }
 
 // One whole filter application on this rank's slab, backward (Clenshaw) evaluation, scalar kinds: the choreography of
@@ -480,10 +480,10 @@ int gcmf_slab_apply_backward(gcmf_plan *pl, gcmf_comm *comm, gcmf_p2p *p2p, int 
   }
   const bool fb32 = (dtype == GCMF_F32) && (flags & GCMF_OUT_F32);
   auto land_and_guard = [&]() -> int {   // after the last launch, whichever schedule ran
-    if (land_ok(pl, n_steps)) {
+    if (land_ok(pl, own_view(pl), n_steps)) {
       std::lock_guard<std::mutex> lk(pl->mu);
       GCMF_HIP(hipSetDevice(pl->d.device));
-      if ((rc = land_fix_tail(pl, p, n_steps, c, X, out, fb32, nbatch, s))) return rc;
+      if ((rc = land_fix_tail(pl, own_view(pl), p, n_steps, c, X, out, fb32, nbatch, s))) return rc;
     }
     if (p2p && multi) {   // a failed exchange must not leave a plausible result (the stencils take NaN ghost rows as zero)
       const size_t obytes = (size_t)nbatch * ra * nx * ((dtype == GCMF_F32 && fb32) ? 4 : 8);
@@ -553,7 +553,7 @@ int gcmf_slab_apply_backward(gcmf_plan *pl, gcmf_comm *comm, gcmf_p2p *p2p, int 
       GCMF_HIP(hipSetDevice(pl->d.device));
       MultiArgs mm = m;
       mm.row_lo = r0; mm.row_hi = r1;
-      return advance_multi(pl, mm, s, nullptr, true);
+      return advance_multi(pl, own_view(pl), mm, s, nullptr, true);
     };
     if (first_pending && ovl) {   // (both at once is not worth a fourth piece: the input's ghost rows first, then as below)
       if ((rc = exchange_finish())) return rc;

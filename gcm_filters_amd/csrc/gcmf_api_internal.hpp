@@ -7,19 +7,19 @@
 
 namespace gcmf {
 // gcmf_api.hip
-int step_dispatch(gcmf_plan *pl, const StepArgs &a, hipStream_t s);
-int land_fix_tail(gcmf_plan *pl, const double *p, int n_steps, double c, const void *in, void *out, bool fb32, int64_t nbatch,
+int step_dispatch(gcmf_plan *pl, const CallView &cv, const StepArgs &a, hipStream_t s);
+int land_fix_tail(gcmf_plan *pl, const CallView &cv, const double *p, int n_steps, double c, const void *in, void *out, bool fb32, int64_t nbatch,
                   hipStream_t s);
 // gcmf_api_options.hip: an event pair around every launch of the dominant kernel (gcmf_set_timing(plan, 2))
 int dom_begin(gcmf_plan *pl, hipStream_t s);
 int dom_end(gcmf_plan *pl, hipStream_t s);
 int dom_collect(gcmf_plan *pl);
 // gcmf_api_blocks.hip
-bool land_ok(const gcmf_plan *pl, int n_steps);
+bool land_ok(const gcmf_plan *pl, const CallView &cv, int n_steps);
 bool ringc9_ok(const gcmf_plan *pl);
-int clenshaw_cut(const gcmf_plan *pl, int n_steps, int *depths, int max_depths, bool f32_asked = false, int64_t nbatch = 1);   // (nbatch: a lone field on a cache-resident grid may be cut into shallower launches)
-bool bank_plan_ok(const gcmf_plan *pl);   // an ordinary whole-grid f64 plan of the four flux-form grid types: what gcmf_apply_bank runs on
-int bank_cut(const gcmf_plan *pl, int n_steps, int64_t nentries, int *depths, int max_depths);   // gcmf_bank_cut
+int clenshaw_cut(const gcmf_plan *pl, const CallView &cv, int n_steps, int *depths, int max_depths, bool f32_asked = false, int64_t nbatch = 1);   // (nbatch: a lone field on a cache-resident grid may be cut into shallower launches)
+bool bank_plan_ok(const gcmf_plan *pl, const CallView &cv);   // an ordinary whole-grid f64 plan of the four flux-form grid types: what gcmf_apply_bank runs on
+int bank_cut(const gcmf_plan *pl, const CallView &cv, int n_steps, int64_t nentries, int *depths, int max_depths);   // gcmf_bank_cut
 bool ptr_al16(const void *p);
 int vec_backward_next_depth(const gcmf_plan *pl, int64_t nbatch, int left, int smax);
 

@@ -16,12 +16,12 @@ __global__ __launch_bounds__(256, 1) void k_flux_multi2(const MultiP<T, FB> P) {
   flux_multi2_march<T, FB, S>(P, blockIdx.x * 4 + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6));
 }
 
-template <typename T, typename FB, int S> static int launch_f2(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
+template <typename T, typename FB, int S> static int launch_f2(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) {
   constexpr int VEC = 16 / sizeof(T);
   constexpr int W = 64 * VEC;
   constexpr int M = (S + VEC - 1) / VEC * VEC;
   constexpr int WI = W - 2 * M;
-  const Geom &g = pl->g;
+  const Geom g = view_geom(pl, cv);
   MultiP<T, FB> P;
   P.u0 = (const T *)a.u0;
   P.v0 = (const T *)a.v0;
@@ -77,20 +77,20 @@ bool flux_multi2_supported(const gcmf_plan *pl, int S) {
   return pl->kind == K_FLUX && !pl->g.area_weighted && S >= 5 && S <= 8;
 }
 
-template <typename T, typename FB> static int launch_f2_s(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
+template <typename T, typename FB> static int launch_f2_s(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) {
   switch (a.S) {
-    case 5: return launch_f2<T, FB, 5>(pl, a, s);
-    case 6: return launch_f2<T, FB, 6>(pl, a, s);
-    case 7: return launch_f2<T, FB, 7>(pl, a, s);
-    case 8: return launch_f2<T, FB, 8>(pl, a, s);
+    case 5: return launch_f2<T, FB, 5>(pl, cv, a, s);
+    case 6: return launch_f2<T, FB, 6>(pl, cv, a, s);
+    case 7: return launch_f2<T, FB, 7>(pl, cv, a, s);
+    case 8: return launch_f2<T, FB, 8>(pl, cv, a, s);
   }
   return GCMF_ERR_INVALID_ARG;
 }
 
-int launch_flux_multi2(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
-  if (pl->d.dtype == GCMF_F64) return launch_f2_s<double, double>(pl, a, s);
-  if (a.fb_is_f32) return launch_f2_s<float, float>(pl, a, s);
-  return launch_f2_s<float, double>(pl, a, s);
+int launch_flux_multi2(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) {
+  if (pl->d.dtype == GCMF_F64) return launch_f2_s<double, double>(pl, cv, a, s);
+  if (a.fb_is_f32) return launch_f2_s<float, float>(pl, cv, a, s);
+  return launch_f2_s<float, double>(pl, cv, a, s);
 }
 
 }  // namespace gcmf

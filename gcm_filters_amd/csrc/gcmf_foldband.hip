@@ -279,8 +279,8 @@ __global__ __launch_bounds__(NT) void k_fold_band(const FoldBandP<T, FB> P) {
 }
 
 template <typename T, typename FB, int KIND, bool BACK, int NT, bool PB = false>
-static int launch_fb_nt(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
-  const Geom &g = pl->g;
+static int launch_fb_nt(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) {
+  const Geom g = view_geom(pl, cv);
   FoldBandP<T, FB> P{};
   P.u0 = (const T *)a.u0;
   P.v0 = (const T *)a.v0;
@@ -301,8 +301,8 @@ static int launch_fb_nt(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
   P.cN = (const T *)g.coef[1];
   P.ra = (const T *)g.coef[2];
   P.mbits = g.mbits;
-  P.lbits = pl->lbits;
-  P.mper = pl->mask_per_field;
+  P.lbits = cv.lbits;
+  P.mper = cv.mask_per_field;
   P.area = (const T *)g.area;
   P.nx = g.nx;
   P.rows = g.rows;
@@ -312,7 +312,7 @@ static int launch_fb_nt(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
   P.last = a.last;
   P.area_weighted = (KIND == K_FLUX) ? 0 : g.area_weighted;
   // backward: f is masked in every launch (k_ringc does the same); forward: only a first launch whose land k_land_fix restores
-  P.zero_land = (pl->lbits && pl->n_land > 0 && (BACK || (a.first && a.ring_first))) ? 1 : 0;
+  P.zero_land = (cv.lbits && cv.n_land > 0 && (BACK || (a.first && a.ring_first))) ? 1 : 0;
   P.bstride = (long long)g.rows * g.nx;
   for (int t = 0; t < MAX_S; ++t) P.pk[t] = t < a.S ? a.pk[t] : 0.0;
   P.p0 = a.p0;
@@ -322,11 +322,11 @@ static int launch_fb_nt(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
                (KIND == K_FLUX ? 0 : (size_t)FB_CELLS);
   static bool attr_set = false;  // per instantiation
   if constexpr (PB) {   // a filter bank's launch: the coefficients from the plan's reversed table (launch_ringc_bank_sf sets the same five)
-    P.ptab = pl->bank_rev;
-    P.pstride = (int)pl->bank_stride;
+    P.ptab = cv.bank_rev;
+    P.pstride = (int)cv.bank_stride;
     P.poff = a.lvl - 1;
-    P.nfield = (int)pl->bank_nfield;
-    P.ent0 = (int)pl->entry0;
+    P.nfield = (int)cv.bank_nfield;
+    P.ent0 = (int)cv.entry0;
     lds += (size_t)(MAX_S + 1) * sizeof(double);
     if (!attr_set && lds > 48 * 1024) {
       GCMF_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_fold_band<T, FB, KIND, BACK, NT, true>),
@@ -347,8 +347,8 @@ static int launch_fb_nt(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
   return GCMF_OK;
 }
 template <typename T, typename FB, int KIND, bool BACK>
-static int launch_fb(gcmf_plan *pl, const MultiArgs &a, hipStream_t s, bool wide) {
-  return wide ? launch_fb_nt<T, FB, KIND, BACK, 1024>(pl, a, s) : launch_fb_nt<T, FB, KIND, BACK, 256>(pl, a, s);
+static int launch_fb(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s, bool wide) {
+  return wide ? launch_fb_nt<T, FB, KIND, BACK, 1024>(pl, cv, a, s) : launch_fb_nt<T, FB, KIND, BACK, 256>(pl, cv, a, s);
 }
 
 bool fold_band_supported(const gcmf_plan *pl, const MultiArgs &a) {
@@ -359,26 +359,26 @@ bool fold_band_supported(const gcmf_plan *pl, const MultiArgs &a) {
 // The top S rows of an S-step launch on a plan whose last row is the tripole seam.  `backward`: a = the arguments of a k_ringc
 // launch (a.fb_in = the constant input f), otherwise of a forward launch.
 // (wide: 1024 threads per tile, for a band that runs alone)
-int launch_fold_band(gcmf_plan *pl, const MultiArgs &a, bool backward, hipStream_t s, bool wide) {
+int launch_fold_band(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, bool backward, hipStream_t s, bool wide) {
   if (!fold_band_supported(pl, a)) {
     set_error("k_fold_band: not a tripolar scalar plan / depth %d", a.S);
     return GCMF_ERR_UNSUPPORTED;
   }
   const bool f64 = pl->d.dtype == GCMF_F64, flux = pl->kind == K_FLUX;
-  if (pl->bank_n > 0) {   // inside gcmf_apply_bank: every entry its own polynomial (beside or after launch_ringc_bank's strips)
-    if (!backward || !f64 || !flux || pl->stacked || !pl->bank_rev || a.lvl < 1 || (size_t)(a.lvl - 1 + a.S) >= pl->bank_stride) {
+  if (cv.bank_n > 0) {   // inside gcmf_apply_bank: every entry its own polynomial (beside or after launch_ringc_bank's strips)
+    if (!backward || !f64 || !flux || cv.stacked || !cv.bank_rev || a.lvl < 1 || (size_t)(a.lvl - 1 + a.S) >= cv.bank_stride) {
       set_error("k_fold_band (filter bank): not a backward launch of an ordinary f64 flux plan inside gcmf_apply_bank");
       return GCMF_ERR_INVALID_ARG;
     }
-    return wide ? launch_fb_nt<double, double, K_FLUX, true, 1024, true>(pl, a, s) : launch_fb_nt<double, double, K_FLUX, true, 256, true>(pl, a, s);
+    return wide ? launch_fb_nt<double, double, K_FLUX, true, 1024, true>(pl, cv, a, s) : launch_fb_nt<double, double, K_FLUX, true, 256, true>(pl, cv, a, s);
   }
   if (backward) {
-    if (f64) return flux ? launch_fb<double, double, K_FLUX, true>(pl, a, s, wide) : launch_fb<double, double, K_MASK, true>(pl, a, s, wide);
-    return flux ? launch_fb<float, float, K_FLUX, true>(pl, a, s, wide) : launch_fb<float, float, K_MASK, true>(pl, a, s, wide);
+    if (f64) return flux ? launch_fb<double, double, K_FLUX, true>(pl, cv, a, s, wide) : launch_fb<double, double, K_MASK, true>(pl, cv, a, s, wide);
+    return flux ? launch_fb<float, float, K_FLUX, true>(pl, cv, a, s, wide) : launch_fb<float, float, K_MASK, true>(pl, cv, a, s, wide);
   }
-  if (f64) return flux ? launch_fb<double, double, K_FLUX, false>(pl, a, s, wide) : launch_fb<double, double, K_MASK, false>(pl, a, s, wide);
-  if (a.fb_is_f32) return flux ? launch_fb<float, float, K_FLUX, false>(pl, a, s, wide) : launch_fb<float, float, K_MASK, false>(pl, a, s, wide);
-  return flux ? launch_fb<float, double, K_FLUX, false>(pl, a, s, wide) : launch_fb<float, double, K_MASK, false>(pl, a, s, wide);
+  if (f64) return flux ? launch_fb<double, double, K_FLUX, false>(pl, cv, a, s, wide) : launch_fb<double, double, K_MASK, false>(pl, cv, a, s, wide);
+  if (a.fb_is_f32) return flux ? launch_fb<float, float, K_FLUX, false>(pl, cv, a, s, wide) : launch_fb<float, float, K_MASK, false>(pl, cv, a, s, wide);
+  return flux ? launch_fb<float, double, K_FLUX, false>(pl, cv, a, s, wide) : launch_fb<float, double, K_MASK, false>(pl, cv, a, s, wide);
 }
 
 }  // namespace gcmf

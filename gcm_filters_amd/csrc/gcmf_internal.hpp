@@ -181,24 +181,14 @@ struct gcmf_plan {
   // k_land_fix at the end.
   const uint8_t *lbits = nullptr;
   int64_t n_land = 0;
-  // GCMF_MASK_FROM_NAN: for the duration of such a gcmf_apply call (the plan's mutex is held) g.mbits / lbits point at the call's own
-  // planes of mask bytes in the work buffer, one per batch entry (the field's own batch offset addresses them), and n_land says "has land".
-  // Everything that launches holds the mutex; the lock-free queries (land_ok in gcmf_has_land, clenshaw_cut, resident_fits) may see the
-  // call's values from another thread -- include/gcmf.h tells callers not to race them with a flagged call.
-  int mask_per_field = 0;
   // A STACKED plan (gcmf_plan_create_levels): g.coef[0..2] and lbits hold nlev planes of the whole grid, one after the other, and batch
   // entry b of a gcmf_apply call is filtered with level b % nlev.  Only the plain strips of the backward evaluation know the level axis
-  // (k_ringc<..., LV>, k_land_fix): every other schedule, the building blocks and gcmf_laplacian refuse such a plan.  entry0: the index,
-  // within the caller's batch, of the first entry of the chunk that runs now (the host pipeline and very long batches cut a call into
-  // chunks whose boundaries need not be multiples of nlev); written and read under the plan's mutex.
+  // (k_ringc<..., LV>, k_land_fix): every other schedule, the building blocks and gcmf_laplacian refuse such a plan.
+  // g.coef, g.mbits, lbits, n_land, stacked and nlev are written while the plan is created and never again: what a flagged call or a
+  // filter bank sees in their place it carries in its own CallView (below).
   bool stacked = false;
   int64_t nlev = 1;
-  int64_t entry0 = 0;
-  // GCMF_FACES_FROM_NAN (whole f64 plans of IRREGULAR_WITH_LAND, MOM5U, MOM5T): for the duration of such a gcmf_apply launch (the plan's
-  // mutex is held) the plan LOOKS stacked -- g.coef[0..2] and lbits point at the launch's own planes in the work buffer, one per batch entry,
-  // folded from the plan's planes and the entry's NaNs (launch_gap_fold), nlev = the launch's batch, entry0 = 0, n_land says "has land" --
-  // and everything is put back when the launch leaves (GapFaces, gcmf_api.hip).  The lock-free queries may see the launch's values, as
-  // with mask_per_field.  gap_scratch_mb: the most scratch one launch may take (25 bytes per cell and entry); longer batches are cut.
+  // GCMF_FACES_FROM_NAN: the most scratch one launch may take for its folded planes (25 bytes per cell and entry); longer batches are cut.
   int gap_scratch_mb = 4096;   // gcmf_set_option "gap_scratch_mb"
   int zero_land = 1;     // env GCMF_ZERO_LAND=0 turns it off
   int ring = 1;           // env GCMF_RING=0: deep launches stay with k_flux_multi2 / k_scalar_multi
@@ -220,7 +210,6 @@ struct gcmf_plan {
   // blocked forward schedule zeroes land in its state too, but no schedule is trusted: every one other than sched_backward_scalar on
   // an eligible call clears the flag, and so does a work buffer or layout other than the last call's.
   int wet_rows = 3;
-  bool wet_now = false;         // this launch belongs to a gcmf_apply schedule that may take the table (sched_backward_scalar)
   bool pool_clean = false;
   void *pool_base = nullptr;    // the four state planes of the call that runs now (contiguous) ...
   size_t pool_bytes = 0;        // ... 0: the call has no such pool
@@ -243,28 +232,64 @@ struct gcmf_plan {
   double *dev_p = nullptr;   // p[0..n_steps] of the last filter, for k_land_fix
   size_t dev_p_n = 0;
   std::vector<double> host_p;
-  // A FILTER BANK (gcmf_apply_bank; ordinary whole-grid f64 plans of the four flux-form grid types): for the duration of such a call (the plan's mutex
-  // is held) bank_n polynomials of one degree are applied to bank_nfield fields -- entry e of the call is polynomial e / bank_nfield on
-  // field e % bank_nfield, entry0 the first entry of the launch that runs now -- by the plain strips of the backward evaluation alone
-  // (ringc_march<..., PB>, k_land_fix<..., PB>; on TRIPOLAR_POP_WITH_LAND with k_fold_band<..., PB> on the seam's rows), which read the
-  // polynomials from two grow-only tables of bank_stride doubles per row: bank_rev reversed (MultiP::ptab, FoldBandP::ptab) and bank_fwd as
-  // given; bank_host is what both hold (bank_fwd's order).  The lock-free queries may see the call's values, as with mask_per_field.
-  int bank_n = 0;
-  int64_t bank_nfield = 1;
+  // The coefficient tables of the last FILTER BANK (gcmf_apply_bank, gcmf_apply_bank_gaps), a grow-only cache: bank_stride doubles per
+  // polynomial, bank_rev reversed (MultiP::ptab, FoldBandP::ptab) and bank_fwd as given (k_land_fix); bank_host is what both hold
+  // (bank_fwd's order).  A bank call points its CallView at the rows it runs (ensure_bank_tables).
   double *bank_rev = nullptr, *bank_fwd = nullptr;
   size_t bank_cap = 0, bank_stride = 0;   // doubles each table holds; doubles per row
   std::vector<double> bank_host;
-  // A filter bank on GAPPY fields (gcmf_apply_bank_gaps; the three flux-form grid types without a seam): while a launch runs the plan carries
-  // BOTH guards -- GapFaces with nlev = bank_nfield (one folded level per FIELD, entry0 kept: lev0 = entry0 % nlev is the field of the launch's
-  // first entry) and the bank's bank_n / bank_nfield / entry0 -- and launch_ringc / run_schedule take the forms that know both axes
-  // (launch_ringc_bank_gaps, k_land_fix<.., LV, PB>).  The fold is per field, so consecutive launches of one call that find the same fields
-  // folded at the same place in the work buffer (gap_fold_*; cleared when the call begins and leaves) do not fold again.
-  const void *gap_fold_in = nullptr, *gap_fold_at = nullptr;
-  int64_t gap_fold_n = 0;
   std::mutex mu;
 };
 
 namespace gcmf {
+// The grid and the entry layout as ONE CALL sees them.  Every launcher, predicate and cut that a call reaches reads these from the view
+// it is handed, never from the plan, so a call changes nothing on the plan and the C-ABI queries answer for the plan itself at any time.
+//   own_view(pl)           the plan's own planes: the building blocks, the slab drivers, gcmf_laplacian, every query, an unflagged gcmf_apply
+//   GCMF_MASK_FROM_NAN     mbits = lbits = the call's own mask bytes in the work buffer, one plane per batch entry (the field's own batch
+//                          offset addresses them: mask_per_field), n_land says "has land"
+//   GCMF_FACES_FROM_NAN    the view of a STACKED plan whose levels are the launch's entries: coef[0..2] and lbits are planes in the work
+//                          buffer, folded from the plan's planes and each entry's NaNs (launch_gap_fold), nlev = the launch's batch -- so
+//                          the launches are exactly a stacked plan's (launch_ringc_levels, the level form of k_land_fix)
+//   a filter bank          bank_n polynomials of one degree on bank_nfield fields: entry e of the call is polynomial e / bank_nfield on field
+//                          e % bank_nfield, by the plain strips of the backward evaluation alone (ringc_march<..., PB>, k_land_fix<..., PB>;
+//                          on TRIPOLAR_POP_WITH_LAND with k_fold_band<..., PB> on the seam's rows), which read row j of bank_rev / bank_fwd
+//                          (bank_stride doubles each) for polynomial j
+//   ... on gappy fields    both: one folded level per FIELD (nlev = bank_nfield), launch_ringc_bank_gaps and k_land_fix<.., LV, PB>
+// entry0: the index, within the caller's batch, of the first entry of the launch that runs now -- the host pipeline, very long batches and
+// the banks cut a call into launches whose boundaries need not be multiples of nlev or bank_nfield.  The kernels take the level of entry y
+// of a launch as (entry0 % nlev + y) % nlev and its polynomial and field from entry0 + y.
+struct CallView {
+  const void *coef[3];          // cE, cN, 1 / area (the flux kinds)
+  const uint8_t *mbits, *lbits;
+  int64_t n_land;
+  int mask_per_field;
+  bool stacked;
+  int64_t nlev;
+  int64_t entry0;
+  int bank_n;
+  int64_t bank_nfield;
+  const double *bank_rev, *bank_fwd;
+  size_t bank_stride;
+  bool wet_now;                 // the launch belongs to a schedule that may take a wet-row table (sched_backward_scalar)
+};
+inline CallView own_view(const gcmf_plan *pl) {
+  CallView cv{};
+  for (int k = 0; k < 3; ++k) cv.coef[k] = pl->g.coef[k];
+  cv.mbits = pl->g.mbits;
+  cv.lbits = pl->lbits;
+  cv.n_land = pl->n_land;
+  cv.stacked = pl->stacked;
+  cv.nlev = pl->nlev;
+  cv.bank_nfield = 1;
+  return cv;
+}
+// the geometry a kernel's parameters are filled from: the plan's, with the view's coefficient planes and mask bytes
+inline Geom view_geom(const gcmf_plan *pl, const CallView &cv) {
+  Geom g = pl->g;
+  for (int k = 0; k < 3; ++k) g.coef[k] = cv.coef[k];
+  g.mbits = cv.mbits;
+  return g;
+}
 template <typename T> inline const char *tyname() { return sizeof(T) == 8 ? "double" : "float"; }
 // name as rocprofv3 prints it (without "void " and the argument list); weight = recurrence steps per launch
 // geom: the launch geometry of blocked kernels ("H=.. nstrips=.. nwx=.. xcd=.. grid=..x.. rows=.."), what a PMC traffic
@@ -284,35 +309,35 @@ inline std::string launch_geom(int H, int nstrips, int nwx, int xcd, unsigned gx
 }
 size_t dtype_size(int dtype);
 // kernel launchers (defined in gcmf_scalar.hip / gcmf_vector.hip)
-int launch_scalar_step(gcmf_plan *pl, const StepArgs &a, hipStream_t s);
+int launch_scalar_step(gcmf_plan *pl, const CallView &cv, const StepArgs &a, hipStream_t s);
 int launch_vector_step(gcmf_plan *pl, const StepArgs &a, hipStream_t s);
-int launch_scalar_multi(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);
+int launch_scalar_multi(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s);
 bool flux_multi2_supported(const gcmf_plan *pl, int S);
-bool ring_supported(const gcmf_plan *pl, const MultiArgs &a);
-int launch_ring_flux_f32(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);   // gcmf_ring_flux_f32.hip
+bool ring_supported(const gcmf_plan *pl, const CallView &cv, const MultiArgs &a);
+int launch_ring_flux_f32(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s);   // gcmf_ring_flux_f32.hip
 // backward (Clenshaw) evaluation, gcmf_ringc_impl.hpp: one launch of S = 5..9 levels; a.fb_in = the constant input f, a.fb_out =
 // the result (last launch), a.pk[t] = the coefficient of level t + 1 of this launch; cut = ringc_cut()'s answer for the launch
 // (gcmf_ringc_cut.hpp), which the launchers apply: advance_multi asks once and picks the launcher by cut.form
-inline RingcCutIn ringc_cut_in(const gcmf_plan *pl, int rows, bool seam, int64_t nbatch, int S, bool band_beside) {
-  return RingcCutIn{pl->g.nx, rows, seam, (long long)nbatch, S, pl->d.dtype == GCMF_F64, pl->kind, band_beside, pl->mask_per_field != 0,
-                    pl->strip_rows, pl->ringc_xe_rows, pl->ringc_zip, pl->zip_fold, pl->pack_batch, pl->stacked || pl->bank_n > 0};
+inline RingcCutIn ringc_cut_in(const gcmf_plan *pl, const CallView &cv, int rows, bool seam, int64_t nbatch, int S, bool band_beside) {
+  return RingcCutIn{pl->g.nx, rows, seam, (long long)nbatch, S, pl->d.dtype == GCMF_F64, pl->kind, band_beside, cv.mask_per_field != 0,
+                    pl->strip_rows, pl->ringc_xe_rows, pl->ringc_zip, pl->zip_fold, pl->pack_batch, cv.stacked || cv.bank_n > 0};
 }
-int launch_ringc_reg(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_maskz(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_flux(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_flux9(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // nine levels: whole f64 flux grids without a seam (gcmf_ringc_flux9.hip)
-int launch_ringc_levels(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // a stacked plan's plain strips (gcmf_ringc_levels.hip)
-int launch_ringc_bank(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // a filter bank's plain strips (gcmf_ringc_bank.hip)
-int launch_ringc_bank_gaps(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // ... over per-field planes (gcmf_apply_bank_gaps; gcmf_ringc_bank_gaps.hip)
-int launch_ringc_flux_slab(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // no seam's band beside, short strips: early exits (k_ringcs)
-int launch_ringc_flux_slab_f32(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_zip(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // f64 flux plans: pairs of strips zipped at a shared seam, fold strips at the tripole seam (k_ringcz, gcmf_ringc_zip.hip)
+int launch_ringc_reg(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
+int launch_ringc_maskz(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
+int launch_ringc_flux(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
+int launch_ringc_flux9(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // nine levels: whole f64 flux grids without a seam (gcmf_ringc_flux9.hip)
+int launch_ringc_levels(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // a stacked plan's plain strips (gcmf_ringc_levels.hip)
+int launch_ringc_bank(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // a filter bank's plain strips (gcmf_ringc_bank.hip)
+int launch_ringc_bank_gaps(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // ... over per-field planes (gcmf_apply_bank_gaps; gcmf_ringc_bank_gaps.hip)
+int launch_ringc_flux_slab(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // no seam's band beside, short strips: early exits (k_ringcs)
+int launch_ringc_flux_slab_f32(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
+int launch_ringc_zip(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // f64 flux plans: pairs of strips zipped at a shared seam, fold strips at the tripole seam (k_ringcz, gcmf_ringc_zip.hip)
 // k_ringcz's pairs cut from the wet rows of each window (round 7): the table of this launch geometry (built once, cached on the plan), or
 // nullptr where the launch keeps the even cut (not eligible, the policy of option "wet_rows" against the even cut's march, or an error --
 // then *rc says which)
-const WetTable *wet_table(gcmf_plan *pl, const MultiArgs &a, long long even_march, hipStream_t s, int *rc);
-int launch_flux_multi2(gcmf_plan *pl, const MultiArgs &a, hipStream_t s);
-// the on-chip kernel (gcmf_resident.hip): L <= 64 levels of the backward evaluation in ONE launch on a field that fits the register
+const WetTable *wet_table(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, long long even_march, hipStream_t s, int *rc);
+int launch_flux_multi2(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s);
+// the on-chip kernel (gcmf_resident.hip; the plan's own view only): L <= 64 levels of the backward evaluation in ONE launch on a field that fits the register
 // files + LDS of the chip (short slabs, small grids); pk = the L coefficients (a.S / a.pk are ignored)
 bool resident_supported(const gcmf_plan *pl, int row_lo, int row_hi, int L, int n_total, int *why = nullptr);   // fits AND the policy says so (n_total: levels of the whole filter; why: GCMF_RESIDENT_* when not)
 bool resident_fits(const gcmf_plan *pl, int row_lo, int row_hi, int L);
@@ -351,19 +376,19 @@ inline int launch_vec_multi(gcmf_plan *pl, const VecMultiArgs &a, hipStream_t s)
 }
 // S fused steps on rows [row_lo,row_hi) incl. the tripole band when the range ends at the fold row (gcmf_api.hip)
 // backward: m = the arguments of a k_ringc launch (the polynomial evaluated backwards)
-int advance_multi(gcmf_plan *pl, const MultiArgs &m, hipStream_t s, int *launches, bool backward = false);
+int advance_multi(gcmf_plan *pl, const CallView &cv, const MultiArgs &m, hipStream_t s, int *launches, bool backward = false);
 // the tripole seam rows of an S-step launch in one launch (gcmf_foldband.hip)
 bool fold_band_supported(const gcmf_plan *pl, const MultiArgs &a);
-int launch_fold_band(gcmf_plan *pl, const MultiArgs &a, bool backward, hipStream_t s, bool wide = false);
+int launch_fold_band(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, bool backward, hipStream_t s, bool wide = false);
 int launch_prepare(gcmf_plan *pl, const void *const *in, void *const *out, int64_t nbatch, int row_lo,
                    int row_hi, hipStream_t s);
 // the isolated cells' own polynomial, written over out (gcmf_landfix.hip); dp = p[0..n_steps] on the device
-int launch_zero_land(gcmf_plan *pl, void *a, void *b, int64_t nbatch, hipStream_t s, int row_lo = 0, int row_hi = 0);
-int launch_land_fix(gcmf_plan *pl, const void *in, void *out, const double *dp, int n_steps, double c, int fb_is_f32,
+int launch_zero_land(gcmf_plan *pl, const CallView &cv, void *a, void *b, int64_t nbatch, hipStream_t s, int row_lo = 0, int row_hi = 0);
+int launch_land_fix(gcmf_plan *pl, const CallView &cv, const void *in, void *out, const double *dp, int n_steps, double c, int fb_is_f32,
                     int64_t nbatch, hipStream_t s);
-// ... of a filter bank (gcmf_apply_bank): entry e of the launch's nbatch, counted from pl->entry0, is row e / bank_nfield of pl->bank_fwd
+// ... of a filter bank (gcmf_apply_bank): entry e of the launch's nbatch, counted from cv.entry0, is row e / bank_nfield of cv.bank_fwd
 // on field e % bank_nfield of `in`
-int launch_land_fix_bank(gcmf_plan *pl, const void *in, void *out, int n_steps, double c, int64_t nbatch, hipStream_t s);
+int launch_land_fix_bank(gcmf_plan *pl, const CallView &cv, const void *in, void *out, int n_steps, double c, int64_t nbatch, hipStream_t s);
 // plan-time precompute (gcmf_precompute.hip): fills pl->g from the raw global planes (device pointers)
 int precompute(gcmf_plan *pl, const void *const *dplanes, const void *const *hplanes_or_null);
 // ... of a stacked plan (f64 flux kinds without a seam, whole grid): plane k holds plane_levels[k] (1 or pl->nlev) planes

@@ -106,8 +106,8 @@ __global__ __launch_bounds__(256) void k_zero_land(T *a, T *b, const uint8_t *lb
 }
 
 // rows [row_lo, row_hi) of both planes (row_hi <= 0: all rows)
-int launch_zero_land(gcmf_plan *pl, void *a, void *b, int64_t nbatch, hipStream_t s, int row_lo, int row_hi) {
-  if (pl->stacked) {   // (only the forward schedule and gcmf_zero_land zero land in place: neither runs on a stacked plan)
+int launch_zero_land(gcmf_plan *pl, const CallView &cv, void *a, void *b, int64_t nbatch, hipStream_t s, int row_lo, int row_hi) {
+  if (cv.stacked) {   // (only the forward schedule and gcmf_zero_land zero land in place: neither runs on a stacked plan)
     set_error("k_zero_land: not available on a stacked plan (gcmf_plan_create_levels)");
     return GCMF_ERR_UNSUPPORTED;
   }
@@ -119,15 +119,15 @@ int launch_zero_land(gcmf_plan *pl, void *a, void *b, int64_t nbatch, hipStream_
   if (nb > 65536) nb = 65536;
   dim3 block(256), grid((unsigned)nb);
   if (pl->d.dtype == GCMF_F64)
-    hipLaunchKernelGGL(k_zero_land<double>, grid, block, 0, s, (double *)a, (double *)b, pl->lbits, ncell, cell0, nsub, ntotal, pl->mask_per_field);
+    hipLaunchKernelGGL(k_zero_land<double>, grid, block, 0, s, (double *)a, (double *)b, cv.lbits, ncell, cell0, nsub, ntotal, cv.mask_per_field);
   else
-    hipLaunchKernelGGL(k_zero_land<float>, grid, block, 0, s, (float *)a, (float *)b, pl->lbits, ncell, cell0, nsub, ntotal, pl->mask_per_field);
+    hipLaunchKernelGGL(k_zero_land<float>, grid, block, 0, s, (float *)a, (float *)b, cv.lbits, ncell, cell0, nsub, ntotal, cv.mask_per_field);
   GCMF_HIP(hipGetLastError());
   return GCMF_OK;
 }
 
 template <typename T, typename FB>
-static int launch_lf(gcmf_plan *pl, const void *in, void *out, const double *dp, int n_steps, double c, int64_t nbatch,
+static int launch_lf(gcmf_plan *pl, const CallView &cv, const void *in, void *out, const double *dp, int n_steps, double c, int64_t nbatch,
                      hipStream_t s) {
   const long long ncell = (long long)pl->rows_alloc * pl->d.nx, ntotal = ncell * nbatch;
   const T *area = pl->area_weighted ? (const T *)pl->g.area : nullptr;
@@ -136,29 +136,29 @@ static int launch_lf(gcmf_plan *pl, const void *in, void *out, const double *dp,
   dim3 block(256), grid((unsigned)nb);
   const size_t lds = ((size_t)n_steps + 1) * sizeof(double);
   if constexpr (sizeof(T) == 8 && sizeof(FB) == 8) {
-    if (pl->stacked) {   // (f64 flux kinds; one level: the plan's one plane, the ordinary kernel)
-      if (pl->nlev >= 2) {
-        hipLaunchKernelGGL((k_land_fix<T, FB, true, true>), grid, block, lds, s, (const T *)in, (FB *)out, pl->lbits, area, dp, n_steps, c, ncell,
-                           ntotal, (int)pl->nlev | ((int)(pl->entry0 % pl->nlev) << 16), 0);
+    if (cv.stacked) {   // (f64 flux kinds; one level: the plan's one plane, the ordinary kernel)
+      if (cv.nlev >= 2) {
+        hipLaunchKernelGGL((k_land_fix<T, FB, true, true>), grid, block, lds, s, (const T *)in, (FB *)out, cv.lbits, area, dp, n_steps, c, ncell,
+                           ntotal, (int)cv.nlev | ((int)(cv.entry0 % cv.nlev) << 16), 0);
         GCMF_HIP(hipGetLastError());
         return GCMF_OK;
       }
     }
   }
   if (pl->kind == K_FLUX)
-    hipLaunchKernelGGL((k_land_fix<T, FB, true>), grid, block, lds, s, (const T *)in, (FB *)out, pl->lbits, area, dp, n_steps, c,
-                       ncell, ntotal, pl->mask_per_field, 0);
+    hipLaunchKernelGGL((k_land_fix<T, FB, true>), grid, block, lds, s, (const T *)in, (FB *)out, cv.lbits, area, dp, n_steps, c,
+                       ncell, ntotal, cv.mask_per_field, 0);
   else
-    hipLaunchKernelGGL((k_land_fix<T, FB, false>), grid, block, lds, s, (const T *)in, (FB *)out, pl->lbits, area, dp, n_steps,
-                       c, ncell, ntotal, pl->mask_per_field, 0);
+    hipLaunchKernelGGL((k_land_fix<T, FB, false>), grid, block, lds, s, (const T *)in, (FB *)out, cv.lbits, area, dp, n_steps,
+                       c, ncell, ntotal, cv.mask_per_field, 0);
   GCMF_HIP(hipGetLastError());
   return GCMF_OK;
 }
 
-int launch_land_fix_bank(gcmf_plan *pl, const void *in, void *out, int n_steps, double c, int64_t nbatch, hipStream_t s) {
-  // (a plan that looks stacked: gcmf_apply_bank_gaps, one plane of land bytes per field)
-  if (pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || (pl->stacked && pl->nlev != pl->bank_nfield) || pl->area_weighted || pl->bank_n < 1 || !pl->bank_fwd ||
-      pl->bank_stride != (size_t)n_steps + 1 || nbatch < 1 || nbatch > 65535 || (pl->d.nx % 4) != 0) {
+int launch_land_fix_bank(gcmf_plan *pl, const CallView &cv, const void *in, void *out, int n_steps, double c, int64_t nbatch, hipStream_t s) {
+  // (a stacked view: gcmf_apply_bank_gaps, one plane of land bytes per field)
+  if (pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || (cv.stacked && cv.nlev != cv.bank_nfield) || pl->area_weighted || cv.bank_n < 1 || !cv.bank_fwd ||
+      cv.bank_stride != (size_t)n_steps + 1 || nbatch < 1 || nbatch > 65535 || (pl->d.nx % 4) != 0) {
     set_error("k_land_fix (filter bank): not an ordinary f64 flux plan inside gcmf_apply_bank / gcmf_apply_bank_gaps");
     return GCMF_ERR_INVALID_ARG;
   }
@@ -167,21 +167,21 @@ int launch_land_fix_bank(gcmf_plan *pl, const void *in, void *out, int n_steps, 
   if (nb > 32768) nb = 32768;
   dim3 block(256), grid((unsigned)nb, (unsigned)nbatch);
   const size_t lds = ((size_t)n_steps + 1) * sizeof(double);
-  if (pl->stacked)
-    hipLaunchKernelGGL((k_land_fix<double, double, true, true, true>), grid, block, lds, s, (const double *)in, (double *)out, pl->lbits, (const double *)nullptr,
-                       pl->bank_fwd, n_steps, c, ncell, ncell, (int)pl->bank_nfield, (int)pl->entry0);
+  if (cv.stacked)
+    hipLaunchKernelGGL((k_land_fix<double, double, true, true, true>), grid, block, lds, s, (const double *)in, (double *)out, cv.lbits, (const double *)nullptr,
+                       cv.bank_fwd, n_steps, c, ncell, ncell, (int)cv.bank_nfield, (int)cv.entry0);
   else
-    hipLaunchKernelGGL((k_land_fix<double, double, true, false, true>), grid, block, lds, s, (const double *)in, (double *)out, pl->lbits, (const double *)nullptr,
-                       pl->bank_fwd, n_steps, c, ncell, ncell, (int)pl->bank_nfield, (int)pl->entry0);
+    hipLaunchKernelGGL((k_land_fix<double, double, true, false, true>), grid, block, lds, s, (const double *)in, (double *)out, cv.lbits, (const double *)nullptr,
+                       cv.bank_fwd, n_steps, c, ncell, ncell, (int)cv.bank_nfield, (int)cv.entry0);
   GCMF_HIP(hipGetLastError());
   return GCMF_OK;
 }
 
-int launch_land_fix(gcmf_plan *pl, const void *in, void *out, const double *dp, int n_steps, double c, int fb_is_f32,
+int launch_land_fix(gcmf_plan *pl, const CallView &cv, const void *in, void *out, const double *dp, int n_steps, double c, int fb_is_f32,
                     int64_t nbatch, hipStream_t s) {
-  if (pl->d.dtype == GCMF_F64) return launch_lf<double, double>(pl, in, out, dp, n_steps, c, nbatch, s);
-  if (fb_is_f32) return launch_lf<float, float>(pl, in, out, dp, n_steps, c, nbatch, s);
-  return launch_lf<float, double>(pl, in, out, dp, n_steps, c, nbatch, s);
+  if (pl->d.dtype == GCMF_F64) return launch_lf<double, double>(pl, cv, in, out, dp, n_steps, c, nbatch, s);
+  if (fb_is_f32) return launch_lf<float, float>(pl, cv, in, out, dp, n_steps, c, nbatch, s);
+  return launch_lf<float, double>(pl, cv, in, out, dp, n_steps, c, nbatch, s);
 }
 
 }  // namespace gcmf

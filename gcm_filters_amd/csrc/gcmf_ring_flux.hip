@@ -2,5 +2,5 @@
 #include "gcmf_ring_impl.hpp"
 
 namespace gcmf {
-int launch_ring_flux(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) { return launch_ring_kind<K_FLUX>(pl, a, s); }
+int launch_ring_flux(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) { return launch_ring_kind<K_FLUX>(pl, cv, a, s); }
 }  // namespace gcmf

@@ -4,8 +4,8 @@
 #include "gcmf_ring_impl.hpp"
 
 namespace gcmf {
-int launch_ring_flux_f32(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
-  if (a.fb_is_f32) return launch_ring_k<float, float, K_FLUX, 2>(pl, a, s);
-  return launch_ring_k<float, double, K_FLUX, 2>(pl, a, s);
+int launch_ring_flux_f32(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) {
+  if (a.fb_is_f32) return launch_ring_k<float, float, K_FLUX, 2>(pl, cv, a, s);
+  return launch_ring_k<float, double, K_FLUX, 2>(pl, cv, a, s);
 }
 }  // namespace gcmf

@@ -412,12 +412,12 @@ __global__ __launch_bounds__(256, 1) void k_ring(const MultiP<T, FB> P) {
 }
 
 template <typename T, typename FB, int KIND, int S, bool FIRST, int VEC = 16 / (int)sizeof(T)>
-static int launch_ring_sf(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
+static int launch_ring_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) {
   constexpr int W = 64 * VEC;
   constexpr int M = (S + VEC - 1) / VEC * VEC;
   constexpr int WI = W - 2 * M;
   constexpr int R = RingGeom::R;
-  const Geom &g = pl->g;
+  const Geom g = view_geom(pl, cv);
   MultiP<T, FB> P;
   P.u0 = (const T *)a.u0;
   P.v0 = (const T *)a.v0;
@@ -431,8 +431,8 @@ static int launch_ring_sf(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
   P.zrow = (const T *)pl->zero_row;
   P.nfb = pl->ring_nfb;
   P.mbits = g.mbits;
-  P.lbits = (FIRST && pl->n_land > 0) ? pl->lbits : nullptr;
-  P.mper = pl->mask_per_field;
+  P.lbits = (FIRST && cv.n_land > 0) ? cv.lbits : nullptr;
+  P.mper = cv.mask_per_field;
   P.area = (const T *)g.area;
   P.nx = g.nx;
   P.rows = g.rows;
@@ -468,7 +468,7 @@ static int launch_ring_sf(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
   P.zigzag = 0;
   bool own = false;   // (GCMF_MASK_FROM_NAN: the instantiation that adds the entry's offset to its mask row pointers)
   if constexpr (KIND == K_MASKZ) {
-    own = pl->mask_per_field != 0;
+    own = cv.mask_per_field != 0;
     if (own) hipLaunchKernelGGL((k_ring<T, FB, KIND, S, FIRST, VEC, true>), grid, block, 0, s, P);
   }
   if (!own) hipLaunchKernelGGL((k_ring<T, FB, KIND, S, FIRST, VEC>), grid, block, 0, s, P);
@@ -479,29 +479,29 @@ static int launch_ring_sf(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
   return GCMF_OK;
 }
 
-template <typename T, typename FB, int KIND, int S, int VEC> static int launch_ring_s(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
-  return a.first ? launch_ring_sf<T, FB, KIND, S, true, VEC>(pl, a, s) : launch_ring_sf<T, FB, KIND, S, false, VEC>(pl, a, s);
+template <typename T, typename FB, int KIND, int S, int VEC> static int launch_ring_s(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) {
+  return a.first ? launch_ring_sf<T, FB, KIND, S, true, VEC>(pl, cv, a, s) : launch_ring_sf<T, FB, KIND, S, false, VEC>(pl, cv, a, s);
 }
 
-template <typename T, typename FB, int KIND, int VEC = 16 / (int)sizeof(T)> static int launch_ring_k(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
+template <typename T, typename FB, int KIND, int VEC = 16 / (int)sizeof(T)> static int launch_ring_k(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) {
   switch (a.S) {
-    case 5: return launch_ring_s<T, FB, KIND, 5, VEC>(pl, a, s);
-    case 6: return launch_ring_s<T, FB, KIND, 6, VEC>(pl, a, s);
-    case 7: return launch_ring_s<T, FB, KIND, 7, VEC>(pl, a, s);
-    case 8: return launch_ring_s<T, FB, KIND, 8, VEC>(pl, a, s);
+    case 5: return launch_ring_s<T, FB, KIND, 5, VEC>(pl, cv, a, s);
+    case 6: return launch_ring_s<T, FB, KIND, 6, VEC>(pl, cv, a, s);
+    case 7: return launch_ring_s<T, FB, KIND, 7, VEC>(pl, cv, a, s);
+    case 8: return launch_ring_s<T, FB, KIND, 8, VEC>(pl, cv, a, s);
   }
   return GCMF_ERR_INVALID_ARG;
 }
 
 // one translation unit per stencil kind (compile time): the dtype dispatch
-template <int KIND> static int launch_ring_kind(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
-  if (pl->d.dtype == GCMF_F64) return launch_ring_k<double, double, KIND>(pl, a, s);
+template <int KIND> static int launch_ring_kind(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) {
+  if (pl->d.dtype == GCMF_F64) return launch_ring_k<double, double, KIND>(pl, cv, a, s);
   if constexpr (KIND == K_FLUX) {
     // f32 state of the flux kinds: its own translation unit (gcmf_ring_flux_f32.hip, two cells per lane)
-    return launch_ring_flux_f32(pl, a, s);
+    return launch_ring_flux_f32(pl, cv, a, s);
   } else {
-    if (a.fb_is_f32) return launch_ring_k<float, float, KIND>(pl, a, s);
-    return launch_ring_k<float, double, KIND>(pl, a, s);
+    if (a.fb_is_f32) return launch_ring_k<float, float, KIND>(pl, cv, a, s);
+    return launch_ring_k<float, double, KIND>(pl, cv, a, s);
   }
 }
 

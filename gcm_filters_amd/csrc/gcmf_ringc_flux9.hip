@@ -11,8 +11,8 @@
 #include "gcmf_ringc_impl.hpp"
 
 namespace gcmf {
-int launch_ringc_flux9(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+int launch_ringc_flux9(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
   if (pl->d.dtype != GCMF_F64 || a.S != 9) return GCMF_ERR_INVALID_ARG;
-  return a.first ? launch_ringc_sf<double, K_FLUX, 9, true>(pl, a, cut, s) : launch_ringc_sf<double, K_FLUX, 9, false>(pl, a, cut, s);
+  return a.first ? launch_ringc_sf<double, K_FLUX, 9, true>(pl, cv, a, cut, s) : launch_ringc_sf<double, K_FLUX, 9, false>(pl, cv, a, cut, s);
 }
 }  // namespace gcmf

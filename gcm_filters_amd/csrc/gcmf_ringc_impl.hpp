@@ -742,8 +742,8 @@ __global__ __launch_bounds__(256, 1) void k_ringcz(const MultiP<T, T> P) {
 
 // What every backward scalar launch passes to its kernel: the caller's planes, the plan's coefficient planes, and the cut (ringc_cut,
 // gcmf_ringc_cut.hpp) -- nothing about the geometry is worked out here
-template <typename T> static void ringc_params(MultiP<T, T> &P, const gcmf_plan *pl, const MultiArgs &a, const RingcCut &c) {
-  const Geom &g = pl->g;
+template <typename T> static void ringc_params(MultiP<T, T> &P, const gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &c) {
+  const Geom g = view_geom(pl, cv);
   P.u0 = (const T *)a.u0;
   P.v0 = (const T *)a.v0;
   P.uo = (T *)a.uo;
@@ -761,11 +761,11 @@ template <typename T> static void ringc_params(MultiP<T, T> &P, const gcmf_plan 
   P.zrow = (const T *)pl->zero_row;
   P.nfb = pl->ring_nfb;
   P.mbits = g.mbits;
-  P.lbits = (pl->n_land > 0) ? pl->lbits : nullptr;
-  P.mper = pl->mask_per_field;
-  P.lstride = pl->stacked ? (long long)g.rows * g.nx : 0;
-  P.nlev = (int)pl->nlev;
-  P.lev0 = (int)(pl->entry0 % pl->nlev);
+  P.lbits = (cv.n_land > 0) ? cv.lbits : nullptr;
+  P.mper = cv.mask_per_field;
+  P.lstride = cv.stacked ? (long long)g.rows * g.nx : 0;
+  P.nlev = (int)cv.nlev;
+  P.lev0 = (int)(cv.entry0 % cv.nlev);
   P.area = (const T *)g.area;
   P.nx = g.nx;
   P.rows = g.rows;
@@ -791,7 +791,7 @@ template <typename T> static void ringc_params(MultiP<T, T> &P, const gcmf_plan 
 }
 
 template <typename T, int S, bool FIRST>
-static int launch_ringc_zip_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+static int launch_ringc_zip_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
   const int nrows = a.row_hi - a.row_lo;
   const bool folds = cut.form == RINGC_ZIP_FOLD;
   if (cut.pairs < 1 || nrows - cut.fold_rows < 2 * cut.pairs) {
@@ -803,9 +803,9 @@ static int launch_ringc_zip_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut
   const WetTable *tab = nullptr;
   // (round 9: the table march addresses a plane with 32-bit byte offsets and knows no closed end -- a plane of 4 GiB or more, or a grid
   // that does not wrap in y, keeps the even cut)
-  if (sizeof(T) == 8 && pl->wet_now && !folds && table_rows_ok(pl->g.rows, pl->g.nx, (long long)sizeof(T), pl->g.south_wrap && pl->g.north_wrap)) {
+  if (sizeof(T) == 8 && cv.wet_now && !folds && table_rows_ok(pl->g.rows, pl->g.nx, (long long)sizeof(T), pl->g.south_wrap && pl->g.north_wrap)) {
     int rc = GCMF_OK;
-    tab = wet_table(pl, a, cut.march, s, &rc);
+    tab = wet_table(pl, cv, a, cut.march, s, &rc);
     if (rc) return rc;
     if (tab && !pl->pool_clean) {   // cells no pair owns are read as ghost cells: they must be finite (gcmf_plan::pool_clean)
       if (FIRST) {                  // (a first launch reads no state: nothing the fill could destroy)
@@ -829,7 +829,7 @@ static int launch_ringc_zip_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut
     c.xe = ringc_zip_exits(tab->H, S, pl->ringc_zip);
   }
   MultiP<T, T> P;
-  ringc_params(P, pl, a, c);
+  ringc_params(P, pl, cv, a, c);
   if (tab) {
     P.utab = (const int4 *)tab->dev;
     P.nunits = tab->nunits;
@@ -857,9 +857,9 @@ static int launch_ringc_zip_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut
 
 // k_ringc / k_ringcs (XE) on whole strips, k_ringcp on a packed batch: as the cut says
 template <typename T, int KIND, int S, bool FIRST, bool XE = false>
-static int launch_ringc_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+static int launch_ringc_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
   MultiP<T, T> P;
-  ringc_params(P, pl, a, cut);
+  ringc_params(P, pl, cv, a, cut);
   const int nrows = a.row_hi - a.row_lo;
   dim3 block(256), grid(cut.grid_x, cut.grid_y);
   if (cut.form == RINGC_PACKED) {
@@ -879,7 +879,7 @@ static int launch_ringc_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cu
   }
   bool own = false;   // (GCMF_MASK_FROM_NAN: the instantiation that adds the entry's offset to its mask row pointers)
   if constexpr (KIND == K_MASKZ) {
-    own = pl->mask_per_field != 0;
+    own = cv.mask_per_field != 0;
     if (own) hipLaunchKernelGGL((k_ringc<T, KIND, S, FIRST, true>), grid, block, 0, s, P);
   }
   if (!own) hipLaunchKernelGGL((k_ringc<T, KIND, S, FIRST>), grid, block, 0, s, P);
@@ -892,95 +892,95 @@ static int launch_ringc_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cu
 // a stacked plan's launch (gcmf_plan_create_levels): k_ringc<double, K_FLUX, S, FIRST, false, true>; reported under the ordinary kernel's
 // name, as the per-entry-mask instantiation is, with " levels=<nlev>" behind the geometry
 template <int S, bool FIRST>
-static int launch_ringc_levels_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  if (cut.form != RINGC_PLAIN || cut.xe || pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || !pl->stacked) {
+static int launch_ringc_levels_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+  if (cut.form != RINGC_PLAIN || cut.xe || pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || !cv.stacked) {
     set_error("k_ringc (stacked plan): the cut is not the plain strips of an f64 flux plan");
     return GCMF_ERR_INVALID_ARG;
   }
   MultiP<double, double> P;
-  ringc_params(P, pl, a, cut);
+  ringc_params(P, pl, cv, a, cut);
   const int nrows = a.row_hi - a.row_lo;
   dim3 block(256), grid(cut.grid_x, cut.grid_y);
   hipLaunchKernelGGL((k_ringc<double, K_FLUX, S, FIRST, false, true>), grid, block, 0, s, P);
   GCMF_HIP(hipGetLastError());
   note_kernel(pl, std::string("gcmf::k_ringc<double, ") + std::to_string((int)K_FLUX) + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
-              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " levels=" + std::to_string((long long)pl->nlev));
+              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " levels=" + std::to_string((long long)cv.nlev));
   return GCMF_OK;
 }
 
 // a filter bank's launch (gcmf_apply_bank): k_ringc<double, K_FLUX, S, FIRST, true, true>; reported under the ordinary kernel's name,
 // as the stacked plans' instantiation is, with " bank=<nbank>" behind the geometry
 template <int S, bool FIRST>
-static int launch_ringc_bank_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  if (cut.form != RINGC_PLAIN || cut.xe || pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || pl->stacked || pl->bank_n < 1 || !pl->bank_rev ||
-      a.lvl < 1 || (size_t)(a.lvl - 1 + S) >= pl->bank_stride) {
+static int launch_ringc_bank_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+  if (cut.form != RINGC_PLAIN || cut.xe || pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || cv.stacked || cv.bank_n < 1 || !cv.bank_rev ||
+      a.lvl < 1 || (size_t)(a.lvl - 1 + S) >= cv.bank_stride) {
     set_error("k_ringc (filter bank): the cut is not the plain strips of an ordinary f64 flux plan inside gcmf_apply_bank");
     return GCMF_ERR_INVALID_ARG;
   }
   MultiP<double, double> P;
-  ringc_params(P, pl, a, cut);
-  P.ptab = pl->bank_rev;
-  P.pstride = (int)pl->bank_stride;
+  ringc_params(P, pl, cv, a, cut);
+  P.ptab = cv.bank_rev;
+  P.pstride = (int)cv.bank_stride;
   P.poff = a.lvl - 1;
-  P.nfield = (int)pl->bank_nfield;
-  P.ent0 = (int)pl->entry0;
+  P.nfield = (int)cv.bank_nfield;
+  P.ent0 = (int)cv.entry0;
   const int nrows = a.row_hi - a.row_lo;
   dim3 block(256), grid(cut.grid_x, cut.grid_y);
   hipLaunchKernelGGL((k_ringc<double, K_FLUX, S, FIRST, true, true>), grid, block, 0, s, P);
   GCMF_HIP(hipGetLastError());
   note_kernel(pl, std::string("gcmf::k_ringc<double, ") + std::to_string((int)K_FLUX) + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
-              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " bank=" + std::to_string(pl->bank_n));
+              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " bank=" + std::to_string(cv.bank_n));
   return GCMF_OK;
 }
 
-// a filter bank over per-field planes (gcmf_apply_bank_gaps: the plan looks stacked, one level per field, while the bank runs):
+// a filter bank over per-field planes (gcmf_apply_bank_gaps: the view is stacked, one level per field):
 // k_ringc<double, K_FLUX, S, FIRST, true, false>; reported under the ordinary kernel's name with " levels=<nfield> bank=<nbank>" behind the geometry
 template <int S, bool FIRST>
-static int launch_ringc_bank_gaps_sf(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  if (cut.form != RINGC_PLAIN || cut.xe || pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || !pl->stacked || pl->bank_n < 1 || !pl->bank_rev ||
-      pl->nlev != pl->bank_nfield || pl->g.fold || a.lvl < 1 || (size_t)(a.lvl - 1 + S) >= pl->bank_stride) {
+static int launch_ringc_bank_gaps_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+  if (cut.form != RINGC_PLAIN || cut.xe || pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || !cv.stacked || cv.bank_n < 1 || !cv.bank_rev ||
+      cv.nlev != cv.bank_nfield || pl->g.fold || a.lvl < 1 || (size_t)(a.lvl - 1 + S) >= cv.bank_stride) {
     set_error("k_ringc (filter bank over per-field planes): the cut is not the plain strips of an f64 flux plan without a seam inside gcmf_apply_bank_gaps");
     return GCMF_ERR_INVALID_ARG;
   }
   MultiP<double, double> P;
-  ringc_params(P, pl, a, cut);   // (lev0 = entry0 % nlev: the field of the launch's first entry)
-  P.ptab = pl->bank_rev;
-  P.pstride = (int)pl->bank_stride;
+  ringc_params(P, pl, cv, a, cut);   // (lev0 = entry0 % nlev: the field of the launch's first entry)
+  P.ptab = cv.bank_rev;
+  P.pstride = (int)cv.bank_stride;
   P.poff = a.lvl - 1;
-  P.nfield = (int)pl->bank_nfield;
-  P.ent0 = (int)pl->entry0;
+  P.nfield = (int)cv.bank_nfield;
+  P.ent0 = (int)cv.entry0;
   const int nrows = a.row_hi - a.row_lo;
   dim3 block(256), grid(cut.grid_x, cut.grid_y);
   hipLaunchKernelGGL((k_ringc<double, K_FLUX, S, FIRST, true, false>), grid, block, 0, s, P);
   GCMF_HIP(hipGetLastError());
   note_kernel(pl, std::string("gcmf::k_ringc<double, ") + std::to_string((int)K_FLUX) + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
-              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " levels=" + std::to_string((long long)pl->nlev) + " bank=" + std::to_string(pl->bank_n));
+              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " levels=" + std::to_string((long long)cv.nlev) + " bank=" + std::to_string(cv.bank_n));
   return GCMF_OK;
 }
 
 // one stencil kind, one state type (their own translation units: gcmf_ringc_<kind>.hip = f64, gcmf_ringc_<kind>_f32.hip = f32 -- the
 // instantiations of a kind compile for four to five minutes in one unit)
-template <int KIND> static int launch_ringc_kind_f32(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+template <int KIND> static int launch_ringc_kind_f32(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
   // f32 state, four cells per lane, the whole polynomial carried in f32 (f64 result unless GCMF_OUT_F32): the flux kinds since round 3,
   // the REGULAR / land-mask kinds since round 4
   switch (a.S) {
-    case 5: return a.first ? launch_ringc_sf<float, KIND, 5, true>(pl, a, cut, s) : launch_ringc_sf<float, KIND, 5, false>(pl, a, cut, s);
-    case 6: return a.first ? launch_ringc_sf<float, KIND, 6, true>(pl, a, cut, s) : launch_ringc_sf<float, KIND, 6, false>(pl, a, cut, s);
-    case 7: return a.first ? launch_ringc_sf<float, KIND, 7, true>(pl, a, cut, s) : launch_ringc_sf<float, KIND, 7, false>(pl, a, cut, s);
+    case 5: return a.first ? launch_ringc_sf<float, KIND, 5, true>(pl, cv, a, cut, s) : launch_ringc_sf<float, KIND, 5, false>(pl, cv, a, cut, s);
+    case 6: return a.first ? launch_ringc_sf<float, KIND, 6, true>(pl, cv, a, cut, s) : launch_ringc_sf<float, KIND, 6, false>(pl, cv, a, cut, s);
+    case 7: return a.first ? launch_ringc_sf<float, KIND, 7, true>(pl, cv, a, cut, s) : launch_ringc_sf<float, KIND, 7, false>(pl, cv, a, cut, s);
     case 8:   // (never a first launch: clenshaw_cut starts an f32 filter with at most seven levels -- eight spill there)
       if (a.first) break;
-      return launch_ringc_sf<float, KIND, 8, false>(pl, a, cut, s);
+      return launch_ringc_sf<float, KIND, 8, false>(pl, cv, a, cut, s);
   }
   set_error("k_ringc<float>: depth %d%s is not offered", a.S, a.first ? " as a first launch" : "");
   return GCMF_ERR_INVALID_ARG;
 }
 
-template <int KIND> static int launch_ringc_kind_f64(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+template <int KIND> static int launch_ringc_kind_f64(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
   switch (a.S) {
-    case 5: return a.first ? launch_ringc_sf<double, KIND, 5, true>(pl, a, cut, s) : launch_ringc_sf<double, KIND, 5, false>(pl, a, cut, s);
-    case 6: return a.first ? launch_ringc_sf<double, KIND, 6, true>(pl, a, cut, s) : launch_ringc_sf<double, KIND, 6, false>(pl, a, cut, s);
-    case 7: return a.first ? launch_ringc_sf<double, KIND, 7, true>(pl, a, cut, s) : launch_ringc_sf<double, KIND, 7, false>(pl, a, cut, s);
-    case 8: return a.first ? launch_ringc_sf<double, KIND, 8, true>(pl, a, cut, s) : launch_ringc_sf<double, KIND, 8, false>(pl, a, cut, s);
+    case 5: return a.first ? launch_ringc_sf<double, KIND, 5, true>(pl, cv, a, cut, s) : launch_ringc_sf<double, KIND, 5, false>(pl, cv, a, cut, s);
+    case 6: return a.first ? launch_ringc_sf<double, KIND, 6, true>(pl, cv, a, cut, s) : launch_ringc_sf<double, KIND, 6, false>(pl, cv, a, cut, s);
+    case 7: return a.first ? launch_ringc_sf<double, KIND, 7, true>(pl, cv, a, cut, s) : launch_ringc_sf<double, KIND, 7, false>(pl, cv, a, cut, s);
+    case 8: return a.first ? launch_ringc_sf<double, KIND, 8, true>(pl, cv, a, cut, s) : launch_ringc_sf<double, KIND, 8, false>(pl, cv, a, cut, s);
   }
   return GCMF_ERR_INVALID_ARG;
 }

@@ -2,5 +2,5 @@
 #include "gcmf_ringc_impl.hpp"
 
 namespace gcmf {
-int launch_ringc_maskz_f32(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) { return launch_ringc_kind_f32<K_MASKZ>(pl, a, cut, s); }
+int launch_ringc_maskz_f32(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) { return launch_ringc_kind_f32<K_MASKZ>(pl, cv, a, cut, s); }
 }  // namespace gcmf

@@ -109,8 +109,9 @@ int ringc_one_depth(const gcmf_plan *pl, int n_steps, int64_t nbatch) {
 
 template <int S> static int launch_one(gcmf_plan *pl, const double *p, int n_steps, double c, const void *f, void *out, void *const *pool, hipStream_t s) {
   const Geom &g = pl->g;
+  const CallView cv = own_view(pl);   // (run_schedule: never a flagged call, a stacked plan or a bank)
   // the strips of k_ringc<double, K_FLUX, S> on a lone field: whole ring periods, no zipped pairs (the passes share one geometry)
-  RingcCutIn in = ringc_cut_in(pl, g.rows, false, 1, S, false);
+  RingcCutIn in = ringc_cut_in(pl, cv, g.rows, false, 1, S, false);
   in.ringc_zip = in.ringc_xe_rows = 0;
   const RingcCut cut = ringc_cut(in);
   MultiArgs a{};   // (the state planes, the coefficients and first / last are the passes' own: OneP, k_ringc_one)
@@ -122,7 +123,7 @@ template <int S> static int launch_one(gcmf_plan *pl, const double *p, int n_ste
   a.c = c;
   OneP<S> P{};
   MultiP<double, double> &B = P.base;
-  ringc_params(B, pl, a, cut);
+  ringc_params(B, pl, cv, a, cut);
   P.npass = n_steps / S;
   P.nwg = (int)cut.grid_x;
   int dev = 0, ncu = 0;

@@ -3,13 +3,13 @@
 #include "gcmf_wet_cut.hpp"
 
 namespace gcmf {
-int launch_ringc_zip_b(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_zip(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+int launch_ringc_zip_b(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
+int launch_ringc_zip(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
   if (pl->d.dtype != GCMF_F64 || pl->kind != K_FLUX) return GCMF_ERR_INVALID_ARG;
   switch (a.S) {
-    case 9: return a.first ? launch_ringc_zip_sf<double, 9, true>(pl, a, cut, s) : launch_ringc_zip_sf<double, 9, false>(pl, a, cut, s);
+    case 9: return a.first ? launch_ringc_zip_sf<double, 9, true>(pl, cv, a, cut, s) : launch_ringc_zip_sf<double, 9, false>(pl, cv, a, cut, s);
   }
-  return launch_ringc_zip_b(pl, a, cut, s);
+  return launch_ringc_zip_b(pl, cv, a, cut, s);
 }
 // Strips cut from the wet rows of each window (round 7).  A quarter to a third of an ocean grid is land in continents many windows wide:
 // a (window, strip) tile whose 128 columns hold nothing but isolated cells marches its rows for nothing -- the state there is +-0 at every
@@ -22,9 +22,9 @@ int launch_ringc_zip(gcmf_plan *pl, const MultiArgs &a, const RingcCut &cut, hip
 // Round 8: options 3 and 4 take the TIGHT cut instead (wet_cut_tight, gcmf_wet_cut.hpp: no widening, rows needed by a window's owned columns
 // only, the window grid shifted to the coast); options 1 and 2 keep the rules above and the code below.  Either way a pair goes to the
 // device as (x0, lo, mid, hi), x0 = its window's first footprint column.
-static bool land_bytes(gcmf_plan *pl, std::vector<uint8_t> &bits, hipStream_t s, const char *who, int *rc) {
+static bool land_bytes(gcmf_plan *pl, const CallView &cv, std::vector<uint8_t> &bits, hipStream_t s, const char *who, int *rc) {
   bits.resize((size_t)pl->g.rows * pl->g.nx);
-  if (hipMemcpyAsync(bits.data(), pl->lbits, bits.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+  if (hipMemcpyAsync(bits.data(), cv.lbits, bits.size(), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
     set_error("%s: reading the plan's land bytes back failed: %s", who, hipGetErrorString(hipGetLastError()));
     *rc = GCMF_ERR_HIP;
     return false;
@@ -50,7 +50,7 @@ static bool upload_units(gcmf_plan *pl, WetTable &nt, const std::vector<int4> &u
   }
   return true;
 }
-static const WetProfile *wet_profile(gcmf_plan *pl, int WI, hipStream_t s, int *rc) {
+static const WetProfile *wet_profile(gcmf_plan *pl, const CallView &cv, int WI, hipStream_t s, int *rc) {
   for (const WetProfile &p : pl->wet_prof)
     if (p.WI == WI) return &p;
   // once per plan and window width, on the host: the plan's land bytes come back once (rows x nx bytes), a row's windows are ranges of
@@ -58,7 +58,7 @@ static const WetProfile *wet_profile(gcmf_plan *pl, int WI, hipStream_t s, int *
   // the x wrap)
   const int rows = pl->g.rows, nx = pl->g.nx, nwx = (nx + WI - 1) / WI, M = (128 - WI) / 2;
   std::vector<uint8_t> bits;
-  if (!land_bytes(pl, bits, s, "wet_profile", rc)) return nullptr;
+  if (!land_bytes(pl, cv, bits, s, "wet_profile", rc)) return nullptr;
   WetProfile p;
   p.WI = WI;
   p.need.assign((size_t)nwx * rows, 0);
@@ -84,11 +84,11 @@ static const WetProfile *wet_profile(gcmf_plan *pl, int WI, hipStream_t s, int *
   return &pl->wet_prof.back();
 }
 
-const WetTable *wet_table(gcmf_plan *pl, const MultiArgs &a, long long even_march, hipStream_t s, int *rc) {
+const WetTable *wet_table(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, long long even_march, hipStream_t s, int *rc) {
   *rc = GCMF_OK;
   const Geom &g = pl->g;
   const int S = a.S, rows = g.rows, nrows = a.row_hi - a.row_lo;
-  if (!pl->wet_rows || !pl->wet_now || pl->mask_per_field || pl->stacked || pl->n_land <= 0 || !pl->lbits || pl->d.dtype != GCMF_F64 || pl->kind != K_FLUX ||
+  if (!pl->wet_rows || !cv.wet_now || cv.mask_per_field || cv.stacked || cv.n_land <= 0 || !cv.lbits || pl->d.dtype != GCMF_F64 || pl->kind != K_FLUX ||
       g.fold || a.nbatch != 1 || !pl->pool_base || !pl->pool_bytes || S < 5 || S > 9 || nrows < 4)
     return nullptr;
   const bool tight = pl->wet_rows >= 3;
@@ -99,7 +99,7 @@ const WetTable *wet_table(gcmf_plan *pl, const MultiArgs &a, long long even_marc
     // once per plan, launch geometry and cut: the land bytes come back and the host-only planner weighs every offset of the window grid
     // (no profile is kept: each depth of a filter asks once)
     std::vector<uint8_t> bits;
-    if (!land_bytes(pl, bits, s, "wet_table", rc)) return nullptr;
+    if (!land_bytes(pl, cv, bits, s, "wet_table", rc)) return nullptr;
     const WetCut cut = wet_cut_tight(bits.data(), rows, g.nx, S, a.row_lo, a.row_hi);
     WetTable nt;
     nt.S = S; nt.row_lo = a.row_lo; nt.row_hi = a.row_hi; nt.nbatch = a.nbatch; nt.tight = true;
@@ -115,7 +115,7 @@ const WetTable *wet_table(gcmf_plan *pl, const MultiArgs &a, long long even_marc
   }
   if (!t) {
     const int WI = ringc_window(true, S), nwx = (g.nx + WI - 1) / WI, reach = S + 1;
-    const WetProfile *prof = wet_profile(pl, WI, s, rc);
+    const WetProfile *prof = wet_profile(pl, cv, WI, s, rc);
     if (!prof) return nullptr;
     const bool wrap = g.south_wrap && g.north_wrap;
     WetTable nt;

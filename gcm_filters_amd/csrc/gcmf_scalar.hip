@@ -233,8 +233,8 @@ __global__ __launch_bounds__(256) void k_scalar_step(const ScalarP<T, FB> P) {
 }
 
 template <typename T, typename FB, int KIND, int VEC>
-static int launch_k(gcmf_plan *pl, const StepArgs &a, hipStream_t s) {
-  const Geom &g = pl->g;
+static int launch_k(gcmf_plan *pl, const CallView &cv, const StepArgs &a, hipStream_t s) {
+  const Geom g = view_geom(pl, cv);
   ScalarP<T, FB> P;
   P.t1 = (const T *)a.t1[0];
   P.t2 = (const T *)a.t2[0];
@@ -257,7 +257,7 @@ static int launch_k(gcmf_plan *pl, const StepArgs &a, hipStream_t s) {
   P.north_wrap = g.north_wrap;
   P.fold = g.fold;
   P.area_weighted = g.area_weighted;
-  P.mper = pl->mask_per_field;
+  P.mper = cv.mask_per_field;
   P.mode = a.mode;
   P.coef0 = a.coef0;
   P.coef1 = a.coef1;
@@ -280,31 +280,31 @@ static int launch_k(gcmf_plan *pl, const StepArgs &a, hipStream_t s) {
 
 static bool aligned16(const void *p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-template <typename T, typename FB, int KIND> static int launch_kv(gcmf_plan *pl, const StepArgs &a, hipStream_t s) {
+template <typename T, typename FB, int KIND> static int launch_kv(gcmf_plan *pl, const CallView &cv, const StepArgs &a, hipStream_t s) {
   constexpr int V = 16 / sizeof(T);
-  const Geom &g = pl->g;
+  const Geom g = view_geom(pl, cv);
   bool vec_ok = (g.nx % V == 0) && g.nx >= V;
   const void *ptrs[] = {a.t1[0], a.t2[0], a.fb_in[0], a.t0[0], a.fb_out[0], g.coef[0], g.coef[1], g.coef[2], g.area};
   for (const void *p : ptrs) vec_ok = vec_ok && aligned16(p);
   if (KIND == K_MASK) vec_ok = vec_ok && ((reinterpret_cast<uintptr_t>(g.mbits) & (V - 1)) == 0);
-  if (vec_ok) return launch_k<T, FB, KIND, V>(pl, a, s);
-  return launch_k<T, FB, KIND, 1>(pl, a, s);
+  if (vec_ok) return launch_k<T, FB, KIND, V>(pl, cv, a, s);
+  return launch_k<T, FB, KIND, 1>(pl, cv, a, s);
 }
 
-template <typename T, typename FB> static int launch_kind(gcmf_plan *pl, const StepArgs &a, hipStream_t s) {
+template <typename T, typename FB> static int launch_kind(gcmf_plan *pl, const CallView &cv, const StepArgs &a, hipStream_t s) {
   switch (pl->kind) {
-    case K_REG: return launch_kv<T, FB, K_REG>(pl, a, s);
-    case K_MASK: return launch_kv<T, FB, K_MASK>(pl, a, s);
-    case K_FLUX: return launch_kv<T, FB, K_FLUX>(pl, a, s);
+    case K_REG: return launch_kv<T, FB, K_REG>(pl, cv, a, s);
+    case K_MASK: return launch_kv<T, FB, K_MASK>(pl, cv, a, s);
+    case K_FLUX: return launch_kv<T, FB, K_FLUX>(pl, cv, a, s);
   }
   set_error("launch_scalar_step: plan is not a scalar kind");
   return GCMF_ERR_INVALID_ARG;
 }
 
-int launch_scalar_step(gcmf_plan *pl, const StepArgs &a, hipStream_t s) {
-  if (pl->d.dtype == GCMF_F64) return launch_kind<double, double>(pl, a, s);
-  if (a.fb_is_f32) return launch_kind<float, float>(pl, a, s);
-  return launch_kind<float, double>(pl, a, s);
+int launch_scalar_step(gcmf_plan *pl, const CallView &cv, const StepArgs &a, hipStream_t s) {
+  if (pl->d.dtype == GCMF_F64) return launch_kind<double, double>(pl, cv, a, s);
+  if (a.fb_is_f32) return launch_kind<float, float>(pl, cv, a, s);
+  return launch_kind<float, double>(pl, cv, a, s);
 }
 
 // ---- prepare: T_0 = field * area (AreaWeightedMixin.prepare, kernels.py:100-101) or a plain copy ----

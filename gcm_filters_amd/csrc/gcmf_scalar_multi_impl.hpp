@@ -442,12 +442,12 @@ __global__ __launch_bounds__(256, (WavesPerSimd<T, KIND, S>::value)) void k_scal
 
 // ------------------------------------------------------------------------------------------------------
 template <typename T, typename FB, int KIND, int S, int D>
-static int launch_multi_s(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
+static int launch_multi_s(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) {
   constexpr int VEC = 16 / sizeof(T);
   constexpr int W = 64 * VEC;
   constexpr int M = (S + VEC - 1) / VEC * VEC;
   constexpr int WI = W - 2 * M;
-  const Geom &g = pl->g;
+  const Geom g = view_geom(pl, cv);
   MultiP<T, FB> P;
   P.u0 = (const T *)a.u0;
   P.v0 = (const T *)a.v0;
@@ -464,7 +464,7 @@ static int launch_multi_s(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
   P.xcd_per = 0;
   P.zigzag = 0;
   P.mbits = g.mbits;
-  P.mper = pl->mask_per_field;
+  P.mper = cv.mask_per_field;
   P.area = (const T *)g.area;
   P.nx = g.nx;
   P.rows = g.rows;
@@ -504,30 +504,30 @@ static int launch_multi_s(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
   return GCMF_OK;
 }
 
-template <typename T, typename FB, int KIND> static int launch_multi_k(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
+template <typename T, typename FB, int KIND> static int launch_multi_k(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) {
   switch (a.S) {
-    case 2: return launch_multi_s<T, FB, KIND, 2, 2>(pl, a, s);
-    case 3: return launch_multi_s<T, FB, KIND, 3, 2>(pl, a, s);
-    case 4: return pl->prefetch_rows == 1 ? launch_multi_s<T, FB, KIND, 4, 1>(pl, a, s) : launch_multi_s<T, FB, KIND, 4, 2>(pl, a, s);
-    case 5: return launch_multi_s<T, FB, KIND, 5, 1>(pl, a, s);  // 5 and 7 serve remainders (63 = 7 x 8 + 7)
-    case 6: return pl->prefetch_rows == 2 ? launch_multi_s<T, FB, KIND, 6, 2>(pl, a, s) : launch_multi_s<T, FB, KIND, 6, 1>(pl, a, s);
-    case 7: return launch_multi_s<T, FB, KIND, 7, 1>(pl, a, s);
+    case 2: return launch_multi_s<T, FB, KIND, 2, 2>(pl, cv, a, s);
+    case 3: return launch_multi_s<T, FB, KIND, 3, 2>(pl, cv, a, s);
+    case 4: return pl->prefetch_rows == 1 ? launch_multi_s<T, FB, KIND, 4, 1>(pl, cv, a, s) : launch_multi_s<T, FB, KIND, 4, 2>(pl, cv, a, s);
+    case 5: return launch_multi_s<T, FB, KIND, 5, 1>(pl, cv, a, s);  // 5 and 7 serve remainders (63 = 7 x 8 + 7)
+    case 6: return pl->prefetch_rows == 2 ? launch_multi_s<T, FB, KIND, 6, 2>(pl, cv, a, s) : launch_multi_s<T, FB, KIND, 6, 1>(pl, cv, a, s);
+    case 7: return launch_multi_s<T, FB, KIND, 7, 1>(pl, cv, a, s);
     case 8:
       // one wave per SIMD is issue-bound, not latency-bound: a shallower prefetch frees registers (fewer
       // VGPR<->AGPR moves) and measures 4-5 % faster than 2 rows in flight
-      if (pl->prefetch_rows == 2) return launch_multi_s<T, FB, KIND, 8, 2>(pl, a, s);
-      if (pl->prefetch_rows == 3) return launch_multi_s<T, FB, KIND, 8, 3>(pl, a, s);
-      return launch_multi_s<T, FB, KIND, 8, 1>(pl, a, s);
+      if (pl->prefetch_rows == 2) return launch_multi_s<T, FB, KIND, 8, 2>(pl, cv, a, s);
+      if (pl->prefetch_rows == 3) return launch_multi_s<T, FB, KIND, 8, 3>(pl, cv, a, s);
+      return launch_multi_s<T, FB, KIND, 8, 1>(pl, cv, a, s);
   }
   set_error("launch_scalar_multi: unsupported S=%d", a.S);
   return GCMF_ERR_INVALID_ARG;
 }
 
 // one translation unit per stencil kind (compile time): the dtype dispatch of launch_scalar_multi
-template <int KIND> static int launch_multi_kind(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) {
-  if (pl->d.dtype == GCMF_F64) return launch_multi_k<double, double, KIND>(pl, a, s);
-  if (a.fb_is_f32) return launch_multi_k<float, float, KIND>(pl, a, s);
-  return launch_multi_k<float, double, KIND>(pl, a, s);
+template <int KIND> static int launch_multi_kind(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) {
+  if (pl->d.dtype == GCMF_F64) return launch_multi_k<double, double, KIND>(pl, cv, a, s);
+  if (a.fb_is_f32) return launch_multi_k<float, float, KIND>(pl, cv, a, s);
+  return launch_multi_k<float, double, KIND>(pl, cv, a, s);
 }
 
 }  // namespace gcmf

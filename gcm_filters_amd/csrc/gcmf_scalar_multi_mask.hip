@@ -2,5 +2,5 @@
 #include "gcmf_scalar_multi_impl.hpp"
 
 namespace gcmf {
-int launch_multi_mask(gcmf_plan *pl, const MultiArgs &a, hipStream_t s) { return launch_multi_kind<K_MASK>(pl, a, s); }
+int launch_multi_mask(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s) { return launch_multi_kind<K_MASK>(pl, cv, a, s); }
 }  // namespace gcmf

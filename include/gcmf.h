@@ -92,9 +92,9 @@ typedef enum gcmf_dtype { GCMF_F32 = 0, GCMF_F64 = 1 } gcmf_dtype;
                               /* into the plan's work buffer (1 byte per cell and entry); the plan's own mask is never modified, so        */
                               /* flagged and unflagged calls may alternate.  Runs the strip-marching launches (never the on-chip           */
                               /* kernel).  Other plans, gcmf_laplacian, the gcmf_cheb_* building blocks and the slab drivers return        */
-                              /* GCMF_ERR_UNSUPPORTED for it.  While a flagged call runs, the plan's queries that take no lock            */
-                              /* (gcmf_has_land, gcmf_clenshaw_cut[_batch], gcmf_resident_supported) may see the call's own masks         */
-                              /* ("has land"): do not call them from another thread during a flagged gcmf_apply on the same plan.         */
+                              /* GCMF_ERR_UNSUPPORTED for it.  The call's masks are the call's alone: the plan's queries (gcmf_has_land,  */
+                              /* gcmf_clenshaw_cut[_batch], gcmf_bank_cut, gcmf_resident_supported) answer for the plan itself at any     */
+                              /* time, from any thread, also while a flagged call runs on it.                                             */
 #define GCMF_FACES_FROM_NAN 0x40u /* gcmf_apply, whole-grid f64 ORDINARY (not stacked) plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T (host or     */
                               /* device pointers, any nbatch): the same contract as GCMF_MASK_FROM_NAN for the flux-form kinds -- batch    */
                               /* entry b is filtered with wet_mask * [in_b is not NaN]; the output is NaN exactly where the input is;      */
@@ -111,7 +111,7 @@ typedef enum gcmf_dtype { GCMF_F32 = 0, GCMF_F64 = 1 } gcmf_dtype;
                               /* type, f32 plans, row slabs, stacked plans, gcmf_laplacian, the gcmf_cheb_* and gcmf_slab_* building blocks */
                               /* and gcmf_land_fix, the flag combined with GCMF_FORWARD_RECURRENCE or GCMF_MASK_FROM_NAN, and a polynomial  */
                               /* or grid for which the stacked strips offer no backward cut (fewer than five steps, nx not a multiple of 4, */
-                              /* GCMF_CLENSHAW=0 ...).  The lock-free queries are not to be raced with a flagged call, as above.            */
+                              /* GCMF_CLENSHAW=0 ...).  The plan's queries answer for the plan itself at any time, as above.                */
 
 /* Chebyshev step modes for gcmf_cheb_step */
 #define GCMF_STEP_FIRST 0x1u /* T1 = A(T0);            fbar  = p0*T0 + p1*T1                  */
