@@ -93,26 +93,7 @@ static void host_unregister(const void *p) {
 //
 // Tripolar grids: the fold couples column i of the top row with column nx-1-i, i.e. with a DIFFERENT wave of the
 // strip-marching kernel, which therefore stops S rows below the seam; the top S rows ("band") are advanced by k_fold_band.
-// backward: the launcher of the form ringc_cut chose for this launch (gcmf_ringc_cut.hpp has the policy and its measurements)
-static int launch_ringc(gcmf_plan *pl, const CallView &cv, const MultiArgs &m, const RingcCut &cut, hipStream_t s) {
-  if (cut.form == RINGC_NONE) return GCMF_OK;
-  if (cut.form == RINGC_ZIP || cut.form == RINGC_ZIP_FOLD) return launch_ringc_zip(pl, cv, m, cut, s);
-  switch (pl->kind) {
-    case K_REG: return launch_ringc_reg(pl, cv, m, cut, s);
-    case K_MASK: return launch_ringc_maskz(pl, cv, m, cut, s);
-    case K_FLUX:
-      // (gcmf_apply_bank, and gcmf_apply_bank_gaps whose view is stacked, one level per field: always the plain strips, ringc_cut)
-      if (cv.bank_n > 0) return cv.stacked ? launch_ringc_bank_gaps(pl, cv, m, cut, s) : launch_ringc_bank(pl, cv, m, cut, s);
-      if (cv.stacked) return launch_ringc_levels(pl, cv, m, cut, s);   // (always the plain strips: ringc_cut)
-      if (cut.xe) return launch_ringc_flux_slab(pl, cv, m, cut, s);   // (k_ringcs, or k_ringcp's early-exit form)
-      if (m.S == 9) return launch_ringc_flux9(pl, cv, m, cut, s);
-      return launch_ringc_flux(pl, cv, m, cut, s);
-    default: break;
-  }
-  set_error("k_ringc: plan is not a scalar kind");
-  return GCMF_ERR_INVALID_ARG;
-}
-
+// backward: launch_ringc (gcmf_ringc_dispatch.hip) runs the form ringc_cut chose for this launch (gcmf_ringc_cut.hpp has the policy and its measurements)
 int advance_multi(gcmf_plan *pl, const CallView &cv, const MultiArgs &m, hipStream_t s, int *launches, bool backward) {
   const Geom &g = pl->g;
   const int rows = g.rows, S = m.S;

@@ -58,14 +58,15 @@ static bool ringc9_slab_ok(const gcmf_plan *pl) {
 // nullptr if so, otherwise why not.  The one rule gcmf_cheb_multi(GCMF_STEP_CLENSHAW) and gcmf_slab_apply_backward hold a launch to;
 // every depth clenshaw_cut offers for a batch passes it on the plan's whole rows.
 const char *clenshaw_depth_refused(const gcmf_plan *pl, int S, bool first, int64_t nbatch, int64_t row_lo, int64_t row_hi) {
-  if (S < 5 || S > 9) return "a launch of the backward evaluation runs 5..9 levels";
+  // (which depths exist at all, and as a first launch on which state type: ringc_offered, gcmf_ringc_cut.hpp; below: what depends on the plan)
+  if (!ringc_depth_exists(S)) return "a launch of the backward evaluation runs 5..9 levels";
   if (S == 9 && !ringc9_ok(pl) && !ringc9_slab_ok(pl) && !ringc9_fold_ok(pl, own_view(pl), nbatch, row_lo, row_hi)) {
     if (pl->g.fold && pl->full)
       return "nine levels on a tripolar plan need the seam advanced inside the launch (k_ringcz's fold strips: rows up to the seam, at "
              "most 64 fields, a batch the launcher would not pack); k_fold_band stops at eight";
     return "nine levels need an f64 flux-form plan of 64 rows or more (a whole grid, or a row slab with option slab_nines)";
   }
-  if (first && S == 8 && pl->d.dtype != GCMF_F64) return "an f32-state evaluation never starts with eight levels";
+  if (pl->d.dtype != GCMF_F64 && !ringc_offered_any(false, S, first)) return "an f32-state evaluation never starts with eight levels";
   return nullptr;
 }
 
@@ -147,8 +148,9 @@ static int clenshaw_cut_for(const gcmf_plan *pl, const CallView &cv, int n_steps
   int n = 0, left = n_steps;
   while (left > 0) {
     int S = 0;
-    // (f32 state: the first launch -- it also carries the land bits of the rows that become b_n -- spills at eight levels)
-    for (int cand = (n == 0 && pl->d.dtype != GCMF_F64) ? 7 : 8; cand >= 5 && !S; --cand) {
+    // (f32 state: no first launch of eight levels, ringc_offered)
+    for (int cand = 8; cand >= 5 && !S; --cand) {
+      if (!ringc_offered_any(pl->d.dtype == GCMF_F64, cand, n == 0)) continue;
       const int rest = left - cand;
       if (rest == 0 || (rest >= 5 && rest != 9)) S = cand;
     }

@@ -321,7 +321,7 @@ static int launch_fb_nt(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, h
   size_t lds = (size_t)FB_CELLS * sizeof(T) * (2 + (KIND == K_FLUX ? 3 : 0) + (BACK ? 1 : 0)) + (BACK ? 0 : (size_t)FB_CELLS * sizeof(FB)) +
                (KIND == K_FLUX ? 0 : (size_t)FB_CELLS);
   static bool attr_set = false;  // per instantiation
-  if constexpr (PB) {   // a filter bank's launch: the coefficients from the plan's reversed table (launch_ringc_bank_sf sets the same five)
+  if constexpr (PB) {   // a filter bank's launch: the coefficients from the plan's reversed table (launch_ringc_sf<.., PF, ..> sets the same five)
     P.ptab = cv.bank_rev;
     P.pstride = (int)cv.bank_stride;
     P.poff = a.lvl - 1;
@@ -365,7 +365,7 @@ int launch_fold_band(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, bool
     return GCMF_ERR_UNSUPPORTED;
   }
   const bool f64 = pl->d.dtype == GCMF_F64, flux = pl->kind == K_FLUX;
-  if (cv.bank_n > 0) {   // inside gcmf_apply_bank: every entry its own polynomial (beside or after launch_ringc_bank's strips)
+  if (cv.bank_n > 0) {   // inside gcmf_apply_bank: every entry its own polynomial (beside or after the bank's strips)
     if (!backward || !f64 || !flux || cv.stacked || !cv.bank_rev || a.lvl < 1 || (size_t)(a.lvl - 1 + a.S) >= cv.bank_stride) {
       set_error("k_fold_band (filter bank): not a backward launch of an ordinary f64 flux plan inside gcmf_apply_bank");
       return GCMF_ERR_INVALID_ARG;

@@ -249,12 +249,12 @@ namespace gcmf {
 //                          offset addresses them: mask_per_field), n_land says "has land"
 //   GCMF_FACES_FROM_NAN    the view of a STACKED plan whose levels are the launch's entries: coef[0..2] and lbits are planes in the work
 //                          buffer, folded from the plan's planes and each entry's NaNs (launch_gap_fold), nlev = the launch's batch -- so
-//                          the launches are exactly a stacked plan's (launch_ringc_levels, the level form of k_land_fix)
+//                          the launches are exactly a stacked plan's (launch_ringc_sf<.., LV>, the level form of k_land_fix)
 //   a filter bank          bank_n polynomials of one degree on bank_nfield fields: entry e of the call is polynomial e / bank_nfield on field
 //                          e % bank_nfield, by the plain strips of the backward evaluation alone (ringc_march<..., PB>, k_land_fix<..., PB>;
 //                          on TRIPOLAR_POP_WITH_LAND with k_fold_band<..., PB> on the seam's rows), which read row j of bank_rev / bank_fwd
 //                          (bank_stride doubles each) for polynomial j
-//   ... on gappy fields    both: one folded level per FIELD (nlev = bank_nfield), launch_ringc_bank_gaps and k_land_fix<.., LV, PB>
+//   ... on gappy fields    both: one folded level per FIELD (nlev = bank_nfield), launch_ringc_sf<.., PF, !LV> and k_land_fix<.., LV, PB>
 // entry0: the index, within the caller's batch, of the first entry of the launch that runs now -- the host pipeline, very long batches and
 // the banks cut a call into launches whose boundaries need not be multiples of nlev or bank_nfield.  The kernels take the level of entry y
 // of a launch as (entry0 % nlev + y) % nlev and its polynomial and field from entry0 + y.
@@ -291,7 +291,20 @@ inline Geom view_geom(const gcmf_plan *pl, const CallView &cv) {
   return g;
 }
 template <typename T> inline const char *tyname() { return sizeof(T) == 8 ? "double" : "float"; }
-// name as rocprofv3 prints it (without "void " and the argument list); weight = recurrence steps per launch
+// "gcmf::k_ringc<double, 2, 8, true>": a kernel's name with its template arguments as rocprofv3 prints them (bench.py's traffic records and
+// the dispatch tests key on these strings)
+struct KernelArg {
+  std::string text;
+  KernelArg(const char *s) : text(s) {}
+  KernelArg(int v) : text(std::to_string(v)) {}
+  KernelArg(bool b) : text(b ? "true" : "false") {}
+};
+inline std::string kernel_name(const char *kernel, std::initializer_list<KernelArg> args) {
+  std::string name = std::string("gcmf::") + kernel + "<";
+  for (const KernelArg &a : args) name += (&a == args.begin() ? "" : ", ") + a.text;
+  return name + ">";
+}
+// note_kernel: name as rocprofv3 prints it (without "void " and the argument list); weight = recurrence steps per launch
 // geom: the launch geometry of blocked kernels ("H=.. nstrips=.. nwx=.. xcd=.. grid=..x.. rows=.."), what a PMC traffic
 // record of the kernel is only valid for (gcmf_last_kernel_geometry; bench.py load_traffic)
 inline void note_kernel(gcmf_plan *pl, const std::string &name, int weight, const std::string &geom = std::string()) {
@@ -317,21 +330,13 @@ bool ring_supported(const gcmf_plan *pl, const CallView &cv, const MultiArgs &a)
 int launch_ring_flux_f32(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, hipStream_t s);   // gcmf_ring_flux_f32.hip
 // backward (Clenshaw) evaluation, gcmf_ringc_impl.hpp: one launch of S = 5..9 levels; a.fb_in = the constant input f, a.fb_out =
 // the result (last launch), a.pk[t] = the coefficient of level t + 1 of this launch; cut = ringc_cut()'s answer for the launch
-// (gcmf_ringc_cut.hpp), which the launchers apply: advance_multi asks once and picks the launcher by cut.form
+// (gcmf_ringc_cut.hpp), which the launchers apply: advance_multi asks once, and launch_ringc (gcmf_ringc_dispatch.hip) maps the launch to
+// its instantiation -- the one place that does; what has none is GCMF_ERR_INVALID_ARG with the form, state type and depth in the error text
 inline RingcCutIn ringc_cut_in(const gcmf_plan *pl, const CallView &cv, int rows, bool seam, int64_t nbatch, int S, bool band_beside) {
   return RingcCutIn{pl->g.nx, rows, seam, (long long)nbatch, S, pl->d.dtype == GCMF_F64, pl->kind, band_beside, cv.mask_per_field != 0,
                     pl->strip_rows, pl->ringc_xe_rows, pl->ringc_zip, pl->zip_fold, pl->pack_batch, cv.stacked || cv.bank_n > 0};
 }
-int launch_ringc_reg(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_maskz(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_flux(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_flux9(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // nine levels: whole f64 flux grids without a seam (gcmf_ringc_flux9.hip)
-int launch_ringc_levels(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // a stacked plan's plain strips (gcmf_ringc_levels.hip)
-int launch_ringc_bank(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // a filter bank's plain strips (gcmf_ringc_bank.hip)
-int launch_ringc_bank_gaps(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // ... over per-field planes (gcmf_apply_bank_gaps; gcmf_ringc_bank_gaps.hip)
-int launch_ringc_flux_slab(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // no seam's band beside, short strips: early exits (k_ringcs)
-int launch_ringc_flux_slab_f32(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_zip(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);   // f64 flux plans: pairs of strips zipped at a shared seam, fold strips at the tripole seam (k_ringcz, gcmf_ringc_zip.hip)
+int launch_ringc(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
 // k_ringcz's pairs cut from the wet rows of each window (round 7): the table of this launch geometry (built once, cached on the plan), or
 // nullptr where the launch keeps the even cut (not eligible, the policy of option "wet_rows" against the even cut's march, or an error --
 // then *rc says which)

@@ -5,9 +5,5 @@
 #include "gcmf_ringc_impl.hpp"
 
 namespace gcmf {
-int launch_ringc_bank_b(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_bank(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  if (a.S == 9) return a.first ? launch_ringc_bank_sf<9, true>(pl, cv, a, cut, s) : launch_ringc_bank_sf<9, false>(pl, cv, a, cut, s);
-  return launch_ringc_bank_b(pl, cv, a, cut, s);
-}
+GCMF_RINGC_UNIT_bank(GCMF_RINGC_DEFINE)
 }  // namespace gcmf

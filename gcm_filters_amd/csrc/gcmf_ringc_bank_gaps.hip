@@ -5,9 +5,5 @@
 #include "gcmf_ringc_impl.hpp"
 
 namespace gcmf {
-int launch_ringc_bank_gaps_b(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_bank_gaps(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  if (a.S == 9) return a.first ? launch_ringc_bank_gaps_sf<9, true>(pl, cv, a, cut, s) : launch_ringc_bank_gaps_sf<9, false>(pl, cv, a, cut, s);
-  return launch_ringc_bank_gaps_b(pl, cv, a, cut, s);
-}
+GCMF_RINGC_UNIT_bank_gaps(GCMF_RINGC_DEFINE)
 }  // namespace gcmf

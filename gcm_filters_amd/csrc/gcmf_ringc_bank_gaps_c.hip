@@ -2,12 +2,5 @@
 #include "gcmf_ringc_impl.hpp"
 
 namespace gcmf {
-int launch_ringc_bank_gaps_c(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  switch (a.S) {
-    case 7: return a.first ? launch_ringc_bank_gaps_sf<7, true>(pl, cv, a, cut, s) : launch_ringc_bank_gaps_sf<7, false>(pl, cv, a, cut, s);
-    case 6: return a.first ? launch_ringc_bank_gaps_sf<6, true>(pl, cv, a, cut, s) : launch_ringc_bank_gaps_sf<6, false>(pl, cv, a, cut, s);
-  }
-  set_error("k_ringc (filter bank over per-field planes): depth %d is not offered", a.S);
-  return GCMF_ERR_INVALID_ARG;
-}
+GCMF_RINGC_UNIT_bank_gaps_c(GCMF_RINGC_DEFINE)
 }  // namespace gcmf

@@ -76,6 +76,43 @@ enum RingcForm : int {
   RINGC_PACKED        // k_ringcp: the fields of a batch as one column per window, cut into runs
 };
 
+// What a launch enters the kernels as: the rows of the dispatch table (launch_ringc, gcmf_ringc_dispatch.hip) ...
+enum RingcEntry : int {
+  RINGC_E_REG = 0,     // k_ringc / k_ringcp of the REGULAR kinds
+  RINGC_E_MASKZ,       // ... of the land-mask kinds (also with one plane of mask bytes per entry, GCMF_MASK_FROM_NAN)
+  RINGC_E_FLUX,        // ... of the flux kinds, whole ring periods
+  RINGC_E_SLAB,        // the flux kinds with early exits: k_ringcs, k_ringcp's early-exit form
+  RINGC_E_ZIP,         // k_ringcz (RINGC_ZIP, RINGC_ZIP_FOLD)
+  RINGC_E_LEVELS,      // k_ringc on a stacked plan (gcmf_plan_create_levels)
+  RINGC_E_BANK,        // ... of a filter bank (gcmf_apply_bank)
+  RINGC_E_BANK_GAPS,   // ... of a filter bank over per-field planes (gcmf_apply_bank_gaps)
+  RINGC_E_COUNT
+};
+constexpr const char *ringc_entry_name(RingcEntry e) {
+  constexpr const char *names[RINGC_E_COUNT] = {"regular strips", "land-mask strips", "flux strips", "early-exit flux strips", "zipped strips", "stacked plan",
+                                                "filter bank", "filter bank over per-field planes"};
+  return e >= 0 && e < RINGC_E_COUNT ? names[e] : "?";
+}
+// ... and THE statement of which launches exist: an entry form on f64 or f32 state, S levels, as the first launch of an application or a
+// later one.  The translation units gcmf_ringc_*.hip instantiate exactly these (gcmf_ringc_table.hpp; tests/test_ringc_table.py), the
+// dispatcher refuses everything else, and the policies that cut a polynomial into launches ask here.
+//   f64: 5..8 levels everywhere; nine on whole ring periods of the flux kinds and in k_ringcz (the early-exit form of nine was measured and
+//   not built, gcmf_ringc_flux9.hip); f32: the four forms that come per stencil kind, and never a first launch of eight levels -- it also
+//   carries the land bits of the rows that become b_n and spills there.
+constexpr bool ringc_offered(RingcEntry e, bool f64, int S, bool first) {
+  if (e < 0 || e >= RINGC_E_COUNT || S < 5 || S > 9) return false;
+  const bool per_kind = e <= RINGC_E_SLAB;
+  if (!f64) return per_kind && S <= (first ? 7 : 8);
+  return S <= 8 || !(e == RINGC_E_REG || e == RINGC_E_MASKZ || e == RINGC_E_SLAB);
+}
+// some entry form runs S levels on this state type / on any
+constexpr bool ringc_offered_any(bool f64, int S, bool first) {
+  for (int e = 0; e < RINGC_E_COUNT; ++e)
+    if (ringc_offered((RingcEntry)e, f64, S, first)) return true;
+  return false;
+}
+constexpr bool ringc_depth_exists(int S) { return ringc_offered_any(true, S, true) || ringc_offered_any(true, S, false) || ringc_offered_any(false, S, true) || ringc_offered_any(false, S, false); }
+
 struct RingcCutIn {
   int nx, rows;          // columns; rows [row_lo, row_hi) handed to advance_multi ...
   bool seam;             // ... which end at the tripole seam of the plan: fold strips take them all, otherwise k_fold_band takes the top S

@@ -11,8 +11,5 @@
 #include "gcmf_ringc_impl.hpp"
 
 namespace gcmf {
-int launch_ringc_flux9(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  if (pl->d.dtype != GCMF_F64 || a.S != 9) return GCMF_ERR_INVALID_ARG;
-  return a.first ? launch_ringc_sf<double, K_FLUX, 9, true>(pl, cv, a, cut, s) : launch_ringc_sf<double, K_FLUX, 9, false>(pl, cv, a, cut, s);
-}
+GCMF_RINGC_UNIT_flux9(GCMF_RINGC_DEFINE)
 }  // namespace gcmf

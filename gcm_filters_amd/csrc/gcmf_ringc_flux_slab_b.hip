@@ -2,11 +2,5 @@
 #include "gcmf_ringc_impl.hpp"
 
 namespace gcmf {
-int launch_ringc_flux_slab_b(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  switch (a.S) {
-    case 7: return a.first ? launch_ringc_sf<double, K_FLUX, 7, true, true>(pl, cv, a, cut, s) : launch_ringc_sf<double, K_FLUX, 7, false, true>(pl, cv, a, cut, s);
-    case 8: return a.first ? launch_ringc_sf<double, K_FLUX, 8, true, true>(pl, cv, a, cut, s) : launch_ringc_sf<double, K_FLUX, 8, false, true>(pl, cv, a, cut, s);
-  }
-  return GCMF_ERR_INVALID_ARG;
-}
+GCMF_RINGC_UNIT_flux_slab_b(GCMF_RINGC_DEFINE)
 }  // namespace gcmf

@@ -26,9 +26,12 @@
 // below the seam and k_fold_band's backward form (gcmf_foldband.hip) advances those rows beside it.
 #pragma once
 #include "gcmf_ring_impl.hpp"
+#include "gcmf_ringc_table.hpp"
 #include "gcmf_wet_cut.hpp"
 
 namespace gcmf {
+
+static_assert(RINGC_MASKZ == K_MASKZ, "gcmf_ringc_table.hpp names the land-mask kind of the kernels");
 
 // the VEC bytes (mask bits / land bits) of a lane's cells in one load
 template <int VEC> __device__ __forceinline__ unsigned cell_bytes(const uint8_t *p) {
@@ -791,7 +794,7 @@ template <typename T> static void ringc_params(MultiP<T, T> &P, const gcmf_plan 
 }
 
 template <typename T, int S, bool FIRST>
-static int launch_ringc_zip_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+int launch_ringc_zip_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
   const int nrows = a.row_hi - a.row_lo;
   const bool folds = cut.form == RINGC_ZIP_FOLD;
   if (cut.pairs < 1 || nrows - cut.fold_rows < 2 * cut.pairs) {
@@ -850,139 +853,68 @@ static int launch_ringc_zip_sf(gcmf_plan *pl, const CallView &cv, const MultiArg
     hipLaunchKernelGGL((k_ringcz<T, S, FIRST, false>), grid, block, 0, s, P);
   }
   GCMF_HIP(hipGetLastError());
-  note_kernel(pl, std::string("gcmf::k_ringcz<") + tyname<T>() + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ", " + (xe ? "true" : "false") + (tab ? ", true>" : ">"), S,
+  note_kernel(pl, tab ? kernel_name("k_ringcz", {tyname<T>(), S, FIRST, xe, true}) : kernel_name("k_ringcz", {tyname<T>(), S, FIRST, xe}), S,
               launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + (tab ? " units=" + std::to_string(tab->nunits) + (tab->tight ? " xoff=" + std::to_string(tab->xlim - P.nx) : std::string()) : std::string()));
   return GCMF_OK;
 }
 
-// k_ringc / k_ringcs (XE) on whole strips, k_ringcp on a packed batch: as the cut says
-template <typename T, int KIND, int S, bool FIRST, bool XE = false>
-static int launch_ringc_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+// k_ringc / k_ringcs (XE) on whole strips, k_ringcp on a packed batch: as the cut says.
+// PF / LV: the per-entry forms of k_ringc<double, K_FLUX, ...>, which take the same two booleans -- always the plain strips (ringc_cut),
+// reported under the ordinary kernel's name (as the land-mask kinds' per-entry-mask instantiation is) with the form behind the geometry:
+//   LV      a stacked plan (gcmf_plan_create_levels): " levels=<nlev>"
+//   PF, LV  a filter bank (gcmf_apply_bank): " bank=<nbank>"
+//   PF      a filter bank over per-field planes (gcmf_apply_bank_gaps: the view is stacked, one level per field): " levels=<nfield> bank=<nbank>"
+template <typename T, int KIND, int S, bool FIRST, bool XE, bool PF, bool LV>
+int launch_ringc_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
+  constexpr bool ENTRY = PF || LV, BANK = PF, STACKED = PF != LV;
+  static_assert(!ENTRY || (KIND == K_FLUX && sizeof(T) == 8 && !XE), "the per-entry forms are the f64 flux kinds' plain strips");
+  if constexpr (ENTRY) {
+    bool ok = cut.form == RINGC_PLAIN && !cut.xe && pl->kind == K_FLUX && pl->d.dtype == GCMF_F64 && cv.stacked == STACKED;
+    if constexpr (BANK) ok = ok && cv.bank_n >= 1 && cv.bank_rev && a.lvl >= 1 && (size_t)(a.lvl - 1 + S) < cv.bank_stride;
+    if constexpr (BANK && STACKED) ok = ok && cv.nlev == cv.bank_nfield && !pl->g.fold;
+    if (!ok) {
+      set_error(!BANK     ? "k_ringc (stacked plan): the cut is not the plain strips of an f64 flux plan"
+                : !STACKED ? "k_ringc (filter bank): the cut is not the plain strips of an ordinary f64 flux plan inside gcmf_apply_bank"
+                           : "k_ringc (filter bank over per-field planes): the cut is not the plain strips of an f64 flux plan without a seam inside gcmf_apply_bank_gaps");
+      return GCMF_ERR_INVALID_ARG;
+    }
+  }
   MultiP<T, T> P;
-  ringc_params(P, pl, cv, a, cut);
-  const int nrows = a.row_hi - a.row_lo;
+  ringc_params(P, pl, cv, a, cut);   // (a bank over per-field planes: lev0 = entry0 % nlev is the field of the launch's first entry)
+  if constexpr (BANK) {
+    P.ptab = cv.bank_rev;
+    P.pstride = (int)cv.bank_stride;
+    P.poff = a.lvl - 1;
+    P.nfield = (int)cv.bank_nfield;
+    P.ent0 = (int)cv.entry0;
+  }
   dim3 block(256), grid(cut.grid_x, cut.grid_y);
-  if (cut.form == RINGC_PACKED) {
+  std::string name = kernel_name("k_ringc", {tyname<T>(), KIND, S, FIRST});
+  std::string geom = launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, a.row_hi - a.row_lo);
+  if constexpr (ENTRY) {
+    hipLaunchKernelGGL((k_ringc<T, KIND, S, FIRST, PF, LV>), grid, block, 0, s, P);
+    if (STACKED) geom += " levels=" + std::to_string((long long)cv.nlev);
+    if (BANK) geom += " bank=" + std::to_string(cv.bank_n);
+  } else if (cut.form == RINGC_PACKED) {
     hipLaunchKernelGGL((k_ringcp<T, KIND, S, FIRST, XE>), grid, block, 0, s, P);
-    GCMF_HIP(hipGetLastError());
-    note_kernel(pl, std::string("gcmf::k_ringcp<") + tyname<T>() + ", " + std::to_string(KIND) + ", " + std::to_string(S) + ", " +
-                        (FIRST ? "true" : "false") + ", " + (XE ? "true" : "false") + ">", S,
-                launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows));
-    return GCMF_OK;
-  }
-  if constexpr (XE) {
+    name = kernel_name("k_ringcp", {tyname<T>(), KIND, S, FIRST, XE});
+  } else if constexpr (XE) {
     hipLaunchKernelGGL((k_ringcs<T, S, FIRST>), grid, block, 0, s, P);
-    GCMF_HIP(hipGetLastError());
-    note_kernel(pl, std::string("gcmf::k_ringcs<") + tyname<T>() + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
-                launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows));
-    return GCMF_OK;
+    name = kernel_name("k_ringcs", {tyname<T>(), S, FIRST});
+    // (the early-exit units have always compiled the plain k_ringc of their depths as well, which nothing launches from here: named so
+    // that their code objects stay what they were -- dropping it is a change of the device code, to be made and measured on its own)
+    (void)&k_ringc<T, KIND, S, FIRST>;
+  } else {
+    bool own = false;   // (GCMF_MASK_FROM_NAN: the instantiation that adds the entry's offset to its mask row pointers)
+    if constexpr (KIND == K_MASKZ) {
+      own = cv.mask_per_field != 0;
+      if (own) hipLaunchKernelGGL((k_ringc<T, KIND, S, FIRST, true>), grid, block, 0, s, P);
+    }
+    if (!own) hipLaunchKernelGGL((k_ringc<T, KIND, S, FIRST>), grid, block, 0, s, P);
   }
-  bool own = false;   // (GCMF_MASK_FROM_NAN: the instantiation that adds the entry's offset to its mask row pointers)
-  if constexpr (KIND == K_MASKZ) {
-    own = cv.mask_per_field != 0;
-    if (own) hipLaunchKernelGGL((k_ringc<T, KIND, S, FIRST, true>), grid, block, 0, s, P);
-  }
-  if (!own) hipLaunchKernelGGL((k_ringc<T, KIND, S, FIRST>), grid, block, 0, s, P);
   GCMF_HIP(hipGetLastError());
-  note_kernel(pl, std::string("gcmf::k_ringc<") + tyname<T>() + ", " + std::to_string(KIND) + ", " + std::to_string(S) + ", " +
-                      (FIRST ? "true" : "false") + ">", S, launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows));
+  note_kernel(pl, name, S, geom);
   return GCMF_OK;
-}
-
-// a stacked plan's launch (gcmf_plan_create_levels): k_ringc<double, K_FLUX, S, FIRST, false, true>; reported under the ordinary kernel's
-// name, as the per-entry-mask instantiation is, with " levels=<nlev>" behind the geometry
-template <int S, bool FIRST>
-static int launch_ringc_levels_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  if (cut.form != RINGC_PLAIN || cut.xe || pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || !cv.stacked) {
-    set_error("k_ringc (stacked plan): the cut is not the plain strips of an f64 flux plan");
-    return GCMF_ERR_INVALID_ARG;
-  }
-  MultiP<double, double> P;
-  ringc_params(P, pl, cv, a, cut);
-  const int nrows = a.row_hi - a.row_lo;
-  dim3 block(256), grid(cut.grid_x, cut.grid_y);
-  hipLaunchKernelGGL((k_ringc<double, K_FLUX, S, FIRST, false, true>), grid, block, 0, s, P);
-  GCMF_HIP(hipGetLastError());
-  note_kernel(pl, std::string("gcmf::k_ringc<double, ") + std::to_string((int)K_FLUX) + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
-              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " levels=" + std::to_string((long long)cv.nlev));
-  return GCMF_OK;
-}
-
-// a filter bank's launch (gcmf_apply_bank): k_ringc<double, K_FLUX, S, FIRST, true, true>; reported under the ordinary kernel's name,
-// as the stacked plans' instantiation is, with " bank=<nbank>" behind the geometry
-template <int S, bool FIRST>
-static int launch_ringc_bank_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  if (cut.form != RINGC_PLAIN || cut.xe || pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || cv.stacked || cv.bank_n < 1 || !cv.bank_rev ||
-      a.lvl < 1 || (size_t)(a.lvl - 1 + S) >= cv.bank_stride) {
-    set_error("k_ringc (filter bank): the cut is not the plain strips of an ordinary f64 flux plan inside gcmf_apply_bank");
-    return GCMF_ERR_INVALID_ARG;
-  }
-  MultiP<double, double> P;
-  ringc_params(P, pl, cv, a, cut);
-  P.ptab = cv.bank_rev;
-  P.pstride = (int)cv.bank_stride;
-  P.poff = a.lvl - 1;
-  P.nfield = (int)cv.bank_nfield;
-  P.ent0 = (int)cv.entry0;
-  const int nrows = a.row_hi - a.row_lo;
-  dim3 block(256), grid(cut.grid_x, cut.grid_y);
-  hipLaunchKernelGGL((k_ringc<double, K_FLUX, S, FIRST, true, true>), grid, block, 0, s, P);
-  GCMF_HIP(hipGetLastError());
-  note_kernel(pl, std::string("gcmf::k_ringc<double, ") + std::to_string((int)K_FLUX) + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
-              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " bank=" + std::to_string(cv.bank_n));
-  return GCMF_OK;
-}
-
-// a filter bank over per-field planes (gcmf_apply_bank_gaps: the view is stacked, one level per field):
-// k_ringc<double, K_FLUX, S, FIRST, true, false>; reported under the ordinary kernel's name with " levels=<nfield> bank=<nbank>" behind the geometry
-template <int S, bool FIRST>
-static int launch_ringc_bank_gaps_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  if (cut.form != RINGC_PLAIN || cut.xe || pl->kind != K_FLUX || pl->d.dtype != GCMF_F64 || !cv.stacked || cv.bank_n < 1 || !cv.bank_rev ||
-      cv.nlev != cv.bank_nfield || pl->g.fold || a.lvl < 1 || (size_t)(a.lvl - 1 + S) >= cv.bank_stride) {
-    set_error("k_ringc (filter bank over per-field planes): the cut is not the plain strips of an f64 flux plan without a seam inside gcmf_apply_bank_gaps");
-    return GCMF_ERR_INVALID_ARG;
-  }
-  MultiP<double, double> P;
-  ringc_params(P, pl, cv, a, cut);   // (lev0 = entry0 % nlev: the field of the launch's first entry)
-  P.ptab = cv.bank_rev;
-  P.pstride = (int)cv.bank_stride;
-  P.poff = a.lvl - 1;
-  P.nfield = (int)cv.bank_nfield;
-  P.ent0 = (int)cv.entry0;
-  const int nrows = a.row_hi - a.row_lo;
-  dim3 block(256), grid(cut.grid_x, cut.grid_y);
-  hipLaunchKernelGGL((k_ringc<double, K_FLUX, S, FIRST, true, false>), grid, block, 0, s, P);
-  GCMF_HIP(hipGetLastError());
-  note_kernel(pl, std::string("gcmf::k_ringc<double, ") + std::to_string((int)K_FLUX) + ", " + std::to_string(S) + ", " + (FIRST ? "true" : "false") + ">", S,
-              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + " levels=" + std::to_string((long long)cv.nlev) + " bank=" + std::to_string(cv.bank_n));
-  return GCMF_OK;
-}
-
-// one stencil kind, one state type (their own translation units: gcmf_ringc_<kind>.hip = f64, gcmf_ringc_<kind>_f32.hip = f32 -- the
-// instantiations of a kind compile for four to five minutes in one unit)
-template <int KIND> static int launch_ringc_kind_f32(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  // f32 state, four cells per lane, the whole polynomial carried in f32 (f64 result unless GCMF_OUT_F32): the flux kinds since round 3,
-  // the REGULAR / land-mask kinds since round 4
-  switch (a.S) {
-    case 5: return a.first ? launch_ringc_sf<float, KIND, 5, true>(pl, cv, a, cut, s) : launch_ringc_sf<float, KIND, 5, false>(pl, cv, a, cut, s);
-    case 6: return a.first ? launch_ringc_sf<float, KIND, 6, true>(pl, cv, a, cut, s) : launch_ringc_sf<float, KIND, 6, false>(pl, cv, a, cut, s);
-    case 7: return a.first ? launch_ringc_sf<float, KIND, 7, true>(pl, cv, a, cut, s) : launch_ringc_sf<float, KIND, 7, false>(pl, cv, a, cut, s);
-    case 8:   // (never a first launch: clenshaw_cut starts an f32 filter with at most seven levels -- eight spill there)
-      if (a.first) break;
-      return launch_ringc_sf<float, KIND, 8, false>(pl, cv, a, cut, s);
-  }
-  set_error("k_ringc<float>: depth %d%s is not offered", a.S, a.first ? " as a first launch" : "");
-  return GCMF_ERR_INVALID_ARG;
-}
-
-template <int KIND> static int launch_ringc_kind_f64(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  switch (a.S) {
-    case 5: return a.first ? launch_ringc_sf<double, KIND, 5, true>(pl, cv, a, cut, s) : launch_ringc_sf<double, KIND, 5, false>(pl, cv, a, cut, s);
-    case 6: return a.first ? launch_ringc_sf<double, KIND, 6, true>(pl, cv, a, cut, s) : launch_ringc_sf<double, KIND, 6, false>(pl, cv, a, cut, s);
-    case 7: return a.first ? launch_ringc_sf<double, KIND, 7, true>(pl, cv, a, cut, s) : launch_ringc_sf<double, KIND, 7, false>(pl, cv, a, cut, s);
-    case 8: return a.first ? launch_ringc_sf<double, KIND, 8, true>(pl, cv, a, cut, s) : launch_ringc_sf<double, KIND, 8, false>(pl, cv, a, cut, s);
-  }
-  return GCMF_ERR_INVALID_ARG;
 }
 
 }  // namespace gcmf

@@ -4,12 +4,5 @@
 #include "gcmf_ringc_impl.hpp"
 
 namespace gcmf {
-int launch_ringc_levels_b(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_levels(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  switch (a.S) {
-    case 9: return a.first ? launch_ringc_levels_sf<9, true>(pl, cv, a, cut, s) : launch_ringc_levels_sf<9, false>(pl, cv, a, cut, s);
-    case 8: return a.first ? launch_ringc_levels_sf<8, true>(pl, cv, a, cut, s) : launch_ringc_levels_sf<8, false>(pl, cv, a, cut, s);
-  }
-  return launch_ringc_levels_b(pl, cv, a, cut, s);
-}
+GCMF_RINGC_UNIT_levels(GCMF_RINGC_DEFINE)
 }  // namespace gcmf

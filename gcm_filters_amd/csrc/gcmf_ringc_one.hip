@@ -162,7 +162,7 @@ template <int S> static int launch_one(gcmf_plan *pl, const double *p, int n_ste
     return GCMF_OK;
   });
   if (rc) return rc;
-  note_kernel(pl, std::string("gcmf::k_ringc_one<") + std::to_string(S) + ">", n_steps,
+  note_kernel(pl, kernel_name("k_ringc_one", {S}), n_steps,
               launch_geom(B.H, B.nstrips, B.nwx, B.xcd_per > 0, (unsigned)P.nwg, 1, g.rows));
   return GCMF_OK;
 }

@@ -3,8 +3,5 @@
 #include "gcmf_ringc_impl.hpp"
 
 namespace gcmf {
-int launch_ringc_reg_f32(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_reg(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  return pl->d.dtype != GCMF_F64 ? launch_ringc_reg_f32(pl, cv, a, cut, s) : launch_ringc_kind_f64<K_REG>(pl, cv, a, cut, s);
-}
+GCMF_RINGC_UNIT_reg(GCMF_RINGC_DEFINE)
 }  // namespace gcmf

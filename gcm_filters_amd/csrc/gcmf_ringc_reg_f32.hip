@@ -2,5 +2,5 @@
 #include "gcmf_ringc_impl.hpp"
 
 namespace gcmf {
-int launch_ringc_reg_f32(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) { return launch_ringc_kind_f32<K_REG>(pl, cv, a, cut, s); }
+GCMF_RINGC_UNIT_reg_f32(GCMF_RINGC_DEFINE)
 }  // namespace gcmf

@@ -3,14 +3,8 @@
 #include "gcmf_wet_cut.hpp"
 
 namespace gcmf {
-int launch_ringc_zip_b(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_zip(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  if (pl->d.dtype != GCMF_F64 || pl->kind != K_FLUX) return GCMF_ERR_INVALID_ARG;
-  switch (a.S) {
-    case 9: return a.first ? launch_ringc_zip_sf<double, 9, true>(pl, cv, a, cut, s) : launch_ringc_zip_sf<double, 9, false>(pl, cv, a, cut, s);
-  }
-  return launch_ringc_zip_b(pl, cv, a, cut, s);
-}
+GCMF_RINGC_UNIT_zip(GCMF_RINGC_DEFINE)
+
 // Strips cut from the wet rows of each window (round 7).  A quarter to a third of an ocean grid is land in continents many windows wide:
 // a (window, strip) tile whose 128 columns hold nothing but isolated cells marches its rows for nothing -- the state there is +-0 at every
 // level and k_land_fix writes the result.  Leaving such waves out alone would not shorten the launch (it lasts as long as its tallest
@@ -89,7 +83,7 @@ const WetTable *wet_table(gcmf_plan *pl, const CallView &cv, const MultiArgs &a,
   const Geom &g = pl->g;
   const int S = a.S, rows = g.rows, nrows = a.row_hi - a.row_lo;
   if (!pl->wet_rows || !cv.wet_now || cv.mask_per_field || cv.stacked || cv.n_land <= 0 || !cv.lbits || pl->d.dtype != GCMF_F64 || pl->kind != K_FLUX ||
-      g.fold || a.nbatch != 1 || !pl->pool_base || !pl->pool_bytes || S < 5 || S > 9 || nrows < 4)
+      g.fold || a.nbatch != 1 || !pl->pool_base || !pl->pool_bytes || !ringc_offered(RINGC_E_ZIP, true, S, a.first != 0) || nrows < 4)
     return nullptr;
   const bool tight = pl->wet_rows >= 3;
   const WetTable *t = nullptr;

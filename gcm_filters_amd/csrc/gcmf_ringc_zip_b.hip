@@ -2,9 +2,5 @@
 #include "gcmf_ringc_impl.hpp"
 
 namespace gcmf {
-int launch_ringc_zip_c(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s);
-int launch_ringc_zip_b(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, const RingcCut &cut, hipStream_t s) {
-  if (a.S == 8) return a.first ? launch_ringc_zip_sf<double, 8, true>(pl, cv, a, cut, s) : launch_ringc_zip_sf<double, 8, false>(pl, cv, a, cut, s);
-  return launch_ringc_zip_c(pl, cv, a, cut, s);
-}
+GCMF_RINGC_UNIT_zip_b(GCMF_RINGC_DEFINE)
 }  // namespace gcmf
