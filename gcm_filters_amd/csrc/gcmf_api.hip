@@ -1117,8 +1117,8 @@ static int run_whole(gcmf_plan *pl, const double *p, int n_steps, double c, cons
     }
   for (int k = 0; k < pl->ncomp; ++k)
     for (int q = 0; q < pl->ncomp; ++q)
-      if (in[k] == out[q]) {  // the input is read by the first launch, by neighbouring strips and by k_land_fix at the end
-        set_error("gcmf_apply: `out` must not alias `in` (filtering in place is not supported)");
+      if (in[k] == out[q]) {  // (the ranges are compared below, once the plan is known to cover the whole grid: their size is ny * nx)
+        set_error("%s: `out` must not alias `in` (filtering in place is not supported)", lapl_only ? "gcmf_laplacian" : "gcmf_apply");
         return GCMF_ERR_INVALID_ARG;
       }
   if (flags & GCMF_FACES_FROM_NAN) {
@@ -1156,6 +1156,34 @@ static int run_whole(gcmf_plan *pl, const double *p, int n_steps, double c, cons
       set_error("gcmf_apply: a stacked plan of %lld levels takes batches that are multiples of it (entry b runs on level b %% nlev), not %lld",
                 (long long)pl->nlev, (long long)nbatch);
       return GCMF_ERR_INVALID_ARG;
+    }
+  }
+  {
+    // `out` against `in` and against the other `out` plane as BYTE RANGES, as gcmf_apply_bank compares them, host and device pointers
+    // alike (here, where the plan is known to cover the whole grid: a plane is nbatch * ny * nx elements): the input is read by the first launch, by
+    // neighbouring strips, by later launches of the backward evaluation and by k_land_fix at the end, so an `out` that starts a row or a
+    // batch entry into `in` is as wrong as out == in.  (in[0] == in[1] is fine: nothing writes the input.)
+    const size_t cells = (size_t)nbatch * (size_t)pl->d.ny * (size_t)pl->d.nx, its = dtype_size(pl->d.dtype);
+    const size_t ots = lapl_only ? its : ((pl->d.dtype == GCMF_F32 && !(flags & GCMF_OUT_F32)) ? 8 : its);
+    const char *who = lapl_only ? "gcmf_laplacian" : "gcmf_apply";
+    for (int q = 0; q < pl->ncomp; ++q) {
+      const uintptr_t o0 = (uintptr_t)out[q], o1 = o0 + cells * ots;
+      for (int k = 0; k < pl->ncomp; ++k) {
+        const uintptr_t i0 = (uintptr_t)in[k], i1 = i0 + cells * its;
+        if (in[k] == out[q] || (i0 < o1 && o0 < i1)) {
+          set_error("%s: `out` must not alias `in`: the %zu bytes of out[%d] overlap the %zu bytes of in[%d] (filtering in place is not "
+                    "supported)", who, cells * ots, q, cells * its, k);
+          return GCMF_ERR_INVALID_ARG;
+        }
+      }
+      for (int k = 0; k < q; ++k) {
+        const uintptr_t p0 = (uintptr_t)out[k], p1 = p0 + cells * ots;
+        if (out[k] == out[q] || (p0 < o1 && o0 < p1)) {
+          set_error("%s: the %zu bytes of out[%d] overlap those of out[%d]: the components' results need planes of their own", who,
+                    cells * ots, q, k);
+          return GCMF_ERR_INVALID_ARG;
+        }
+      }
     }
   }
   if (nbatch == 0) return GCMF_OK;

@@ -209,8 +209,26 @@ int gcmf_plan_rows(const gcmf_plan *plan, int64_t *rows_alloc, int64_t *first_ow
  * A(x) = -x - c L(x).   `p` has n_steps+1 entries (host memory), n_steps >= 1.
  * `c` = 2/s_max (dimensional Laplacians) or 2/(s_max*dx_min^2)   (filter.py:170-173).
  * `in` / `out`: ncomp pointers (1 scalar, 2 vector) to (nbatch, ny, nx) arrays; `in` has the plan
- * dtype and is not modified; `out` is f64 unless the plan is f32 and GCMF_OUT_F32 is given and must not alias `in`.
+ * dtype and is not modified; `out` is f64 unless the plan is f32 and GCMF_OUT_F32 is given.
  * Only valid on single-slab plans (row_begin = 0, row_end = ny).
+ * THE PLANES OF A CALL (gcmf_apply, gcmf_laplacian, gcmf_apply_bank[_gaps]; host and device pointers alike):
+ *   - Element alignment suffices for every plane: 8 bytes for f64, 4 for f32 (a view into a larger buffer, a slice of a stack).  The
+ *     result does not depend on the alignment, bit for bit.  These launches fall back when a plane of the call is not on a 16-byte
+ *     boundary (same arithmetic per cell, other access widths):
+ *       k_scalar_step            its VEC = 1 form (last template argument)
+ *       k_cgrid_stream           k_cgrid_step
+ *       k_bgrid_stream           k_bgrid_step
+ *       k_cgrid_ringf            k_cgrid_stream2
+ *       k_cgrid_ring             k_cgrid_stream2c, and at most five levels per launch instead of six
+ *       k_pre_isolated (the fold of GCMF_FACES_FROM_NAN and gcmf_apply_bank_gaps)   element loads of the field instead of 16-byte ones
+ *     Every other kernel (the k_ring* / k_ringc* families, k_scalar_multi, k_flux_multi2, k_cgrid_stream2[c], k_bgrid_stream2[c],
+ *     k_fold_band, k_land_fix, k_resident, the banks and the stacked plans) takes element-aligned planes as they are; the alignment
+ *     these check is that of the plan's own coefficient planes, which the library allocates.
+ *   - `out` must not overlap `in` or another `out` plane, as BYTE RANGES: nbatch * ny * nx elements of the plan dtype from in[k],
+ *     of the output type from out[q] (GCMF_ERR_INVALID_ARG names the two planes; nothing is written).  Later launches and k_land_fix
+ *     re-read the input, so an `out` that begins a row or a batch entry into `in` is as wrong as out == in.  in[0] == in[1] is allowed.
+ *   - Nothing outside these byte ranges is read into a result or written: not a vector past the last row, not a row past the
+ *     last strip.  `in` is never modified.  (tests/test_gpu_caller_planes.py)
  * `stream`: hipStream_t to run on.  With GCMF_DEVICE_PTRS the work is enqueued asynchronously on exactly
  * that stream (NULL = the HIP default stream), ordered with the caller's other work on it.  A stream handed in here must stay
  * alive until the NEXT gcmf_apply on this plan has returned (or the plan is destroyed): when that next call arrives on another
