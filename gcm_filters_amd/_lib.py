@@ -536,6 +536,7 @@ class Plan:
     def last_kernel_geometry(self) -> dict:
         """Launch geometry of the kernel last_kernel() named: {"H", "nstrips", "nwx", "xcd", "grid", "rows"} ({} if none)
         (+ "units": a wet-row table's pairs, and behind it "xoff": the first column of the window grid of the tight cut, option "wet_rows" 3 / 4;
+        and behind that "nt": 1 when the launch streamed its state planes, option "stream_state";
         "levels": a stacked plan's; "bank": the polynomials of a filter bank)."""
         buf = C.create_string_buffer(256)
         check(load().gcmf_last_kernel_geometry(self._h, buf, 256))
@@ -567,7 +568,9 @@ class Plan:
         """Named per-plan switch (gcmf_set_option, include/gcmf.h): "cgrid_ring", "cgrid_ring_smax", "cgrid_ring_hmax", "cgrid_ring_ncarry", "pack_batch",
         "single_launch", "ringc9", "ringc_zip", "ringc_smax", "band_seq_cells", "zip_fold", "slab_nines", "clenshaw_f32", "ring_flux_f32", "wet_rows"
         ("wet_rows": 0 the even cut, 3 (default) / 4 the tight wet-row table where it marches 10 % fewer rows / whenever eligible, 1 / 2 the
-        same policies with the wider table of round 7), "gap_scratch_mb" (apply(faces_from_nan=True): the most scratch, in MiB, the
+        same policies with the wider table of round 7), "stream_state" (nine-level launches from a wet-row table load and store their
+        state planes non-temporally so that the constant planes stay in the memory-side cache: 1 (default) where the table's owned cells x
+        65 bytes exceed 256 MiB, 2 whenever such a launch runs, 0 never; same bits), "gap_scratch_mb" (apply(faces_from_nan=True): the most scratch, in MiB, the
         per-entry planes of one launch may take; default 4096, longer batches run as consecutive launches)."""
         check(load().gcmf_set_option(self._h, name.encode(), int(value)))
 

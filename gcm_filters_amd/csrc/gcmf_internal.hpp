@@ -112,6 +112,7 @@ struct WetTable {
   bool tight = false;
   void *dev = nullptr;
   int nunits = 0, H = 0, nstrips = 0, march = 0, xlim = 0;
+  long long cells = 0;   // cells the pairs own (table_owned_cells, gcmf_wet_cut.hpp): what stream_state_ok weighs
 };
 
 }  // namespace gcmf
@@ -210,6 +211,10 @@ struct gcmf_plan {
   // blocked forward schedule zeroes land in its state too, but no schedule is trusted: every one other than sched_backward_scalar on
   // an eligible call clears the flag, and so does a work buffer or layout other than the last call's.
   int wet_rows = 3;
+  // Nine-level table launches (round 10): the state planes streamed with the non-temporal policy (ringc_march<NT>), so that the constant
+  // planes stay in the memory-side cache from launch to launch.  0 never, 1 where the launch moves more than that cache holds
+  // (stream_state_ok, gcmf_wet_cut.hpp; the default), 2 whenever such a launch runs.  gcmf_set_option "stream_state".  Same bits either way.
+  int stream_state = 1;
   bool pool_clean = false;
   void *pool_base = nullptr;    // the four state planes of the call that runs now (contiguous) ...
   size_t pool_bytes = 0;        // ... 0: the call has no such pool

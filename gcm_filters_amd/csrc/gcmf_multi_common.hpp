@@ -20,16 +20,36 @@ template <typename T> __device__ __forceinline__ T msan(T x) {  // numpy.nan_to_
 }
 
 template <typename T, int VEC> struct alignas((sizeof(T) * VEC) > 16 ? 16 : (sizeof(T) * VEC)) MPack { T s[VEC]; };
-template <typename T, int VEC> __device__ __forceinline__ void mload(T (&d)[VEC], const T *p) {
-  const MPack<T, VEC> v = *reinterpret_cast<const MPack<T, VEC> *>(p);
+// NT: the non-temporal policy (the `nt` bit of the global load / store) for bytes that are used once -- a state plane written by one launch,
+// read by the next and dead afterwards -- so that they do not push re-read planes out of the memory-side cache.  One 16-byte vector type,
+// so that the access stays one dwordx4.
+template <typename T, int VEC, bool NT = false> __device__ __forceinline__ void mload(T (&d)[VEC], const T *p) {
+  if constexpr (NT) {
+    static_assert(sizeof(T) * VEC == 16, "the non-temporal forms move 16 bytes");
+    typedef T vt __attribute__((ext_vector_type(VEC)));
+    const vt v = __builtin_nontemporal_load(reinterpret_cast<const vt *>(p));
 #pragma unroll
-  for (int k = 0; k < VEC; ++k) d[k] = v.s[k];
+    for (int k = 0; k < VEC; ++k) d[k] = v[k];
+  } else {
+    const MPack<T, VEC> v = *reinterpret_cast<const MPack<T, VEC> *>(p);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) d[k] = v.s[k];
+  }
 }
-template <typename T, int VEC> __device__ __forceinline__ void mstore(T *p, const T (&d)[VEC]) {
-  MPack<T, VEC> v;
+template <typename T, int VEC, bool NT = false> __device__ __forceinline__ void mstore(T *p, const T (&d)[VEC]) {
+  if constexpr (NT) {
+    static_assert(sizeof(T) * VEC == 16, "the non-temporal forms move 16 bytes");
+    typedef T vt __attribute__((ext_vector_type(VEC)));
+    vt v;
 #pragma unroll
-  for (int k = 0; k < VEC; ++k) v.s[k] = d[k];
-  *reinterpret_cast<MPack<T, VEC> *>(p) = v;
+    for (int k = 0; k < VEC; ++k) v[k] = d[k];
+    __builtin_nontemporal_store(v, reinterpret_cast<vt *>(p));
+  } else {
+    MPack<T, VEC> v;
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) v.s[k] = d[k];
+    *reinterpret_cast<MPack<T, VEC> *>(p) = v;
+  }
 }
 
 // lane i <- lane i-1 / lane i+1 of the same wave by DPP (one VALU move per dword; no LDS crossbar round trip).

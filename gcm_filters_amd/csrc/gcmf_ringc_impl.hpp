@@ -75,8 +75,14 @@ template <bool ZIP> constexpr bool ringc_ramp_on(int t, int ph) { return ZIP ? (
 // PB and LV TOGETHER: a filter bank over per-field planes (gcmf_apply_bank_gaps) -- the launcher sets nlev = nfield and lev0 = ent0 % nfield,
 // so LV's level (lev0 + blockIdx.y) % nlev = (ent0 + blockIdx.y) % nfield is PB's field index: entry e marches with row e / nfield of the table
 // on the input plane, the coefficient planes and the land bytes of field e % nfield.  Both halves as they are; an instantiation of its own.
+// NT (round 10; a table march only, nothing outside `if constexpr (XO)` reads it): the STATE planes are streamed -- the loads of b_{k+1} and
+// b_{k+2} and the stores of the two new states carry the non-temporal policy (mload / mstore<NT>), because each of those bytes is written by
+// one launch, read by the next and dead afterwards, while the four constant planes and the land bytes are read again by every launch: on a
+// grid whose launch moves more than the memory-side cache holds, state lines that do not stay there leave the constants in it
+// (experiments/mall_probe march; the policy is the host's, stream_state_ok in gcmf_wet_cut.hpp).  The constant input f, the coefficient
+// planes and the land bytes keep the default policy; so does every access of the nan_to_num redo march.
 template <typename T, int KIND, int S, bool FIRST, bool SANI, bool XE = false, bool ZIP = false, bool PF = false, bool LV = false, bool XO = false,
-          bool PB = false>
+          bool PB = false, bool NT = false>
 __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx, const int a, const int b, const long long boff, const bool odd,
                                             T *zmine = nullptr, const T *zpart = nullptr, const bool fold = false, const int pos_at = 0,
                                             const int klo = -(1 << 30), const int khi = 1 << 30) {
@@ -90,6 +96,7 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
   static_assert(!ZIP || FLUX, "the seam exchange is the flux kinds' (a carried face flux per level)");
   static_assert(!LV || (FLUX && !ZIP && !PF), "stacked plans: the flux kinds' plain strips");
   static_assert(!XO || ZIP, "a window origin per pair: k_ringcz's table launches");
+  static_assert(!NT || (XO && !SANI && sizeof(T) == 8), "streamed state planes: the f64 table march, not its redo");
   static_assert(!PB || (FLUX && sizeof(T) == 8 && !ZIP && !XE && !PF), "filter banks: the f64 flux kinds' plain strips");
   constexpr bool WATCH = (KIND != K_REG) && !SANI;  // K_REG has no nan_to_num in the reference: NaN spreads by plain arithmetic
   constexpr bool FUSED = true;   // nothing here is bit-identical with numpy anyway: every multiply-add pair is one fma
@@ -254,7 +261,7 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
     constexpr int sl = decltype(slot_c)::value;
     if constexpr (XO) {
       if constexpr (!FIRST) {
-        mload<T, VEC>(G0[sl], reinterpret_cast<const T *>(xat(xbU, xvc)));
+        mload<T, VEC, NT>(G0[sl], reinterpret_cast<const T *>(xat(xbU, xvc)));
       } else {
         mload<T, VEC>(G0[sl], reinterpret_cast<const T *>(xat(xbF, xvc)));
         Zu[sl] = cell_bytes<VEC>(reinterpret_cast<const uint8_t *>(xat(xbZ, xvc / (unsigned)sizeof(T))));
@@ -285,7 +292,7 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
       mload<T, VEC>(ra[sl], reinterpret_cast<const T *>(xat(xbA, oc)));
       mload<T, VEC>(Ff[sl], reinterpret_cast<const T *>(xat(xbF, oc)));
       Zc[sl] = cell_bytes<VEC>(reinterpret_cast<const uint8_t *>(xat(xbZ, oc / (unsigned)sizeof(T))));
-      if constexpr (!FIRST) mload<T, VEC>(V[vs], reinterpret_cast<const T *>(xat(xbV, oc)));
+      if constexpr (!FIRST) mload<T, VEC, NT>(V[vs], reinterpret_cast<const T *>(xat(xbV, oc)));
       return;
     }
     const bool out_c = cout_prev;
@@ -485,10 +492,10 @@ __device__ __forceinline__ bool ringc_march(const MultiP<T, T> &P, const int wx,
     if constexpr (XO) {   // (f64 flux kinds: no finalize(), no f64 copy of an f32 state)
       const unsigned q = (unsigned)(r - S - a);   // the store row in march order, from a: the mirror maps [a, b) onto itself
       if (q < (unsigned)(b - a)) {  // wave-uniform
-        if (keep) mstore<T, VEC>(reinterpret_cast<T *>(xat(xbSu, xsu + colT)), out_u);
+        if (keep) mstore<T, VEC, NT>(reinterpret_cast<T *>(xat(xbSu, xsu + colT)), out_u);
       }
       if (q + 1u < xhv) {
-        if (keep) mstore<T, VEC>(reinterpret_cast<T *>(xat(xbSv, xsu + xstep + colT)), out_v);
+        if (keep) mstore<T, VEC, NT>(reinterpret_cast<T *>(xat(xbSv, xsu + xstep + colT)), out_v);
       }
       xsu += xstep;
       return;
@@ -675,7 +682,9 @@ __global__ __launch_bounds__(256, 1) void k_ringcs(const MultiP<T, T> P) {
 // the table cost the ordinary launch 3-4 % (these marches are paced by their instruction stream, see PF above and DESIGN.md 6).
 // Round 8: a pair's first int is its window's first footprint column x0 (ringc_march<XO>), so that the window grid of a table may start at
 // any even column; the column limit of ownership travels in MultiP::nfw, which a table launch (no fold strips) has no other use for.
-template <typename T, int S, bool FIRST, bool XE, bool TAB>
+// NT (round 10): a table launch that streams its state planes (ringc_march<NT>) -- a kernel of its own again, k_ringcz<T, S, FIRST, XE, true, true>;
+// the redo march is the one every table launch has.
+template <typename T, int S, bool FIRST, bool XE, bool TAB, bool NT = false>
 __device__ __forceinline__ void ringcz_body(const MultiP<T, T> &P, T (*zl)[S * 64 * (16 / sizeof(T))]) {
   constexpr int VEC = 16 / sizeof(T), W = 64 * VEC, M = (S + VEC - 1) / VEC * VEC, WI = W - 2 * M;
   int bx = blockIdx.x;
@@ -719,7 +728,7 @@ __device__ __forceinline__ void ringcz_body(const MultiP<T, T> &P, T (*zl)[S * 6
   }
   const int nbar = P.fold_rows > 0 ? S : S - 1;   // (barriers of a march: one more in a launch with fold strips)
   bool bad = false;
-  if (active) bad = ringc_march<T, K_FLUX, S, FIRST, false, XE, true, false, false, TAB>(P, wx, a, b, boff, odd, zl[w], zl[w ^ 1], fold, pos_at, klo, khi);
+  if (active) bad = ringc_march<T, K_FLUX, S, FIRST, false, XE, true, false, false, TAB, false, NT>(P, wx, a, b, boff, odd, zl[w], zl[w ^ 1], fold, pos_at, klo, khi);
   else
     for (int k = 0; k < nbar; ++k) __syncthreads();
   if (__syncthreads_or(bad ? 1 : 0)) {
@@ -741,6 +750,12 @@ __global__ __launch_bounds__(256, 1) void k_ringcz(const MultiP<T, T> P) {
   static_assert(TAB, "the even cut is k_ringcz<T, S, FIRST, XE>");
   __shared__ __attribute__((aligned(16))) T zl[4][S * 64 * (16 / sizeof(T))];
   ringcz_body<T, S, FIRST, XE, true>(P, zl);
+}
+template <typename T, int S, bool FIRST, bool XE, bool TAB, bool NT>
+__global__ __launch_bounds__(256, 1) void k_ringcz(const MultiP<T, T> P) {
+  static_assert(TAB && NT, "the table launch that streams its state planes");
+  __shared__ __attribute__((aligned(16))) T zl[4][S * 64 * (16 / sizeof(T))];
+  ringcz_body<T, S, FIRST, XE, true, true>(P, zl);
 }
 
 // What every backward scalar launch passes to its kernel: the caller's planes, the plan's coefficient planes, and the cut (ringc_cut,
@@ -840,11 +855,19 @@ int launch_ringc_zip_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, c
   }
   const bool xe = c.xe;
   dim3 block(256), grid(c.grid_x, c.grid_y);
+  // (round 10) nine levels from a table: the state planes streamed where the launch moves more than the memory-side cache holds (option
+  // "stream_state": 0 never, 1 by stream_state_ok, 2 whenever such a launch runs) -- same arithmetic, same bits
+  constexpr bool STREAMS = S == 9 && sizeof(T) == 8;
+  const bool nt = STREAMS && tab && grid.x > 0 && (pl->stream_state >= 2 || (pl->stream_state == 1 && stream_state_ok(tab->cells)));
   if (tab) {
     if constexpr (sizeof(T) == 8) {   // (f64 only: wet_table)
       if (grid.x > 0) {   // (a grid that is all land has no pair: k_land_fix writes the whole result)
-        if (xe) hipLaunchKernelGGL((k_ringcz<T, S, FIRST, true, true>), grid, block, 0, s, P);
-        else hipLaunchKernelGGL((k_ringcz<T, S, FIRST, false, true>), grid, block, 0, s, P);
+        if constexpr (STREAMS) {   // (nt is false at every other depth)
+          if (nt && xe) hipLaunchKernelGGL((k_ringcz<T, S, FIRST, true, true, true>), grid, block, 0, s, P);
+          if (nt && !xe) hipLaunchKernelGGL((k_ringcz<T, S, FIRST, false, true, true>), grid, block, 0, s, P);
+        }
+        if (!nt && xe) hipLaunchKernelGGL((k_ringcz<T, S, FIRST, true, true>), grid, block, 0, s, P);
+        if (!nt && !xe) hipLaunchKernelGGL((k_ringcz<T, S, FIRST, false, true>), grid, block, 0, s, P);
       }
     }
   } else if (xe) {
@@ -854,7 +877,7 @@ int launch_ringc_zip_sf(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, c
   }
   GCMF_HIP(hipGetLastError());
   note_kernel(pl, tab ? kernel_name("k_ringcz", {tyname<T>(), S, FIRST, xe, true}) : kernel_name("k_ringcz", {tyname<T>(), S, FIRST, xe}), S,
-              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + (tab ? " units=" + std::to_string(tab->nunits) + (tab->tight ? " xoff=" + std::to_string(tab->xlim - P.nx) : std::string()) : std::string()));
+              launch_geom(P.H, P.nstrips, P.nwx, P.xcd_per > 0, grid.x, grid.y, nrows) + (tab ? " units=" + std::to_string(tab->nunits) + (tab->tight ? " xoff=" + std::to_string(tab->xlim - P.nx) : std::string()) + (nt ? " nt=1" : "") : std::string()));
   return GCMF_OK;
 }
 

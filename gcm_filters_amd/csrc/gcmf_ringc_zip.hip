@@ -102,6 +102,7 @@ const WetTable *wet_table(gcmf_plan *pl, const CallView &cv, const MultiArgs &a,
       units.reserve(cut.units.size());
       for (const WetUnit &u : cut.units) units.push_back(make_int4(u.x0, u.lo, u.mid, u.hi));
       nt.H = cut.H; nt.nstrips = cut.nstrips; nt.march = cut.march; nt.xlim = g.nx + cut.xoff;
+      nt.cells = table_owned_cells(cut.units.data(), cut.units.size(), S, nt.xlim);
       if (!upload_units(pl, nt, units, rc)) return nullptr;
     }
     pl->wet_tabs.push_back(nt);
@@ -164,7 +165,13 @@ const WetTable *wet_table(gcmf_plan *pl, const CallView &cv, const MultiArgs &a,
       nt.march = (int)ringc_zip_rows(nt.H + S + 1, S, nullptr);
       nt.xlim = g.nx;   // this cut's window grid starts at column 0: window wx's footprint at wx WI - M, ownership below nx
       const int M = (128 - WI) / 2;
-      for (int4 &u : units) u.x = u.x * WI - M;
+      std::vector<WetUnit> owned;
+      owned.reserve(units.size());
+      for (int4 &u : units) {
+        u.x = u.x * WI - M;
+        owned.push_back({u.x, u.y, u.z, u.w});
+      }
+      nt.cells = table_owned_cells(owned.data(), owned.size(), S, nt.xlim);
       if (!upload_units(pl, nt, units, rc)) return nullptr;
     }
     pl->wet_tabs.push_back(nt);

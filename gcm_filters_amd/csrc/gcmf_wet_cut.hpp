@@ -53,6 +53,27 @@ inline bool table_rows_fit32(long long rows, long long nx, long long cell) {
 // (whole grids without a fold wrap); the launcher asks all the same.
 inline bool table_rows_ok(long long rows, long long nx, long long cell, bool wraps_in_y) { return wraps_in_y && table_rows_fit32(rows, nx, cell); }
 
+// Round 10: whether a nine-level table launch streams its state planes (ringc_march<NT>).  Per owned cell a later launch reads four constant
+// planes and a land byte (33 bytes, the same ones in every launch of every application) and reads and writes two state planes (32 bytes, each
+// used once).  The memory-side cache keeps a line while everything moved between two uses of it fits: a launch that moves less than the cache
+// holds finds its STATE there too, written by the launch before, and must leave it there -- the default policy; one that moves more finds
+// nothing, unless the state passes by without staying and the constants alone (with the ghost rows) fit.  The budget is the cache's size.
+constexpr long long STREAM_CACHE_BYTES = 256ll << 20;   // the memory-side cache of an MI355X
+constexpr long long STREAM_CELL_BYTES = 65;             // 4 x 8 + 1 constant, 2 x 8 read and 2 x 8 written state
+inline bool stream_state_ok(long long owned_cells) {
+  return owned_cells > STREAM_CACHE_BYTES / STREAM_CELL_BYTES;   // cells x 65 > budget, for whole cells, without the product
+}
+// the cells the pairs of a table own: window columns [x0 + M, min(x0 + M + WI, xlim)), rows [lo, hi)
+inline long long table_owned_cells(const WetUnit *units, size_t n, int S, int xlim) {
+  const int WI = ringc_window(true, S), M = (128 - WI) / 2;
+  long long cells = 0;
+  for (size_t i = 0; i < n; ++i) {
+    const int c0 = units[i].x0 + M, cols = std::min(c0 + WI, xlim) - c0;
+    if (cols > 0 && units[i].hi > units[i].lo) cells += (long long)cols * (units[i].hi - units[i].lo);
+  }
+  return cells;
+}
+
 namespace wet_detail {
 
 struct Run { int wx, lo, hi; };

@@ -423,7 +423,8 @@ int gcmf_last_kernel(gcmf_plan *plan, char *buf, int n);
  * describes the kernel at the geometry it was profiled with.  A k_ringcz launch whose strips were cut from the wet rows of each
  * window (option "wet_rows") appends " units=<pairs of strips>" (0: a grid that is all land, nothing was launched); H is then the
  * tallest strip and nstrips twice the largest number of pairs of a window.  The tight cut (values 3 and 4 of the option) appends
- * " xoff=<columns>" after that: the column at which its window grid starts. */
+ * " xoff=<columns>" after that: the column at which its window grid starts; " nt=1" after that: the launch streamed its state planes
+ * (option "stream_state"). */
 int gcmf_last_kernel_geometry(gcmf_plan *plan, char *buf, int n);
 /* Wave strips of the register-ring kernels (k_ring) that met a NaN / inf since this was last called and were redone by the
  * general kernel (results are the same; each costs about two strip times).  Synchronises the device; reading resets.  A large
@@ -550,6 +551,11 @@ int gcmf_set_tuning(gcmf_plan *plan, int rows_per_wave, int xcd_remap, int multi
  * exact zero next to land may differ; the FIRST eligible gcmf_apply of a plan builds the tables: it copies the plan's land bytes
  * (one byte per cell) to the host, synchronises the caller's stream and uploads the tables with a blocking copy -- once per plan and
  * launch depth, but not asynchronous and not legal inside a stream capture: capture after one warm-up call, or set 0),
+ * "stream_state" 1 / 0 / 2 (nine-level launches from a wet-row table: the state planes, each byte of which is written by one launch and
+ * read by the next only, are loaded and stored with the non-temporal policy, so that the constant planes every launch re-reads stay in the
+ * 256 MiB memory-side cache; 1 (the default) = where the table's owned cells x 65 bytes exceed that cache -- a smaller launch finds its
+ * state there and keeps the default policy --, 2 = whenever such a launch runs, 0 = never; same bits; gcmf_last_kernel_geometry appends
+ * " nt=1" when the streaming form ran),
  * "gap_scratch_mb" N (GCMF_FACES_FROM_NAN: the most scratch, in MiB, the per-entry planes of one launch may take; default 4096; a batch
  * whose planes need more is cut into consecutive launches of at least one entry; same bits; gcmf_apply_bank_gaps: per field, not per
  * entry, and the FIELDS are cut into runs).  Unknown names: GCMF_ERR_INVALID_ARG. */
