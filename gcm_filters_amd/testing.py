@@ -312,7 +312,8 @@ def coastline_names(tripolar=False):
 
 
 def coastline(name, shape, seed=0, tripolar=False, cuts=()):
-    """Wet mask (1 = ocean, 0 = land; float64) of coastline `name` on `shape` (ny >= 24, nx >= 24), from PCG64(seed).
+    """Wet mask (1 = ocean, 0 = land; float64) of coastline `name` on `shape` (ny >= 24, nx >= 24; `speckle`, `checker` and `all_land`,
+    which place nothing, at any size), from PCG64(seed).
 
     open_south     rows 0 and ny-1 wet along most of x, a land band in mid-grid, land blocks that straddle the x seam
     speckle        each cell land with probability 0.35
@@ -327,7 +328,7 @@ def coastline(name, shape, seed=0, tripolar=False, cuts=()):
 
     `tripolar=True` forces row 0 to land (the tripolar kinds refuse anything else) and is the only thing that does."""
     ny, nx = shape
-    if ny < 24 or nx < 24:
+    if (ny < 24 or nx < 24) and name not in ("speckle", "checker", "all_land"):
         raise ValueError(f"coastline: shape {shape} is smaller than 24 x 24")
     if name not in COASTLINES:
         raise KeyError(name)
@@ -440,6 +441,27 @@ def cgrid_coast_vars(name, shape, seed=0, independent_q=False):
     gv["kappa_iso"] = smooth_kappa(shape, 13)
     gv["kappa_aniso"] = 0.5 * smooth_kappa(shape, 14)
     return {k: gv[k] for k in FIXTURE_ARG_ORDER["VECTOR_C_GRID"]}
+
+
+def roll_rows(r, fields, gv):
+    """(fields, grid variables) rolled by `r` rows along y (``np.roll(axis=-2)``): global row j becomes row (j + r) % ny.  A ring of slabs
+    exchanges only across row ny-1 / row 0, so rolling every plane and the field alike moves that seam onto another row of the same
+    periodic problem (tests/test_gpu_slab_seams.py).  Non-tripolar kinds only: the tripole fold is not periodic in y."""
+    roll = lambda a: np.ascontiguousarray(np.roll(np.asarray(a), int(r), axis=-2))
+    return [roll(f) for f in fields], {k: roll(v) for k, v in gv.items()}
+
+
+def live_seam_faces(wet, kappa_s=None, mom5=False):
+    """Number of faces between row ny-1 and row 0 that carry flux: both cells wet (and, with `kappa_s`, a non-zero kappa on row 0's
+    southern face).  `mom5`: the MOM5 kinds mask the difference along y with ``wet * E(wet)`` of the southern row, as the reference does
+    (oracle/gcmf_oracle.py _mom5u): the seam's faces are live where row ny-1 has two wet cells side by side."""
+    wet = np.asarray(wet)
+    if mom5:
+        return int(((wet[-1] != 0) & (np.roll(wet[-1], -1) != 0)).sum())
+    live = (wet[0] != 0) & (wet[-1] != 0)
+    if kappa_s is not None:
+        live &= np.asarray(kappa_s)[0] != 0
+    return int(live.sum())
 
 
 LAND_TREATMENTS = ("nan", "finite", "mixed")

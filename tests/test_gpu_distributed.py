@@ -44,6 +44,12 @@ CASES = [
     # a sixth slot that is a dict: extras by name.  coast = a coastline of gcm_filters_amd.testing.coastline: rows 0 and ny-1 wet, so the
     # wrap between the last and the first rank carries flux (the fixture mask closes it: row 0 is land)
     ("IRREGULAR_WITH_LAND", (50, 66), 4, 2, "f8", dict(coast="open_south")),
+    # more coastlines on slab boundaries (tests/test_gpu_slab_seams.py runs the table on a ring of one rank): land on the tripole seam of the top
+    # rank (k_fold_band / the fold strips on a slab), one-cell channels and a zonal wall between ranks, a speckle on the uneven 19 / 19 / 20 cut
+    ("TRIPOLAR_POP_WITH_LAND", (48, 64), 8, 2, "f8", dict(coast="fold")),
+    ("IRREGULAR_WITH_LAND", (50, 66), 4, 2, "f8", dict(coast="channels")),
+    ("REGULAR_WITH_LAND", (58, 16), 5, 2, "f4", dict(coast="speckle")),
+    ("REGULAR_WITH_LAND", (58, 16), 5, 2, "f4b", dict(coast="speckle")),
 ]
 
 
@@ -60,6 +66,8 @@ CASES_WIDE = [
     ("VECTOR_C_GRID", (80, 64), 4, 4, "f4"),
     ("IRREGULAR_WITH_LAND", (350, 64), 10, 2, "f8", 27),    # nine levels per launch on slabs of 70 rows
     ("IRREGULAR_WITH_LAND", (90, 64), 8, 2, "f8", dict(coast="open_south")),
+    ("TRIPOLAR_POP_WITH_LAND", (100, 64), 8, 2, "f8", dict(coast="fold")),
+    ("IRREGULAR_WITH_LAND", (90, 64), 8, 2, "f8", dict(coast="on_the_cuts", cuts=(18,))),      # rectangles on either side of every slab boundary
 ]
 
 
@@ -97,8 +105,10 @@ def _worker(rank, world, port, q, exchange="auto"):
             vec = grid in T.VECTOR_GRIDS
             gv = T.vector_grid_vars(grid, shape) if vec else T.scalar_grid_vars(grid, shape)
             if coast:
-                gv["wet_mask"] = T.coastline(coast, shape, seed=55)
-                assert (gv["wet_mask"][0] * gv["wet_mask"][-1]).any()
+                tripolar = grid.startswith("TRIPOLAR")
+                gv["wet_mask"] = T.coastline(coast, shape, seed=55, tripolar=tripolar, cuts=tuple(extra.get("cuts", ())))
+                if not tripolar:
+                    assert (gv["wet_mask"][0] * gv["wet_mask"][-1]).any()
             fields = [np.stack([T.random_field(shape, 7 + 10 * c + b) for b in range(nbatch)]) for c in range(2 if vec else 1)]
             nanland = (not vec) and "wet_mask" in gv and nbatch >= 2   # ocean-like input in the last batch entry
             if nanland:
@@ -160,7 +170,7 @@ def test_slabs_on_one_gpu_match_single_domain(world, exchange):
     res = q.get()
     assert len(res) == len(CASES_WIDE if world == WIDE else CASES)
     for name, (e_one, e_ref) in res.items():
-        f32 = name.endswith(("f4", "f4b"))
+        f32 = name.endswith(("f4", "f4b")) or "-f4-" in name or "-f4b-" in name      # (a coastline's name follows the dtype)
         assert e_one <= (1e-5 if f32 else 1e-13), (name, e_one)   # slab run == single-domain GPU run
         assert e_ref <= (1e-4 if f32 else 1e-11), (name, e_ref)   # and == the reference
 

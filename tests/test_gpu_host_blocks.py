@@ -78,3 +78,78 @@ def test_row_blocks_are_built_lazily_and_really_used(monkeypatch):
     assert np.array_equal(flt.apply(torch.from_numpy(f).cuda()).cpu().numpy(), outs[0])
     clear_plan_cache()
     assert "_host_blocks" not in plan.__dict__     # closing the plan closed the block plans
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# row blocks on coastlines: the block boundaries (and, on the tripolar kinds, the seam the top block owns) on land, straits and gaps
+# ------------------------------------------------------------------------------------------------------------------------------
+def _coast_block_cases():
+    out = []
+    for grid, dt in (("IRREGULAR_WITH_LAND", "f8"), ("REGULAR_WITH_LAND_AREA_WEIGHTED", "f8"), ("REGULAR_WITH_LAND_AREA_WEIGHTED", "f4"),
+                     ("TRIPOLAR_POP_WITH_LAND", "f8"), ("TRIPOLAR_REGULAR_WITH_LAND_AREA_WEIGHTED", "f8")):
+        for coast in ("on_the_cuts", "channels", "speckle") + (("fold",) if grid.startswith("TRIPOLAR") else ()):
+            for nblocks in (2, 3):
+                for n_steps in (11, 19):
+                    out.append((grid, dt, coast, nblocks, n_steps))
+    return out
+
+
+@pytest.mark.parametrize("grid,dt,coast,nblocks,n_steps", _coast_block_cases())
+def test_row_blocks_on_coastlines(grid, dt, coast, nblocks, n_steps):
+    """RowBlockPipeline built directly (choose_blocks wants 128 rows per block) on 96 rows: two and three blocks whose boundaries fall on
+    the rectangles of `on_the_cuts` (cuts = the block height), between the straits of `channels`, in a speckle, and -- tripolar kinds --
+    with land on the seam of the top block (`fold`).  NaN on land, and a NaN in a wet cell on the last row of block 0 and on the first row
+    of the top block: rows every neighbouring block holds as ghost rows.  The pipeline must give the bits of Plan.apply on the parent
+    plan, the oracle's NaN pattern, and an error within test_gpu_dispatch_edges.errors()'s bound."""
+    from types import SimpleNamespace
+    from gcm_filters_amd import _lib
+    from test_gpu_dispatch_edges import errors
+
+    shape = (96, 256) if dt == "f4" else (96, 128)
+    ny, nx = shape
+    height = ny // nblocks
+    tripolar = grid.startswith("TRIPOLAR")
+    gv = T.scalar_grid_vars(grid, shape)
+    gv["wet_mask"] = wet = T.coastline(coast, shape, seed=55, tripolar=tripolar, cuts=(height,))
+    f = T.treat_land(T.random_field(shape, 100), wet, "nan")
+    for j in (height - 1, ny - height):
+        ii = np.nonzero(wet[j])[0]
+        assert ii.size, (coast, j)
+        f[j, ii[(5 * j + 1) % ii.size]] = np.nan
+    gv = {k: v.astype(dt) for k, v in gv.items()}
+    f = np.ascontiguousarray(f.astype(dt))
+    dx = T.grid_dx_min(grid, gv) if O.DIMENSIONAL[grid] else 1.0
+    flt = Filter(filter_scale=4.0 * dx, dx_min=dx, n_steps=n_steps, filter_shape=FilterShape.GAUSSIAN, grid_type=GridType[grid], grid_vars=gv)
+    fs = flt.filter_spec
+    p = np.asarray(fs.p, dtype=np.float64)
+    c = 2 / fs.s_max if O.DIMENSIONAL[grid] else 2 / (fs.s_max * fs.dx_min_sq)
+    clear_plan_cache()
+    lap = ALL_KERNELS[GridType[grid]](**gv)
+    plan = lap._plan(_lib.dtype_code(dt), shape)
+    pipe = None
+    try:
+        want = np.empty(shape)
+        plan.apply(p, c, [f.ctypes.data], [want.ctypes.data], 1, device_ptrs=False)
+        parent_kernel = plan.last_kernel()
+        pipe = host_blocks.RowBlockPipeline(GridType[grid].value, _lib.dtype_code(dt), ny, nx, [np.asarray(a) for a in lap._planes], plan.device,
+                                            n_steps, nblocks, skip_kappa_one=lap._skip_kappa_one, cut=plan.clenshaw_cut(n_steps))
+        assert pipe.ok and pipe.nblocks == nblocks and [b.ro for b in pipe.blocks] == [height] * nblocks
+        got = np.empty(shape)
+        pipe.apply(p, c, f, got, False)
+        block_kernel = pipe.blocks[-1].plan.last_kernel()
+        assert block_kernel and plan.last_kernel() == ""            # the launches ran on the block plans
+    finally:
+        if pipe is not None:
+            pipe.close()
+        clear_plan_cache()
+    spec = O.FilterSpec(fs.n_steps, fs.s_max, p, fs.dx_min_sq)
+    with np.errstate(all="ignore"):
+        truth = O.filter_func(spec, grid, f.astype("f8"), {k: v.astype("f8") for k, v in gv.items()})
+        ref32 = O.filter_func(spec, grid, f, gv) if dt == "f4" else None
+    assert np.isfinite(truth).any()
+    assert np.array_equal(np.isnan(got), np.isnan(truth)), (grid, coast, "NaN pattern differs from the oracle's")
+    r = dict(got=(got,), truth=(truth,), ref32=(ref32,), lap=(truth,), ltruth=(truth,), lref32=(ref32,))
+    e, bound, _, _ = errors(SimpleNamespace(dt=dt, scheme="forward"), r)
+    print(f"\n{grid} {dt} {coast} {nblocks} blocks n {n_steps}: parent {parent_kernel} blocks {block_kernel} error {e:.3e} (bound {bound:.3e})")
+    assert e <= bound, (grid, coast, e, bound)
+    assert np.array_equal(got, want, equal_nan=True), (grid, coast, nblocks, n_steps, float(np.nanmax(np.abs(got - want))))
