@@ -43,6 +43,8 @@ EXPORTS_LEVELS = ["gcmf_plan_create_levels", "gcmf_plan_levels"]
 EXPORTS_BANK = ["gcmf_apply_bank", "gcmf_bank_cut"]
 # ... and of filter banks on gappy fields (gcmf_apply_bank_gaps): likewise
 EXPORTS_BANK_GAPS = ["gcmf_apply_bank_gaps"]
+# ... and of the adjoint application (gcmf_apply_adjoint): likewise
+EXPORTS_ADJOINT = ["gcmf_apply_adjoint"]
 PATH_NAMES = {0: None, 1: "resident", 2: "strips", 3: "resident-lock-busy", 4: "resident-disabled"}
 RESIDENT_STATES = {0: "ok", 1: "lock-busy", 2: "disabled", 3: "off"}
 PLAN_SELF_RING, PLAN_SKIP_KAPPA_ONE = 0x1, 0x2
@@ -120,6 +122,8 @@ def load() -> C.CDLL:
         lib.gcmf_plan_rows.restype = C.c_int
         lib.gcmf_apply.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_double, vpp, vpp, C.c_int64, C.c_uint32, vp]
         lib.gcmf_apply.restype = C.c_int
+        lib.gcmf_apply_adjoint.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_double, vpp, vpp, vpp, C.c_int64, C.c_uint32, vp]
+        lib.gcmf_apply_adjoint.restype = C.c_int
         lib.gcmf_apply_bank.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double, vp, vp, C.c_int64, C.c_uint32, vp]
         lib.gcmf_apply_bank.restype = C.c_int
         lib.gcmf_apply_bank_gaps.argtypes = lib.gcmf_apply_bank.argtypes
@@ -370,6 +374,21 @@ class Plan:
         check(load().gcmf_apply(self._h, p.ctypes.data_as(C.POINTER(C.c_double)), len(p) - 1, float(c),
                                 _ptr_array(ins), _ptr_array(outs), int(nbatch), flags, C.c_void_p(stream or None)))
 
+    def apply_adjoint(self, p: np.ndarray, c: float, ins: Sequence[int], outs: Sequence[int], nbatch: int, *, likes: Optional[Sequence[int]] = None,
+                      device_ptrs: bool, out_f32: bool = False, stream: int = 0, forward: bool = False, backward_f32: bool = False,
+                      mask_from_nan: bool = False, faces_from_nan: bool = False, flags: int = 0):
+        """The transpose of apply() with the same arguments (gcmf_apply_adjoint): outs = F^T ins, F^T = D F D^-1 with the diagonal D of
+        the grid type (include/gcmf.h).  likes: None, or the forward call's input planes -- where they are NaN the input is taken as 0
+        and the result is 0; required with mask_from_nan / faces_from_nan, whose gaps are the NaNs of `likes`.  VECTOR_B_GRID, row
+        slabs and self-ring plans raise GcmfError(ERR_UNSUPPORTED).  flags: further GCMF_* bits (GCMF_NO_RESIDENT)."""
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        bits = ((DEVICE_PTRS if device_ptrs else 0) | (OUT_F32 if out_f32 else 0) | (FORWARD_RECURRENCE if forward else 0)
+                | (BACKWARD_F32 if backward_f32 else 0) | (MASK_FROM_NAN if mask_from_nan else 0)
+                | (FACES_FROM_NAN if faces_from_nan else 0) | int(flags))
+        check(load().gcmf_apply_adjoint(self._h, p.ctypes.data_as(C.POINTER(C.c_double)), len(p) - 1, float(c), _ptr_array(ins),
+                                        None if likes is None else _ptr_array(likes), _ptr_array(outs), int(nbatch), bits,
+                                        C.c_void_p(stream or None)))
+
     def apply_bank(self, p: np.ndarray, c: float, src: int, out: int, nfield: int, *, device_ptrs: bool = True, stream: int = 0,
                    flags: int = 0, faces_from_nan: bool = False):
         """A filter bank (gcmf_apply_bank): the rows of `p`, (nbank, n_steps + 1), are polynomials of one degree; out[j, i] = row j
@@ -571,7 +590,8 @@ class Plan:
         same policies with the wider table of round 7), "stream_state" (nine-level launches from a wet-row table load and store their
         state planes non-temporally so that the constant planes stay in the memory-side cache: 1 (default) where the table's owned cells x
         65 bytes exceed 256 MiB, 2 whenever such a launch runs, 0 never; same bits), "gap_scratch_mb" (apply(faces_from_nan=True): the most scratch, in MiB, the
-        per-entry planes of one launch may take; default 4096, longer batches run as consecutive launches)."""
+        per-entry planes of one launch may take; default 4096, longer batches run as consecutive launches), "adjoint_scratch_mb" (apply_adjoint:
+        the same bound for its pre-scaled planes, one per component and entry)."""
         check(load().gcmf_set_option(self._h, name.encode(), int(value)))
 
 

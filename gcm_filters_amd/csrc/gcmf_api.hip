@@ -490,6 +490,15 @@ struct GapFold {
   int64_t n = 0;
 };
 
+// gcmf_apply_adjoint (gcmf.h): out = F^T in = D F(in / D), F = what gcmf_apply applies.  A launch that is handed one of these scales its
+// input into a plane of the work buffer first (the forms of k_prepare in gcmf_scalar.hip), runs gcmf_apply's own schedule on that
+// plane, and scales the result in place.  like: the forward call's input planes (has_like), whose NaNs are the cells without a
+// derivative -- and, under the two NaN flags, the gaps the launch derives its masks / faces from, as the forward call did.
+struct Adjoint {
+  const void *like[2] = {nullptr, nullptr};
+  bool has_like = false;
+};
+
 static const char *const FACES_WHERE = "GCMF_FACES_FROM_NAN is a gcmf_apply flag for whole-grid f64 ordinary plans of IRREGULAR_WITH_LAND, MOM5U and MOM5T";
 
 static int lapl_step(ApplyCtx &x) {
@@ -856,7 +865,8 @@ static int finish_call(ApplyCtx &x, bool on_dev, void *const *out, size_t out_by
 // the bank's fields and table rows; the flags put the call's own mask bytes or folded planes into it.  fold: gcmf_apply_bank_gaps' memo.
 // `timed` = false: the caller (the pipelined host path) brackets the launches with the timing events itself.
 static int run_whole_locked(gcmf_plan *pl, const CallView &base, GapFold *fold, const double *p, int n_steps, double c, const void *const *in,
-                            void *const *out, int64_t nbatch, uint32_t flags, void *stream, bool lapl_only, bool timed) {
+                            void *const *out, int64_t nbatch, uint32_t flags, void *stream, bool lapl_only, bool timed,
+                            const Adjoint *adj = nullptr) {
   const bool on_dev = flags & GCMF_DEVICE_PTRS;
   ApplyCtx x{};
   x.pl = pl;
@@ -898,6 +908,10 @@ static int run_whole_locked(gcmf_plan *pl, const CallView &base, GapFold *fold, 
   const size_t nface = (size_t)nfold * pl->d.ny * pl->d.nx;
   const size_t szG = align_up(nface * 8 + 256, 256), szL = align_up(nface + 256, 256);   // (padded as precompute_levels pads a stacked plan's)
   const size_t oG = per; if (faces) per += 3 * szG + szL;
+  // gcmf_apply_adjoint: the pre-scaled input, behind everything a forward call lays out (host pointers: and the staged `like`)
+  const bool adj_like = adj && adj->has_like;
+  const size_t oAdj = per; if (adj) per += szT;
+  const size_t oLike = per; if (adj_like && !on_dev) per += szT;
   int rc = ensure_work(pl, per * pl->ncomp);
   if (rc || (rc = wait_for_work(pl, x.s))) return rc;
   char *w = (char *)pl->work;
@@ -920,12 +934,22 @@ static int run_whole_locked(gcmf_plan *pl, const CallView &base, GapFold *fold, 
       GCMF_HIP(hipMemcpyAsync(base + oIn, in[k], ncell * ts, hipMemcpyHostToDevice, x.s));
     }
   }
+  const void *dlike[2] = {nullptr, nullptr};
+  for (int k = 0; adj_like && k < pl->ncomp; ++k) {
+    dlike[k] = adj->like[k];
+    if (!on_dev) {
+      dlike[k] = w + per * k + oLike;
+      GCMF_HIP(hipMemcpyAsync(w + per * k + oLike, adj->like[k], ncell * ts, hipMemcpyHostToDevice, x.s));
+    }
+  }
+  // (the adjoint of a flagged call: the gaps are those of the forward call's input)
+  const void *gaps_of = adj ? dlike[0] : x.din[0];
   const bool timing = pl->timing && timed;
   if (timing) GCMF_HIP(hipEventRecord(pl->ev0, x.s));
   CallView &cv = x.cv;
   if (from_nan) {   // the call's own mask bytes where the launchers look for the plan's; the plan's land count does not apply to them
     uint8_t *bits = (uint8_t *)(w + oM);
-    if ((rc = launch_field_masks(pl, pl->g.mbits, x.din[0], bits, nbatch, x.s))) return rc;
+    if ((rc = launch_field_masks(pl, pl->g.mbits, gaps_of, bits, nbatch, x.s))) return rc;
     ++x.launches;
     cv.mbits = cv.lbits = bits;
     cv.n_land = std::max<int64_t>(1, pl->n_land);
@@ -949,14 +973,28 @@ static int run_whole_locked(gcmf_plan *pl, const CallView &base, GapFold *fold, 
     }
     // (a bank: one fold per FIELD -- a later launch of the same call that finds the same fields folded at the same place folds nothing)
     if (!(fold && fold->at == (const void *)cEb && fold->in == x.din[0] && fold->n == nfold)) {
-      if ((rc = launch_gap_fold(pl, (const double *)pl->g.coef[0], (const double *)pl->g.coef[1], (const double *)pl->g.coef[2], x.din[0], cEb, cNb,
+      if ((rc = launch_gap_fold(pl, (const double *)pl->g.coef[0], (const double *)pl->g.coef[1], (const double *)pl->g.coef[2], gaps_of, cEb, cNb,
                                 rab, bits, nfold, x.s)))
         return rc;
       ++x.launches;
       if (fold) *fold = GapFold{x.din[0], cEb, nfold};
     }
   }
+  if (adj) {   // in / D into the scratch plane, with the view's planes
+    // Where `like` is NaN the schedule must see NaN again: the forward call read that cell as the value 0 at EVERY step (nan_to_num inside
+    // the stencil), so what it applied to the finite cells is the polynomial of the principal submatrix on them -- whose transpose is that
+    // submatrix's polynomial again, not the filter with the cell set to 0 once and left to evolve.  (A flagged call derives its gaps from
+    // those NaNs besides.)  The REGULAR kinds' stencil reads a NaN as a NaN, which spreads: there is no derivative to keep, the cell is 0.
+    void *scr[2] = {w + oAdj, w + per + oAdj};
+    if ((rc = launch_adjoint_scale(pl, cv, false, x.din, scr, adj_like ? dlike : nullptr, x.fb32, pl->kind != K_REG, nbatch, x.s))) return rc;
+    for (int k = 0; k < pl->ncomp; ++k) x.din[k] = scr[k];
+    x.launches += pl->ncomp;
+  }
   if ((rc = lapl_only ? lapl_step(x) : run_schedule(x, flags, use_multi, use_vmulti))) return rc;
+  if (adj) {   // ... and the result times D, in place; 0 where `like` is NaN
+    if ((rc = launch_adjoint_scale(pl, cv, true, x.dout, x.dout, adj_like ? dlike : nullptr, x.fb32, false, nbatch, x.s))) return rc;
+    x.launches += pl->ncomp;
+  }
   return finish_call(x, on_dev, out, ncell * fbs, timing, timed);
 }
 
@@ -1086,7 +1124,8 @@ struct Tally {
 // component of `in` / `out` (in_stride 0: a bank, whose every launch reads all the fields) and an entry keeps its place in the call through
 // the view's entry0, which counts on from cv.entry0.
 static int run_launches(gcmf_plan *pl, CallView cv, GapFold *fold, const double *p, int n_steps, double c, const void *const *in, size_t in_stride,
-                        void *const *out, size_t out_stride, int64_t nent, int64_t launch_nb, uint32_t flags, void *stream, bool lapl_only, Tally &t) {
+                        void *const *out, size_t out_stride, int64_t nent, int64_t launch_nb, uint32_t flags, void *stream, bool lapl_only, Tally &t,
+                        const Adjoint *adj = nullptr) {
   const int64_t first = cv.entry0;
   for (int64_t e0 = 0; e0 < nent; e0 += launch_nb) {
     const void *in2[2] = {nullptr, nullptr};
@@ -1096,7 +1135,13 @@ static int run_launches(gcmf_plan *pl, CallView cv, GapFold *fold, const double 
       out2[k] = (char *)out[k] + (size_t)e0 * out_stride;
     }
     cv.entry0 = first + e0;
-    const int rc = run_whole_locked(pl, cv, fold, p, n_steps, c, in2, out2, std::min(nent - e0, launch_nb), flags, stream, lapl_only, true);
+    Adjoint adj2;
+    if (adj) {
+      adj2 = *adj;
+      for (int k = 0; k < pl->ncomp && adj->has_like; ++k) adj2.like[k] = (const char *)adj->like[k] + (size_t)e0 * in_stride;
+    }
+    const int rc = run_whole_locked(pl, cv, fold, p, n_steps, c, in2, out2, std::min(nent - e0, launch_nb), flags, stream, lapl_only, true,
+                                    adj ? &adj2 : nullptr);
     if (rc) return rc;
     t.ms += pl->last_ms;
     t.launches += pl->last_launches;
@@ -1104,23 +1149,39 @@ static int run_launches(gcmf_plan *pl, CallView cv, GapFold *fold, const double 
   return GCMF_OK;
 }
 
+// adj: gcmf_apply_adjoint (like: null or its `like` argument)
 static int run_whole(gcmf_plan *pl, const double *p, int n_steps, double c, const void *const *in, void *const *out,
-                     int64_t nbatch, uint32_t flags, void *stream, bool lapl_only) {
+                     int64_t nbatch, uint32_t flags, void *stream, bool lapl_only, bool adj = false, const void *const *like = nullptr) {
+  const char *who = adj ? "gcmf_apply_adjoint" : lapl_only ? "gcmf_laplacian" : "gcmf_apply";
   if (!pl || !in || !out || nbatch < 0 || (!lapl_only && (!p || n_steps < 1))) {
-    set_error("gcmf_apply: bad argument");
+    set_error("%s: bad argument", adj ? who : "gcmf_apply");
     return GCMF_ERR_INVALID_ARG;
   }
   for (int k = 0; k < pl->ncomp; ++k)
-    if (!in[k] || !out[k]) {
-      set_error("gcmf_apply: null component pointer");
+    if (!in[k] || !out[k] || (like && !like[k])) {
+      set_error("%s: null component pointer", adj ? who : "gcmf_apply");
       return GCMF_ERR_INVALID_ARG;
     }
   for (int k = 0; k < pl->ncomp; ++k)
     for (int q = 0; q < pl->ncomp; ++q)
       if (in[k] == out[q]) {  // (the ranges are compared below, once the plan is known to cover the whole grid: their size is ny * nx)
-        set_error("%s: `out` must not alias `in` (filtering in place is not supported)", lapl_only ? "gcmf_laplacian" : "gcmf_apply");
+        set_error("%s: `out` must not alias `in` (filtering in place is not supported)", who);
         return GCMF_ERR_INVALID_ARG;
       }
+  if (adj) {
+    // F^T = D F D^-1 needs a diagonal D: the B-grid Laplacian has none (sign(L_ij) != sign(L_ji) on part of its couplings)
+    const char *why = pl->d.grid_type == GCMF_VECTOR_B_GRID ? "VECTOR_B_GRID has no diagonal symmetrizer: its adjoint needs a transposed stencil kernel" :
+                      (pl->d.flags & GCMF_PLAN_SELF_RING) ? "not available on a GCMF_PLAN_SELF_RING plan" :
+                      !pl->full ? "not available on a row slab: it needs a plan covering the whole grid" : nullptr;
+    if (why) {
+      set_error("gcmf_apply_adjoint: %s (grid type %d)", why, pl->d.grid_type);
+      return GCMF_ERR_UNSUPPORTED;
+    }
+    if ((flags & (GCMF_MASK_FROM_NAN | GCMF_FACES_FROM_NAN)) && !like) {
+      set_error("gcmf_apply_adjoint: GCMF_MASK_FROM_NAN / GCMF_FACES_FROM_NAN need `like`, the forward call's input: the gaps are its NaNs");
+      return GCMF_ERR_INVALID_ARG;
+    }
+  }
   if (flags & GCMF_FACES_FROM_NAN) {
     const int gt = pl->d.grid_type;
     const bool kind_ok = gt == GCMF_IRREGULAR_WITH_LAND || gt == GCMF_MOM5U || gt == GCMF_MOM5T;
@@ -1165,9 +1226,16 @@ static int run_whole(gcmf_plan *pl, const double *p, int n_steps, double c, cons
     // batch entry into `in` is as wrong as out == in.  (in[0] == in[1] is fine: nothing writes the input.)
     const size_t cells = (size_t)nbatch * (size_t)pl->d.ny * (size_t)pl->d.nx, its = dtype_size(pl->d.dtype);
     const size_t ots = lapl_only ? its : ((pl->d.dtype == GCMF_F32 && !(flags & GCMF_OUT_F32)) ? 8 : its);
-    const char *who = lapl_only ? "gcmf_laplacian" : "gcmf_apply";
     for (int q = 0; q < pl->ncomp; ++q) {
       const uintptr_t o0 = (uintptr_t)out[q], o1 = o0 + cells * ots;
+      for (int k = 0; like && k < pl->ncomp; ++k) {
+        const uintptr_t l0 = (uintptr_t)like[k], l1 = l0 + cells * its;
+        if (l0 < o1 && o0 < l1) {
+          set_error("%s: `out` must not alias `like`: the %zu bytes of out[%d] overlap the %zu bytes of like[%d]", who, cells * ots, q,
+                    cells * its, k);
+          return GCMF_ERR_INVALID_ARG;
+        }
+      }
       for (int k = 0; k < pl->ncomp; ++k) {
         const uintptr_t i0 = (uintptr_t)in[k], i1 = i0 + cells * its;
         if (in[k] == out[q] || (i0 < o1 && o0 < i1)) {
@@ -1190,8 +1258,14 @@ static int run_whole(gcmf_plan *pl, const double *p, int n_steps, double c, cons
   std::lock_guard<std::mutex> lk(pl->mu);
   GCMF_HIP(hipSetDevice(pl->d.device));
   // the most entries one launch takes: the scalar kernels index the batch with gridDim.y (<= 65535)
-  const int64_t launch_nb = (flags & GCMF_FACES_FROM_NAN) ? gap_launch_entries(pl) : MAX_LAUNCH_BATCH;
-  if (!(flags & GCMF_DEVICE_PTRS) && nbatch > 1 && pl->host_chunk_bytes > 0) {
+  int64_t launch_nb = (flags & GCMF_FACES_FROM_NAN) ? gap_launch_entries(pl) : MAX_LAUNCH_BATCH;
+  if (adj) {   // the scratch plane of every component and entry of a launch at or under option "adjoint_scratch_mb", at least one entry
+    const long long bound = (long long)std::max(0, pl->adjoint_scratch_mb) << 20;
+    const long long per_entry = (long long)pl->ncomp * pl->d.ny * pl->d.nx * (long long)dtype_size(pl->d.dtype);
+    launch_nb = std::max<int64_t>(1, std::min<int64_t>(launch_nb, bound / per_entry));
+  }
+  // (the adjoint stages host planes through HBM one launch at a time: no chunk pipeline)
+  if (!adj && !(flags & GCMF_DEVICE_PTRS) && nbatch > 1 && pl->host_chunk_bytes > 0) {
     const size_t entry = (size_t)pl->d.ny * pl->d.nx * dtype_size(pl->d.dtype);
     int64_t chunk_nb = (int64_t)(pl->host_chunk_bytes / entry);
     if (chunk_nb < 1) chunk_nb = 1;
@@ -1202,13 +1276,22 @@ static int run_whole(gcmf_plan *pl, const double *p, int n_steps, double c, cons
   const size_t cell = (size_t)pl->d.ny * pl->d.nx, ts = dtype_size(pl->d.dtype);
   const size_t fbs = lapl_only ? ts : ((pl->d.dtype == GCMF_F32 && !(flags & GCMF_OUT_F32)) ? 8 : ts);
   Tally t;
-  const int rc = run_launches(pl, own_view(pl), nullptr, p, n_steps, c, in, cell * ts, out, cell * fbs, nbatch, launch_nb, flags, stream, lapl_only, t);
+  Adjoint a;
+  for (int k = 0; like && k < pl->ncomp; ++k) a.like[k] = like[k];
+  a.has_like = like != nullptr;
+  const int rc = run_launches(pl, own_view(pl), nullptr, p, n_steps, c, in, cell * ts, out, cell * fbs, nbatch, launch_nb, flags, stream, lapl_only, t,
+                              adj ? &a : nullptr);
   return rc ? rc : t.leave(pl);
 }
 
 int gcmf_apply(gcmf_plan *pl, const double *p, int n_steps, double c, const void *const *in, void *const *out,
                int64_t nbatch, uint32_t flags, void *stream) {
   return run_whole(pl, p, n_steps, c, in, out, nbatch, flags, stream, false);
+}
+
+int gcmf_apply_adjoint(gcmf_plan *pl, const double *p, int n_steps, double c, const void *const *in, const void *const *like,
+                       void *const *out, int64_t nbatch, uint32_t flags, void *stream) {
+  return run_whole(pl, p, n_steps, c, in, out, nbatch, flags, stream, false, true, like);
 }
 
 // The two coefficient tables of a filter bank on the device (gcmf_plan::bank_rev / bank_fwd), uploaded only when they changed -- as

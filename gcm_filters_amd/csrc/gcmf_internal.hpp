@@ -191,6 +191,12 @@ struct gcmf_plan {
   int64_t nlev = 1;
   // GCMF_FACES_FROM_NAN: the most scratch one launch may take for its folded planes (25 bytes per cell and entry); longer batches are cut.
   int gap_scratch_mb = 4096;   // gcmf_set_option "gap_scratch_mb"
+  // gcmf_apply_adjoint: F^T = D F D^-1 (gcmf.h).  D is made of planes the plan holds anyway -- ra of the flux kinds, the area of the
+  // area-weighted ones -- except on the C-grid, whose folded coefficients hold no plane of area_u or area_v alone: such a plan keeps a copy
+  // of both (slab-row layout, two planes more).  The pre-scaled input is one plane of the plan dtype per component and entry of a launch,
+  // in the work buffer behind everything else; longer batches are cut so that it stays at or under "adjoint_scratch_mb".
+  const void *adj_area[2] = {nullptr, nullptr};
+  int adjoint_scratch_mb = 4096;   // gcmf_set_option "adjoint_scratch_mb"
   int zero_land = 1;     // env GCMF_ZERO_LAND=0 turns it off
   int ring = 1;           // env GCMF_RING=0: deep launches stay with k_flux_multi2 / k_scalar_multi
   unsigned *ring_nfb = nullptr;    // device counter behind gcmf_ring_fallbacks (lives behind zero_row)
@@ -392,6 +398,12 @@ bool fold_band_supported(const gcmf_plan *pl, const MultiArgs &a);
 int launch_fold_band(gcmf_plan *pl, const CallView &cv, const MultiArgs &a, bool backward, hipStream_t s, bool wide = false);
 int launch_prepare(gcmf_plan *pl, const void *const *in, void *const *out, int64_t nbatch, int row_lo,
                    int row_hi, hipStream_t s);
+// gcmf_apply_adjoint's two passes (gcmf_scalar.hip, forms of k_prepare): pre (post = false) in -> out = in / D, both of the plan dtype;
+// post: `out` times D in place, of the output type (f64, or f32 with out_f32 on an f32 plan).  D and the land bytes are the view's (the
+// level of a stacked plan, the folded planes of a flagged call); like: null or the forward call's input planes (plan dtype) -- a NaN
+// there gives 0, or NaN itself with nan_gaps (the pre-scale of a flagged call, whose gaps the schedule must see)
+int launch_adjoint_scale(gcmf_plan *pl, const CallView &cv, bool post, const void *const *in, void *const *out, const void *const *like,
+                         bool out_f32, bool nan_gaps, int64_t nbatch, hipStream_t s);
 // the isolated cells' own polynomial, written over out (gcmf_landfix.hip); dp = p[0..n_steps] on the device
 int launch_zero_land(gcmf_plan *pl, const CallView &cv, void *a, void *b, int64_t nbatch, hipStream_t s, int row_lo = 0, int row_hi = 0);
 int launch_land_fix(gcmf_plan *pl, const CallView &cv, const void *in, void *out, const double *dp, int n_steps, double c, int fb_is_f32,

@@ -565,6 +565,12 @@ template <typename T> static int precompute_t(gcmf_plan *pl, const void *const *
     if ((rc = cut_rows(pl, dp[area_idx], &slab, sizeof(T), s))) return rc;
     g.area = slab;
   }
+  if (gt == GCMF_VECTOR_C_GRID)   // area_u, area_v: the diagonal of gcmf_apply_adjoint's similarity (gcmf_plan::adj_area)
+    for (int k = 0; k < 2; ++k) {
+      void *slab = nullptr;
+      if ((rc = cut_rows(pl, dp[10 + k], &slab, sizeof(T), s))) return rc;
+      pl->adj_area[k] = slab;
+    }
   GCMF_HIP(hipStreamSynchronize(s));
   return GCMF_OK;
 }

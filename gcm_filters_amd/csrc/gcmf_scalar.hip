@@ -338,4 +338,126 @@ int launch_prepare(gcmf_plan *pl, const void *const *in, void *const *out, int64
   return GCMF_OK;
 }
 
+// ---- the two diagonal scalings around an adjoint application (gcmf_apply_adjoint, gcmf.h):  F^T g = post * F(pre * g) ----
+// What prepare / finalize do for the area-weighted kinds -- one plane times or over a grid plane -- with what the adjoint's planes need
+// on top: a land byte per cell (bit 0 clear: a land / isolated cell, whose factor is 1, so that junk metrics on land never reach the
+// result), the level axis of a stacked plan, the forward call's input `like` (only its NaN pattern is read: such a cell has no
+// derivative), and element accesses where a plane of the call is not on a 16-byte boundary.  D: the type of the scaled plane (the
+// plan's on the way in, the output's on the way out), T: the plan's.  in == out is allowed (every thread reads its cells before it
+// writes them).
+template <typename T, typename D> struct ScaleP {
+  const D *in;
+  D *out;
+  const T *like;          // nullptr: none (the forward call's input: the plan dtype)
+  const T *scale;         // nullptr: the factor is 1 everywhere
+  const uint8_t *land;    // nullptr: every cell takes the factor
+  long long plane;        // cells of one entry
+  long long lev_stride;   // cells between the levels of `scale` and `land` (0: one plane for every entry)
+  int nlev, lev0;         // entry y of the launch runs on level (lev0 + y) % nlev
+  int land_per_entry;     // `land` holds one plane per entry of the launch (GCMF_MASK_FROM_NAN)
+  int square;             // the factor is scale^2 (the area-weighted kinds: prepare and finalize both carry the area)
+  int nan_gaps;           // where `like` is NaN: write NaN (the cell is a gap of a flagged call) instead of 0
+};
+
+template <bool DIV, int VEC, typename T, typename D>
+__global__ __launch_bounds__(256) void k_prepare(const ScaleP<T, D> P) {
+  const long long nvec = P.plane / VEC;   // (VEC > 1: the launcher has checked that VEC divides the plane)
+  const int y = blockIdx.y;
+  const long long eoff = (long long)y * P.plane;
+  const long long loff = P.lev_stride ? (long long)((P.lev0 + y) % P.nlev) * P.lev_stride : 0;
+  const D *in = P.in + eoff;
+  D *out = P.out + eoff;
+  const T *like = P.like ? P.like + eoff : nullptr;
+  const T *scale = P.scale ? P.scale + loff : nullptr;
+  const uint8_t *land = P.land ? P.land + (P.land_per_entry ? eoff : loff) : nullptr;
+  for (long long q = (long long)blockIdx.x * blockDim.x + threadIdx.x; q < nvec; q += (long long)gridDim.x * blockDim.x) {
+    const long long c0 = q * VEC;
+    D v[VEC];
+    T sc[VEC], lk[VEC];
+    uint8_t lb[VEC];
+    load_vec<D, VEC>(v, in + c0);
+    if (like) load_vec<T, VEC>(lk, like + c0);
+    if (scale) load_vec<T, VEC>(sc, scale + c0);
+    if (land) load_vec<uint8_t, VEC>(lb, land + c0);
+#pragma unroll
+    for (int k = 0; k < VEC; ++k) {
+      D r = v[k];
+      if (scale && (!land || (lb[k] & 1u))) {
+        D f = (D)sc[k];
+        if (P.square) f = f * f;
+        r = DIV ? r / f : r * f;
+      }
+      if (like && lk[k] != lk[k]) r = P.nan_gaps ? (D)lk[k] : D(0);
+      v[k] = r;
+    }
+    store_vec<D, VEC>(out + c0, v);
+  }
+}
+
+template <bool DIV, typename T, typename D> static int launch_scale(const ScaleP<T, D> &P, int64_t nbatch, hipStream_t s) {
+  constexpr int V = 16 / sizeof(D);
+  bool vec_ok = P.plane % V == 0 && P.lev_stride % V == 0;
+  for (const void *p : {(const void *)P.in, (const void *)P.out}) vec_ok = vec_ok && aligned16(p);
+  for (const void *p : {(const void *)P.scale, (const void *)P.like}) vec_ok = vec_ok && (reinterpret_cast<uintptr_t>(p) % (V * sizeof(T))) == 0;
+  vec_ok = vec_ok && (reinterpret_cast<uintptr_t>(P.land) % V) == 0;
+  const long long nvec = vec_ok ? P.plane / V : P.plane;
+  // (a streaming pass: 2048 workgroups per entry at the most, each striding over the rest of the plane)
+  dim3 block(256), grid((unsigned)std::min<long long>((nvec + 255) / 256, 2048), (unsigned)nbatch);
+  if (vec_ok)
+    hipLaunchKernelGGL((k_prepare<DIV, V, T, D>), grid, block, 0, s, P);
+  else
+    hipLaunchKernelGGL((k_prepare<DIV, 1, T, D>), grid, block, 0, s, P);
+  GCMF_HIP(hipGetLastError());
+  return GCMF_OK;
+}
+
+template <typename T, typename D>
+static int adjoint_scale_t(gcmf_plan *pl, const CallView &cv, bool post, const void *const *in, void *const *out, const void *const *like,
+                           bool nan_gaps, int64_t nbatch, hipStream_t s) {
+  const Geom &g = pl->g;
+  for (int cpt = 0; cpt < pl->ncomp; ++cpt) {
+    ScaleP<T, D> P{};
+    P.in = (const D *)in[cpt];
+    P.out = (D *)out[cpt];
+    P.like = like ? (const T *)like[cpt] : nullptr;
+    P.plane = (long long)g.rows * g.nx;
+    P.nlev = 1;
+    P.nan_gaps = nan_gaps;
+    // F^T = D F D^-1: pre = 1 / D, post = D.  The flux kinds hold ra = 1 / area (D = area): times ra on the way in, over ra on the way
+    // out; the area-weighted kinds hold the area (D = area^2), the C-grid area_u and area_v (D = (area_u, area_v)): over on the way in,
+    // times on the way out.
+    bool div = false;
+    if (pl->kind == K_FLUX) {
+      P.scale = (const T *)cv.coef[2];
+      div = post;
+    } else if (g.area_weighted) {
+      P.scale = (const T *)g.area;
+      P.square = 1;
+      div = !post;
+    } else if (pl->kind == K_CGRID) {
+      P.scale = (const T *)pl->adj_area[cpt];
+      div = !post;
+    }
+    if (pl->ncomp == 1 && P.scale) P.land = cv.lbits;   // (K_REG has none: lbits is null there)
+    P.land_per_entry = cv.mask_per_field;
+    if (cv.stacked) {
+      P.lev_stride = P.plane;
+      P.nlev = (int)cv.nlev;
+      P.lev0 = (int)(cv.entry0 % cv.nlev);
+    }
+    const int rc = div ? launch_scale<true, T, D>(P, nbatch, s) : launch_scale<false, T, D>(P, nbatch, s);
+    if (rc) return rc;
+  }
+  return GCMF_OK;
+}
+
+// pre (post = false): in -> out, both of the plan dtype; post: `out` in place, of the output type (f64 unless out_f32 on an f32 plan)
+int launch_adjoint_scale(gcmf_plan *pl, const CallView &cv, bool post, const void *const *in, void *const *out, const void *const *like,
+                         bool out_f32, bool nan_gaps, int64_t nbatch, hipStream_t s) {
+  if (nbatch <= 0) return GCMF_OK;
+  if (pl->d.dtype == GCMF_F64) return adjoint_scale_t<double, double>(pl, cv, post, in, out, like, nan_gaps, nbatch, s);
+  if (!post || out_f32) return adjoint_scale_t<float, float>(pl, cv, post, in, out, like, nan_gaps, nbatch, s);
+  return adjoint_scale_t<float, double>(pl, cv, post, in, out, like, nan_gaps, nbatch, s);
+}
+
 }  // namespace gcmf

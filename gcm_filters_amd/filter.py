@@ -182,17 +182,151 @@ def _create_filter_func(filter_spec: FilterSpec, Laplacian, evaluation: str = "a
     faces = nan_mask == "auto" and Laplacian.GRID_TYPE in GAP_FOLD_GRID_TYPES
     masks = bool(nan_mask) and not faces
 
-    def filter_func(field, *args):
-        assert len(args) == len(Laplacian.required_grid_args())
+    def run(fields, args, adjoint=False, like=None):
         with plan_cache_mode(plan_cache):
             laplacian = memo.get(args)  # device plan: cached while the grid arrays are unchanged
-            out = laplacian._run([field], spec=filter_spec, forward=forward, backward_f32=backward, mask_from_nan=masks,
-                                 faces_from_nan=faces)[0]
+            out = laplacian._run(fields, spec=filter_spec, forward=forward, backward_f32=backward, mask_from_nan=masks,
+                                 faces_from_nan=faces, adjoint=adjoint, like=like)
         filter_func.last_path = kernels_last_path()
         return out
 
+    def filter_func(field, *args):
+        assert len(args) == len(Laplacian.required_grid_args())
+        if _wants_grad(field):   # a torch tensor that requires grad: the same call, with a grad_fn (the adjoint runs in backward)
+            return _differentiable(_Operator(run, args), [field])[0]
+        return run([field], args)[0]
+
+    def adjoint_func(field, *args):
+        """The transpose of filter_func applied to `field`."""
+        assert len(args) == len(Laplacian.required_grid_args())
+        return run([field], args, adjoint=True)[0]
+
+    def adjoint_like_func(field, like, *args):
+        """... with the forward input `like`: 0 where it is NaN, and its NaNs are the gaps of a nan_mask filter."""
+        assert len(args) == len(Laplacian.required_grid_args())
+        return run([field], args, adjoint=True, like=[like])[0]
+
     filter_func.last_path = None
+    filter_func.adjoint, filter_func.adjoint_like = adjoint_func, adjoint_like_func
+    filter_func.operator = lambda args: _Operator(run, args)
     return filter_func
+
+
+# ------------------------------------------------------------------------------------------------
+# torch autograd through the operator: F in forward, F^T (adjoint.py, gcmf_apply_adjoint) in backward
+# ------------------------------------------------------------------------------------------------
+def _wants_grad(*xs) -> bool:
+    """A torch tensor that requires grad while autograd records: everything else -- numpy, xarray payloads, tensors that do not require
+    grad, anything under torch.no_grad() -- takes exactly the path it took before there was a backward."""
+    if not any(_is_torch(x) and x.requires_grad for x in xs):
+        return False
+    import torch
+    return torch.is_grad_enabled()
+
+
+class _Operator:
+    """One filter (a factory's `run` closure and the grid arguments of a call) as the pair of linear maps autograd needs."""
+
+    def __init__(self, run, args):
+        self.run, self.args = run, args
+
+    def forward(self, xs):
+        return self.run(list(xs), self.args)
+
+    def adjoint(self, gs, likes):
+        return self.run(list(gs), self.args, adjoint=True, like=list(likes))
+
+
+_AUTOGRAD = None
+
+
+def _autograd():
+    """The two torch.autograd.Functions, made on first use (torch is imported only when a tensor asks for a gradient).
+
+    _Forward: y = F x; backward: x.grad = F^T g with like = x, the saved input itself (no copy).  _Adjoint: that backward as a
+    Function of its own, so that it is differentiable in turn: it is linear in g, and its transpose is F again -- on the cells where
+    `like` is finite, the only ones it reads or writes (gradgradcheck).  Neither has a derivative with respect to `like`: F is linear
+    and its NaN pattern is not a differentiable thing."""
+    global _AUTOGRAD
+    if _AUTOGRAD is not None:
+        return _AUTOGRAD
+    import torch
+
+    class _Forward(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, op, *xs):
+            ctx.op = op
+            ctx.save_for_backward(*xs)
+            return tuple(op.forward([x.detach() for x in xs]))
+
+        @staticmethod
+        def backward(ctx, *gs):
+            return (None,) + tuple(_Adjoint.apply(ctx.op, *gs, *ctx.saved_tensors))
+
+    class _Adjoint(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, op, *gs_xs):
+            n = len(gs_xs) // 2
+            gs, xs = gs_xs[:n], gs_xs[n:]
+            ctx.op = op
+            ctx.save_for_backward(*xs)
+            outs = op.adjoint([g.detach() for g in gs], [x.detach() for x in xs])
+            # the gradient has the input's dtype and shape
+            return tuple(o.to(x.dtype).reshape(x.shape) for o, x in zip(outs, xs))
+
+        @staticmethod
+        def backward(ctx, *hs):
+            xs = ctx.saved_tensors
+            gaps = [torch.isnan(x) for x in xs]
+            # (F on h with the gaps of `like` -- a nan_mask filter derives its masks from them, any other reads them as 0 --, 0 on the gaps)
+            ins = [torch.where(m, torch.full_like(h, float("nan")), h) for h, m in zip(hs, gaps)]
+            outs = _differentiable(ctx.op, ins) if _wants_grad(*hs) else ctx.op.forward(ins)
+            outs = [torch.where(m, torch.zeros_like(o), o) for o, m in zip(outs, gaps)]
+            return (None,) + tuple(outs) + (None,) * len(xs)
+
+    _AUTOGRAD = (_Forward, _Adjoint)
+    return _AUTOGRAD
+
+
+_BANK_FUNCTION = None
+
+
+def _bank_function():
+    """FilterBank.apply as a torch.autograd.Function: whichever route the forward takes, the backward is the plain sum over the scales
+    of each filter's adjoint (no batched adjoint bank), every term differentiable in turn."""
+    global _BANK_FUNCTION
+    if _BANK_FUNCTION is None:
+        import torch
+
+        class _Bank(torch.autograd.Function):
+            @staticmethod
+            def forward(ctx, bank, args, x):
+                ctx.bank, ctx.args = bank, args
+                ctx.save_for_backward(x)
+                return bank._bank_func(x.detach(), *args)
+
+            @staticmethod
+            def backward(ctx, g):
+                (x,) = ctx.saved_tensors
+                total = None
+                for j, flt in enumerate(ctx.bank.filters):
+                    op = flt._operator(_create_filter_func).operator(ctx.args)
+                    term = _differentiable_adjoint(op, [g[j]], [x])[0]
+                    total = term if total is None else total + term
+                return None, None, total
+
+        _BANK_FUNCTION = _Bank
+    return _BANK_FUNCTION
+
+
+def _differentiable(op, xs):
+    """op.forward(xs) with a grad_fn."""
+    return _autograd()[0].apply(op, *xs)
+
+
+def _differentiable_adjoint(op, gs, likes):
+    """op.adjoint(gs, likes) with a grad_fn (the gradient's dtype and shape are those of `likes`)."""
+    return _autograd()[1].apply(op, *gs, *likes)
 
 
 def _check_nan_mask(nan_mask, grid_type):
@@ -215,15 +349,31 @@ def _create_filter_func_vec(filter_spec: FilterSpec, Laplacian, evaluation: str 
     backward = evaluation == "backward"
     memo = _LaplacianMemo(Laplacian)
 
-    def filter_func_vec(ufield, vfield, *args):
-        assert len(args) == len(Laplacian.required_grid_args())
+    def run(fields, args, adjoint=False, like=None):
         with plan_cache_mode(plan_cache):
             laplacian = memo.get(args)
-            u, v = laplacian._run([ufield, vfield], spec=filter_spec, forward=forward, backward_f32=backward)
+            u, v = laplacian._run(fields, spec=filter_spec, forward=forward, backward_f32=backward, adjoint=adjoint, like=like)
         filter_func_vec.last_path = kernels_last_path()
         return (u, v)
 
+    def filter_func_vec(ufield, vfield, *args):
+        assert len(args) == len(Laplacian.required_grid_args())
+        if _wants_grad(ufield, vfield):
+            if Laplacian.GRID_TYPE is GridType.VECTOR_B_GRID:   # (never a silent detach)
+                raise NotImplementedError("VECTOR_B_GRID is not differentiable: its Laplacian has no diagonal symmetrizer, so the adjoint "
+                                          "needs a transposed stencil kernel; detach() the fields to filter them without a gradient")
+            import torch
+            both = [x if _is_torch(x) else torch.as_tensor(np.asarray(x), device=y.device) for x, y in ((ufield, vfield), (vfield, ufield))]
+            return tuple(_differentiable(_Operator(run, args), both))
+        return run([ufield, vfield], args)
+
+    def adjoint_func_vec(ufield, vfield, *args):
+        """The transpose of filter_func_vec applied to (ufield, vfield)."""
+        assert len(args) == len(Laplacian.required_grid_args())
+        return run([ufield, vfield], args, adjoint=True)
+
     filter_func_vec.last_path = None
+    filter_func_vec.adjoint = adjoint_func_vec
     return filter_func_vec
 
 
@@ -446,15 +596,16 @@ class Filter:
                 raise TypeError(f"grid_vars {bare} must be xarray DataArrays to filter xarray objects")
         return [self.grid_ds[n] for n in names]
 
-    def _through_apply_ufunc(self, func, fields, dims):
+    def _through_apply_ufunc(self, func, fields, dims, extra=()):
         """The one call into ``xarray.apply_ufunc`` (reference filter.py:478-486, 518-527): every field and grid
         variable has ``dims`` as core dims (moved last), one output per field, same keywords as upstream so that lazy
-        (dask) inputs keep working: ``dask="parallelized"`` then calls ``func`` from worker threads, block by block."""
+        (dask) inputs keep working: ``dask="parallelized"`` then calls ``func`` from worker threads, block by block.
+        extra: operands handed to ``func`` between the fields and the grid variables (the adjoint's ``like``)."""
         xr = _xarray()
         if xr is None:
             raise ImportError("xarray is required to filter xarray objects; pass numpy arrays or torch tensors instead")
         assert len(dims) == 2
-        operands = list(fields) + self._grid_args(as_xarray=True)
+        operands = list(fields) + list(extra) + self._grid_args(as_xarray=True)
         return xr.apply_ufunc(
             func,
             *operands,
@@ -524,6 +675,55 @@ class Filter:
             return filter_func_vec(ufield, vfield, *self._grid_args(as_xarray=False))
         u_filtered, v_filtered = self._through_apply_ufunc(filter_func_vec, [ufield, vfield], dims)
         return (u_filtered, v_filtered)
+
+    # -- the adjoint (not in the reference) --------------------------------------------------------
+    def adjoint(self, field, dims=None, like=None):
+        """Apply the TRANSPOSE of ``apply`` to ``field`` (a gradient with respect to the filtered field, say): ``F^T field``, where
+        ``F`` is the linear map ``apply`` is on finite fields.  No transposed stencil runs: ``F^T = D F D^-1`` with a diagonal ``D``
+        made of the grid's cell areas (``gcm_filters_amd.adjoint``), so the cost is one application plus two plane passes.
+
+        Inputs as for ``apply`` -- numpy, torch (host or MI355X-resident), DLPack producers, ``xarray`` objects with ``dims`` -- and the
+        same kind comes out; ``evaluation``, ``plan_cache``, ``nan_mask`` and grid variables with leading dims carry over.
+
+        ``like``: the input the forward ``apply`` was given (same kind and shape as ``field``).  Only its NaN pattern is read: where it
+        is NaN the result is 0, because a NaN input cell has no derivative.  ``Filter(nan_mask=...)`` requires it (``ValueError``
+        without): its NaNs are the gaps the per-slice masks are made of.  The precision is the forward call's: with ``like`` given, the
+        data type of ``like`` and the grid variables decides between a float32 and a float64 plan, not that of ``field``.
+
+        ``torch`` tensors that require grad need none of this: ``apply`` returns a tensor with a ``grad_fn`` whose backward is this
+        method with ``like`` = the input (and is differentiable in turn)."""
+        if issubclass(self.Laplacian, BaseVectorLaplacian):
+            raise ValueError(f"Provided Laplacian {self.Laplacian} is a vector Laplacian. "
+                             f"The ``.adjoint`` method is only suitable for scalar Laplacians.")
+        if self.nan_mask and like is None:
+            raise ValueError("Filter(nan_mask=...).adjoint needs `like`, the field the forward apply() was given: its NaNs are the gaps "
+                             "each slice's wet mask is made of")
+        filter_func = self._operator(_create_filter_func)
+        if _is_bare_array(field):
+            if like is None:
+                return filter_func.adjoint(field, *self._grid_args(as_xarray=False))
+            return filter_func.adjoint_like(field, like, *self._grid_args(as_xarray=False))
+        xr = _xarray()
+        if xr is not None and isinstance(field, xr.Dataset):
+            raise TypeError("Filter.adjoint takes one DataArray at a time: pass the Dataset's variables one by one")
+        if like is None:
+            return self._through_apply_ufunc(filter_func.adjoint, [field], dims)
+        return self._through_apply_ufunc(filter_func.adjoint_like, [field], dims, extra=[like])
+
+    def adjoint_to_vector(self, ufield, vfield, dims=None):
+        """Apply the transpose of ``apply_to_vector`` to the pair (ufield, vfield); inputs and outputs as there.  ``VECTOR_C_GRID``
+        only: ``VECTOR_B_GRID`` raises ``NotImplementedError`` (its Laplacian has no diagonal symmetrizer)."""
+        if not issubclass(self.Laplacian, BaseVectorLaplacian):
+            raise ValueError(f"Provided Laplacian {self.Laplacian} is a scalar Laplacian. "
+                             f"The ``.adjoint_to_vector`` method is only suitable for vector Laplacians.")
+        if self.grid_type is GridType.VECTOR_B_GRID:
+            raise NotImplementedError("VECTOR_B_GRID has no adjoint: its Laplacian has no diagonal symmetrizer D with L^T = D L D^-1; "
+                                      "it needs a transposed stencil kernel")
+        adjoint_vec = self._operator(_create_filter_func_vec).adjoint
+        if _is_bare_array(ufield) and _is_bare_array(vfield):
+            return adjoint_vec(ufield, vfield, *self._grid_args(as_xarray=False))
+        u_adj, v_adj = self._through_apply_ufunc(adjoint_vec, [ufield, vfield], dims)
+        return (u_adj, v_adj)
 
 
 def _bank_by_default(nbank: int, ny: int, nx: int, grid_type=None) -> bool:
@@ -643,6 +843,8 @@ class FilterBank:
 
     def _bank_func(self, field, *args):
         """(len(filter_scales),) + field.shape: every scale's filter of `field`."""
+        if _wants_grad(field):   # the same call with a grad_fn; backward: sum_j filters[j].adjoint(g[j], like=field)
+            return _bank_function().apply(self, args, field)
         want = self._wants_bank()
         eligible = (len(self.filters) > 1 and self.evaluation != "reference" and want is not False
                     and not issubclass(self.Laplacian, BaseVectorLaplacian))

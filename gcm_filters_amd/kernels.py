@@ -576,9 +576,10 @@ class _DeviceLaplacian:
             return self._own_plan
         return PLAN_CACHE.get(key, factory, () if (on_gpu or mode == "verify") else self._planes)
 
-    def _run_stacked(self, given, field, spec, out_lead, core):
+    def _run_stacked(self, given, field, spec, out_lead, core, adjoint=False, like=None):
         """One call of the stacked plan on the field broadcast to (..., *glead, ny, nx), or None where that plan does not take the call
-        (the library offers no backward evaluation for this polynomial: the per-level route then runs)."""
+        (the library offers no backward evaluation for this polynomial: the per-level route then runs).
+        adjoint: the transpose of that call (gcmf_apply_adjoint), like: None or the forward call's input."""
         nbatch = int(np.prod(out_lead, dtype=np.int64))
         full = tuple(out_lead) + tuple(core)
         c = 2 / spec.s_max if self.is_dimensional else 2 / (spec.s_max * spec.dx_min_sq)
@@ -596,16 +597,33 @@ class _DeviceLaplacian:
                 fb = field if tuple(field.shape) == full else field.expand(*full)
                 src = fb if (fb.dtype == torch.float64 and fb.is_contiguous()) else fb.to(torch.float64).contiguous()
                 out = torch.empty(full, dtype=torch.float64, device=field.device)
+                lk = None
+                if like is not None:
+                    lk = like if _is_torch(like) else torch.as_tensor(np.asarray(like))
+                    lk = lk.detach().to(field.device).expand(*full).to(torch.float64).contiguous()
                 if nbatch:
                     cur = torch.cuda.current_stream(dev)
-                    plan.apply(p, c, [src.data_ptr()], [out.data_ptr()], nbatch, device_ptrs=True, stream=cur.cuda_stream)
+                    if adjoint:
+                        plan.apply_adjoint(p, c, [src.data_ptr()], [out.data_ptr()], nbatch, likes=None if lk is None else [lk.data_ptr()],
+                                           device_ptrs=True, stream=cur.cuda_stream)
+                    else:
+                        plan.apply(p, c, [src.data_ptr()], [out.data_ptr()], nbatch, device_ptrs=True, stream=cur.cuda_stream)
                     if src is not field:
                         src.record_stream(cur)
+                    if lk is not None and lk is not like:
+                        lk.record_stream(cur)
             else:
                 host = field.detach().cpu().numpy() if _is_torch(field) else np.asarray(field)
                 src = np.ascontiguousarray(np.broadcast_to(host, full), dtype=np.float64)
                 out = _host_output(full, np.float64)
-                if nbatch:
+                lk = None
+                if like is not None:
+                    lk = like.detach().cpu().numpy() if _is_torch(like) else np.asarray(like)
+                    lk = np.ascontiguousarray(np.broadcast_to(lk, full), dtype=np.float64)
+                if nbatch and adjoint:
+                    plan.apply_adjoint(p, c, [src.ctypes.data], [out.ctypes.data], nbatch, likes=None if lk is None else [lk.ctypes.data],
+                                       device_ptrs=False)
+                elif nbatch:
                     plan.apply(p, c, [src.ctypes.data], [out.ctypes.data], nbatch, device_ptrs=False)
             if nbatch:
                 _note_path(plan.last_path(), plan.device)
@@ -613,9 +631,11 @@ class _DeviceLaplacian:
             raise _translate(e) from None
         return [_same_kind(out, given)]
 
-    def _run_levels(self, fields, spec, out_f32, forward=False, backward_f32=False, mask_from_nan=False, faces_from_nan=False):
+    def _run_levels(self, fields, spec, out_f32, forward=False, backward_f32=False, mask_from_nan=False, faces_from_nan=False,
+                    adjoint=False, like=None):
         given = list(fields)
         fields = [_unwrap(f) for f in fields]
+        like = None if like is None else [_unwrap(a) for a in like]
         shape = tuple(fields[0].shape)
         if len(shape) < 2:
             raise ValueError("fields need at least two (y, x) dimensions")
@@ -627,7 +647,7 @@ class _DeviceLaplacian:
         # (faces_from_nan: the stacked plan's levels are not the entries' -- the per-level plans run the flagged call, as for mask_from_nan)
         if self._stacked and spec is not None and not forward and not mask_from_nan and not faces_from_nan and self._NCOMP == 1 \
                 and out_lead[pad:] == self._glead:
-            res = self._run_stacked(given[0], fields[0], spec, out_lead, core)
+            res = self._run_stacked(given[0], fields[0], spec, out_lead, core, adjoint, None if like is None else like[0])
             if res is not None:
                 return res
         outs = None
@@ -637,8 +657,11 @@ class _DeviceLaplacian:
             for f in fields:
                 fb = f.expand(*out_lead, *core) if _is_torch(f) else np.broadcast_to(f, out_lead + core)
                 sub.append(fb[idx])
+            sub_like = None
+            if like is not None:
+                sub_like = [(a.expand(*out_lead, *core) if _is_torch(a) else np.broadcast_to(a, out_lead + core))[idx] for a in like]
             res = lap._run(sub, spec=spec, out_f32=out_f32, forward=forward, backward_f32=backward_f32, mask_from_nan=mask_from_nan,
-                           faces_from_nan=faces_from_nan)
+                           faces_from_nan=faces_from_nan, adjoint=adjoint, like=sub_like)
             if outs is None:
                 if _is_torch(res[0]):
                     import torch
@@ -691,7 +714,7 @@ class _DeviceLaplacian:
         return PLAN_CACHE.get(key, factory, () if (on_gpu or mode == "verify") else self._planes)
 
     def _run(self, fields: Sequence, spec=None, out_f32: bool = False, forward: bool = False, backward_f32: bool = False,
-             mask_from_nan: bool = False, faces_from_nan: bool = False):
+             mask_from_nan: bool = False, faces_from_nan: bool = False, adjoint: bool = False, like: Optional[Sequence] = None):
         """Shared driver of __call__ (spec None: one Laplacian) and of filter_func (spec: whole polynomial).
         forward: evaluate the polynomial by the reference's forward recurrence with its accumulation scheme (f64 running sum
         also for f32 state) even where the library would evaluate it backwards (Filter(evaluation="reference")).
@@ -701,7 +724,19 @@ class _DeviceLaplacian:
         (Filter(nan_mask=True); the three land-mask grid types, spec given).
         faces_from_nan: the same contract on the three flux-form grid types (Filter(nan_mask="auto"), spec given): the library folds
         every slice's face coefficients from the plan's and the slice's NaNs inside the call (GCMF_FACES_FROM_NAN); where that call is
-        not on offer -- forward, float32, nx % 4 != 0, no backward cut -- the explicit masks run as grid variables (_gap_fallback)."""
+        not on offer -- forward, float32, nx % 4 != 0, no backward cut -- the explicit masks run as grid variables (_gap_fallback).
+        adjoint: the TRANSPOSE of that filter application (spec given; gcmf_apply_adjoint, adjoint.py) applied to `fields`.  like: None
+        or the forward application's inputs, one per field and of their shape: where they are NaN the result is 0, and the masks /
+        faces of mask_from_nan / faces_from_nan are derived from them (required then).  The plan, and with it the precision, is the
+        forward application's: chosen from `like` (from `fields` without it) and the grid variables."""
+        if adjoint:
+            if spec is None:
+                raise ValueError("adjoint needs a filter application")
+            if self.GRID_TYPE is GridType.VECTOR_B_GRID:
+                raise NotImplementedError("VECTOR_B_GRID has no adjoint: its Laplacian has no diagonal symmetrizer D with L^T = D L D^-1; "
+                                          "it needs a transposed stencil kernel")
+            if (mask_from_nan or faces_from_nan) and like is None:
+                raise ValueError("the adjoint of a nan_mask filter needs `like`, the forward input whose NaNs are the gaps")
         if mask_from_nan and (spec is None or self.GRID_TYPE not in NAN_MASK_GRID_TYPES):
             raise ValueError("mask_from_nan needs a filter application on one of the grid types "
                              + ", ".join(g.name for g in NAN_MASK_GRID_TYPES))
@@ -709,21 +744,25 @@ class _DeviceLaplacian:
             raise ValueError("faces_from_nan needs a filter application (without mask_from_nan) on one of the grid types "
                              + ", ".join(g.name for g in GAP_FOLD_GRID_TYPES))
         if self._glead is not None:
-            return self._run_levels(fields, spec, out_f32, forward, backward_f32, mask_from_nan, faces_from_nan)
+            return self._run_levels(fields, spec, out_f32, forward, backward_f32, mask_from_nan, faces_from_nan, adjoint, like)
         given = list(fields)
         fields = [_unwrap(f) for f in fields]
+        if like is not None:
+            like = [_unwrap(a) for a in like]
+            if len(like) != len(fields) or any(tuple(a.shape) != tuple(fields[0].shape) for a in like):
+                raise ValueError("`like` must have the shape of the field it belongs to")
         shape = tuple(fields[0].shape)
         if len(shape) < 2:
             raise ValueError("fields need at least two (y, x) dimensions")
         for f in fields[1:]:
             if tuple(f.shape) != shape:
                 raise ValueError("u and v must have the same shape")
-        dtype = compute_dtype(list(fields) + list(self._planes))
+        dtype = compute_dtype(list(fields if like is None else like) + list(self._planes))
         ny, nx = shape[-2:]
         nbatch = int(np.prod(shape[:-2], dtype=np.int64)) if len(shape) > 2 else 1
         gpu = all(_on_gpu(f) for f in fields)
         if faces_from_nan and nbatch and (forward or dtype != _lib.F64 or nx % 4):
-            return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32)
+            return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32, adjoint, like)
         if spec is None:
             out_np = _lib.np_dtype(dtype)
         else:
@@ -733,9 +772,14 @@ class _DeviceLaplacian:
             dev = fields[0].device.index
             plan = self._plan(dtype, (ny, nx), dev)
             if faces_from_nan and nbatch and not plan.clenshaw_cut(int(spec.n_steps), nbatch):
-                return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32)
+                return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32, adjoint, like)
             tdt = torch.float64 if dtype == _lib.F64 else torch.float32
             ins = [f if (f.dtype == tdt and f.is_contiguous()) else f.to(tdt).contiguous() for f in fields]
+            likes = None
+            if like is not None:
+                likes = [a if _is_torch(a) else torch.as_tensor(np.asarray(a)) for a in like]
+                likes = [a if (a.device == fields[0].device and a.dtype == tdt and a.is_contiguous())
+                         else a.detach().to(device=fields[0].device, dtype=tdt).contiguous() for a in likes]
             outs = [torch.empty(shape, dtype=torch.float64 if out_np == np.float64 else torch.float32,
                                 device=fields[0].device) for _ in fields]
             if nbatch:
@@ -744,23 +788,30 @@ class _DeviceLaplacian:
                 cur = torch.cuda.current_stream(dev)
                 try:
                     self._call(plan, spec, [t.data_ptr() for t in ins], [t.data_ptr() for t in outs], nbatch,
-                               True, out_f32, cur.cuda_stream, forward, backward_f32, mask_from_nan, faces_from_nan)
+                               True, out_f32, cur.cuda_stream, forward, backward_f32, mask_from_nan, faces_from_nan,
+                               adjoint, None if likes is None else [t.data_ptr() for t in likes])
                 except _lib.GcmfError as e:
                     if not (faces_from_nan and _no_backward_cut(e)):
                         raise
-                    return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32)
+                    return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32, adjoint, like)
                 for t, f in zip(ins, fields):   # inputs converted above are temporaries: keep them alive until the stream is done
+                    if t is not f:
+                        t.record_stream(cur)
+                for t, f in zip(likes or (), like or ()):
                     if t is not f:
                         t.record_stream(cur)
             return [_same_kind(o, g) for o, g in zip(outs, given)]   # (cupy in, cupy out -- as the reference's gpu_compat path)
         plan = self._plan(dtype, (ny, nx))
         if faces_from_nan and nbatch and not plan.clenshaw_cut(int(spec.n_steps), nbatch):
-            return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32)
+            return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32, adjoint, like)
         host = [f.detach().cpu().numpy() if _is_torch(f) else np.asarray(f) for f in fields]
         ins = [np.ascontiguousarray(f, dtype=_lib.np_dtype(dtype)) for f in host]
         outs = [_host_output(shape, out_np) for _ in fields]
+        likes = None
+        if like is not None:
+            likes = [np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else np.asarray(a), dtype=_lib.np_dtype(dtype)) for a in like]
         if nbatch == 1 and spec is not None and self._NCOMP == 1 and ny * nx >= host_blocks.MIN_CELLS and not forward and not backward_f32 \
-                and not mask_from_nan and not faces_from_nan:   # (the row blocks are plans of their own, with the static mask)
+                and not mask_from_nan and not faces_from_nan and not adjoint:   # (the row blocks are plans of their own, with the static mask)
             # one large host field: upload / recurrence / download overlapped by row blocks (host_blocks.py)
             pipe = self._row_blocks(plan, dtype, ny, nx, spec)
             if pipe is not None:
@@ -775,11 +826,12 @@ class _DeviceLaplacian:
         if nbatch:
             try:
                 self._call(plan, spec, [a.ctypes.data for a in ins], [a.ctypes.data for a in outs], nbatch, False,
-                           out_f32, 0, forward, backward_f32, mask_from_nan, faces_from_nan)
+                           out_f32, 0, forward, backward_f32, mask_from_nan, faces_from_nan,
+                           adjoint, None if likes is None else [a.ctypes.data for a in likes])
             except _lib.GcmfError as e:
                 if not (faces_from_nan and _no_backward_cut(e)):
                     raise
-                return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32)
+                return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32, adjoint, like)
         return outs
 
     def _run_bank(self, field, specs, faces_from_nan: bool = False):
@@ -854,11 +906,11 @@ class _DeviceLaplacian:
             src.record_stream(cur)
         return _same_kind(out, given)
 
-    def _gap_fallback(self, given, fields, spec, out_f32, forward, backward_f32):
+    def _gap_fallback(self, given, fields, spec, out_f32, forward, backward_f32, adjoint=False, like=None):
         """faces_from_nan where the flagged call is not on offer: wet_mask * notnull(field) built here and handed in as a grid variable
         with the field's leading dims -- the per-level (or stacked) route that existed before the flag, the same contract, slower.  The
         plans it makes belong to this one field's gaps and do not stay in the plan cache."""
-        f = fields[0]
+        f = like[0] if adjoint else fields[0]   # (the adjoint's gaps are the forward input's)
         wm = self._planes[0]   # (wet_mask is the first grid argument of the three kinds)
         if _is_torch(f):
             import torch
@@ -869,7 +921,7 @@ class _DeviceLaplacian:
             m = (~np.isnan(np.asarray(f))).astype(w.dtype) * w
         with plan_cache_mode("off"):
             lap = type(self)(m, *self._planes[1:], _skip_kappa_one=True, _stack_levels=self._stack_levels)
-            return lap._run(given, spec=spec, out_f32=out_f32, forward=forward, backward_f32=backward_f32)
+            return lap._run(given, spec=spec, out_f32=out_f32, forward=forward, backward_f32=backward_f32, adjoint=adjoint, like=like)
 
     def _row_blocks(self, plan, dtype, ny, nx, spec):
         """The row-block pipeline of `plan` for this polynomial length, built once the plan has seen a few single-field
@@ -902,16 +954,21 @@ class _DeviceLaplacian:
             return pipe
 
     def _call(self, plan, spec, ins, outs, nbatch, device_ptrs, out_f32, stream, forward=False, backward_f32=False,
-              mask_from_nan=False, faces_from_nan=False):
+              mask_from_nan=False, faces_from_nan=False, adjoint=False, likes=None):
         try:
             if spec is None:
                 plan.laplacian(ins, outs, nbatch, device_ptrs=device_ptrs, stream=stream)
             else:
                 # shift of the spectrum to [-1, 1]: reference filter.py:170-173
                 c = 2 / spec.s_max if self.is_dimensional else 2 / (spec.s_max * spec.dx_min_sq)
-                plan.apply(np.asarray(spec.p, dtype=np.float64), c, ins, outs, nbatch, device_ptrs=device_ptrs,
-                           out_f32=out_f32, stream=stream, forward=forward, backward_f32=backward_f32,
-                           mask_from_nan=mask_from_nan, faces_from_nan=faces_from_nan)
+                if adjoint:
+                    plan.apply_adjoint(np.asarray(spec.p, dtype=np.float64), c, ins, outs, nbatch, likes=likes, device_ptrs=device_ptrs,
+                                       out_f32=out_f32, stream=stream, forward=forward, backward_f32=backward_f32,
+                                       mask_from_nan=mask_from_nan, faces_from_nan=faces_from_nan)
+                else:
+                    plan.apply(np.asarray(spec.p, dtype=np.float64), c, ins, outs, nbatch, device_ptrs=device_ptrs,
+                               out_f32=out_f32, stream=stream, forward=forward, backward_f32=backward_f32,
+                               mask_from_nan=mask_from_nan, faces_from_nan=faces_from_nan)
                 _note_path(plan.last_path(), plan.device)
         except _lib.GcmfError as e:
             raise _translate(e) from None

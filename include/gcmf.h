@@ -244,6 +244,49 @@ int gcmf_apply(gcmf_plan *plan, const double *p, int n_steps, double c, const vo
                void *const *out, int64_t nbatch, uint32_t flags, void *stream);
 
 /*
+ * THE ADJOINT: out = F^T in, F being the linear map gcmf_apply(plan, p, n_steps, c, ., flags) applies to finite fields -- what a loss
+ * that contains the filter needs for its gradient, and what variational methods call directly.  (The reference has no counterpart.)
+ * No transposed stencil runs: for every grid type but one the transpose of the whole filter is the filter itself between two diagonal
+ * scalings,  F^T = D F D^-1:
+ *   REGULAR, REGULAR_WITH_LAND                                   D = 1
+ *   REGULAR_AREA_WEIGHTED, REGULAR_WITH_LAND_AREA_WEIGHTED,
+ *   TRIPOLAR_REGULAR_WITH_LAND_AREA_WEIGHTED                     D = area^2    (a symmetric stencil between prepare, * area, and finalize, / area)
+ *   IRREGULAR_WITH_LAND, MOM5U, MOM5T, TRIPOLAR_POP_WITH_LAND    D = area      (L = diag(1 / area) M, M symmetric: one coefficient per face, and
+ *                                                                               the tripole fold i <-> nx-1-i is symmetric too)
+ *   VECTOR_C_GRID                                                D = (area_u, area_v)
+ *   VECTOR_B_GRID                                                none: GCMF_ERR_UNSUPPORTED (its Laplacian has no diagonal symmetrizer;
+ *                                                                it needs a transposed stencil kernel)
+ * D is 1 on land cells and on cells cut off from the sea (F is diagonal there, so the identity holds for any finite non-zero D, and
+ * junk metrics on land never reach the result).  D is taken from the planes the plan holds: ra = 1 / area on the flux kinds (in * ra,
+ * then out / ra: the exact symmetrizer of the operator the kernels apply), the area plane of the area-weighted kinds; a VECTOR_C_GRID
+ * plan keeps copies of area_u and area_v for it -- two planes more per C-grid plan.  area_u / area_v <= 0 (where the reference zeroes a
+ * row of L but not its column) break the identity; the library does not look for them.
+ * How it runs: one streaming pass (in / D into a scratch plane of the plan), gcmf_apply's own schedule on that plane -- whatever path
+ * gcmf_apply takes with these flags: on-chip, strips, zipped, tables, forward or backward --, one streaming pass over `out` (times D, in
+ * place).  Both passes are forms of k_prepare (csrc/gcmf_scalar.hip); they use 16-byte accesses where the planes of the call allow and
+ * element accesses otherwise.  gcmf_last_kernel, gcmf_last_kernel_geometry and gcmf_plan_last_path answer for the inner schedule;
+ * gcmf_last_timing covers the schedule and the two passes (one launch per pass and component).
+ * Layout, dtypes, GCMF_DEVICE_PTRS, GCMF_OUT_F32 and the other flags, the stream contract and THE PLANES OF A CALL are gcmf_apply's; `out`
+ * must not overlap `in` or `like` as byte ranges (GCMF_ERR_INVALID_ARG).  Host pointers are staged through HBM one launch at a time
+ * (`in`, `like` and `out`), without gcmf_apply's chunk pipeline.
+ * `like`: NULL, or ncomp pointers to the forward call's input planes (plan dtype, `in`'s layout).  Only their NaN pattern is read: where
+ * `like` is NaN, `in` is taken as 0 and the result is 0 -- a NaN input cell has no derivative (the forward shows it to its neighbours as
+ * the value 0, at every step of the recurrence, and returns NaN in the cell itself).  The pre-scale therefore hands the schedule a NaN
+ * in such a cell, so that it is read as 0 at every step again -- F restricted to the finite cells is the polynomial of a principal
+ * submatrix, and so is its transpose -- and the post-scale writes 0 there.  (REGULAR and REGULAR_AREA_WEIGHTED, whose stencil does not
+ * mask a NaN: the cell is set to 0 once.)  With GCMF_MASK_FROM_NAN or GCMF_FACES_FROM_NAN `like` is required (NULL:
+ * GCMF_ERR_INVALID_ARG): the per-entry masks / faces are derived from `like`, exactly the forward call's.
+ * Stacked plans (gcmf_plan_create_levels): entry b uses the scaling planes of level b % nlev, like the filter itself.
+ * Scratch: one plane of the plan dtype per component and entry of a launch, in the plan's work buffer (grow-only, freed by
+ * gcmf_plan_destroy).  Option "adjoint_scratch_mb" (default 4096) bounds it: a longer batch is cut into consecutive launches of at least
+ * one entry each; same bits.
+ * GCMF_ERR_UNSUPPORTED, naming the function and the limit: VECTOR_B_GRID, row slabs, GCMF_PLAN_SELF_RING; and whatever gcmf_apply
+ * refuses for these flags.
+ */
+extern int gcmf_apply_adjoint(gcmf_plan *plan, const double *p, int n_steps, double c, const void *const *in, const void *const *like,
+                              void *const *out, int64_t nbatch, uint32_t flags, void *stream);
+
+/*
  * A FILTER BANK: nbank polynomials of ONE degree applied to the same nfield fields in one call -- a sweep over filter scales, whose
  * polynomials share n_steps, c and the grid (s_max does not depend on the filter scale) and differ in p alone:
  *     out[j * nfield + i] = the polynomial p[j * (n_steps + 1) .. (j + 1) * (n_steps + 1)) applied to in[i]      (j < nbank, i < nfield)
@@ -558,7 +601,9 @@ int gcmf_set_tuning(gcmf_plan *plan, int rows_per_wave, int xcd_remap, int multi
  * " nt=1" when the streaming form ran),
  * "gap_scratch_mb" N (GCMF_FACES_FROM_NAN: the most scratch, in MiB, the per-entry planes of one launch may take; default 4096; a batch
  * whose planes need more is cut into consecutive launches of at least one entry; same bits; gcmf_apply_bank_gaps: per field, not per
- * entry, and the FIELDS are cut into runs).  Unknown names: GCMF_ERR_INVALID_ARG. */
+ * entry, and the FIELDS are cut into runs), "adjoint_scratch_mb" N (gcmf_apply_adjoint: the most scratch, in MiB, the pre-scaled planes
+ * of one launch may take; default 4096; a longer batch is cut into consecutive launches of at least one entry; same bits).  Unknown
+ * names: GCMF_ERR_INVALID_ARG. */
 int gcmf_set_option(gcmf_plan *plan, const char *name, int value);
 
 /* Last error text of the calling thread (never NULL). */

@@ -1,0 +1,529 @@
+"""The adjoint of the filter on the GPU: ``Filter.adjoint`` / ``adjoint_to_vector``, torch autograd through ``apply``, and the C ABI
+(``gcmf_apply_adjoint``).
+
+F^T = D F D^-1 with the diagonal D of ``gcm_filters_amd.adjoint`` (tests/test_adjoint_rule.py checks that rule against dense matrices
+of the oracle), so the truth of ``adjoint(g)`` is ``post * O.filter_func(spec, kind, pre * g, gv)``.  Gates are those of
+tests/test_gpu_parity.py for f64: rel_err <= 1e-11 and an identical NaN pattern.  Shapes: (96, 160) -- two column windows that wrap --
+and (200, 520) -- five windows and several strips."""
+import functools
+import warnings
+
+import numpy as np
+import pytest
+from numpy.random import PCG64, Generator
+
+from gcm_filters_amd import Filter, FilterBank, FilterShape, GridType, _lib, testing as T
+from gcm_filters_amd.adjoint import adjoint_scaling
+from gcm_filters_amd.kernels import ALL_KERNELS
+from oracle import gcmf_oracle as O
+from test_gpu_parity import rel_err
+
+pytestmark = pytest.mark.gpu
+
+SMALL, BLOCKED = (96, 160), (200, 520)
+SHAPES = {"96x160": SMALL, "200x520": BLOCKED}
+CGRID = "VECTOR_C_GRID"
+KINDS = list(T.SCALAR_GRIDS) + [CGRID]
+LAND_KINDS = ["REGULAR_WITH_LAND", "REGULAR_WITH_LAND_AREA_WEIGHTED", "IRREGULAR_WITH_LAND", "MOM5U", "MOM5T",
+              "TRIPOLAR_REGULAR_WITH_LAND_AREA_WEIGHTED", "TRIPOLAR_POP_WITH_LAND"]
+GATE = 1e-11
+
+
+def grid_vars(kind, shape):
+    if kind == CGRID:
+        return dict(T.vector_grid_vars(kind, shape))
+    gv = dict(T.scalar_grid_vars(kind, shape))
+    if kind == "IRREGULAR_WITH_LAND":
+        gv["kappa_w"], gv["kappa_s"] = T.smooth_kappa(shape, 11), T.smooth_kappa(shape, 12)
+    return gv
+
+
+def make_filter(kind, gv, n_steps, **kw):
+    dx = T.grid_dx_min(kind, gv)
+    shape = FilterShape.GAUSSIAN if kind in T.VECTOR_GRIDS else FilterShape.TAPER
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")     # ("n_steps below the default": the polynomials here are chosen for their launch cuts)
+        return Filter(filter_scale=6.0 * dx, dx_min=dx, filter_shape=shape, n_steps=n_steps, grid_type=GridType[kind], grid_vars=gv, **kw)
+
+
+def spec_of(flt):
+    fs = flt.filter_spec
+    return O.FilterSpec(fs.n_steps, fs.s_max, np.asarray(fs.p), fs.dx_min_sq)
+
+
+def fields(shape, n, seed):
+    return np.stack([T.random_field(shape, seed + b) for b in range(n)])
+
+
+def oracle_adjoint(kind, gv, spec, g):
+    """post * F(pre * g), entry by entry; g: (nb, ny, nx), the C-grid a pair of those."""
+    pre, post = adjoint_scaling(GridType[kind], gv)
+    with np.errstate(all="ignore"):
+        if kind == CGRID:
+            res = [O.filter_func_vec(spec, kind, pre[0] * a, pre[1] * b, gv) for a, b in zip(*g)]
+            return np.stack([post[0] * r[0] for r in res]), np.stack([post[1] * r[1] for r in res])
+        return np.stack([post * O.filter_func(spec, kind, pre * a, gv) for a in g])
+
+
+@functools.lru_cache(maxsize=None)
+def parity_case(kind, shape, n_steps):
+    """(grid variables, the cotangents of three entries, the oracle's adjoint of them): computed once, shared by the cases."""
+    gv = grid_vars(kind, shape)
+    spec = spec_of(make_filter(kind, gv, n_steps))
+    if kind == CGRID:
+        g = (fields(shape, 3, 300), fields(shape, 3, 400))
+    else:
+        g = fields(shape, 3, 300)
+    return gv, g, oracle_adjoint(kind, gv, spec, g)
+
+
+def check(got, want, what, gate=GATE):
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape, what
+    assert np.array_equal(np.isnan(got), np.isnan(want)), (what, "NaN pattern")
+    err = rel_err(got, want)
+    print(f"{what}: rel_err {err:.3e}")
+    assert err <= gate, (what, err)
+    return err
+
+
+# ---- 1. oracle parity ---------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("evaluation", ["auto", "reference"])
+@pytest.mark.parametrize("nb", [1, 3])
+@pytest.mark.parametrize("long", [False, True], ids=["short", "long"])
+@pytest.mark.parametrize("shape", list(SHAPES), ids=list(SHAPES))
+@pytest.mark.parametrize("kind", KINDS)
+def test_oracle_parity(kind, shape, long, nb, evaluation):
+    import torch
+    shape = SHAPES[shape]
+    n_steps = ((12, 44) if kind == CGRID else (24, 63))[long]
+    gv, g, want = parity_case(kind, shape, n_steps)
+    flt = make_filter(kind, gv, n_steps, evaluation=evaluation)
+    what = (kind, shape, n_steps, nb, evaluation)
+    if kind == CGRID:
+        gu, gw = g[0][:nb], g[1][:nb]
+        got = flt.adjoint_to_vector(gu, gw)
+        dev = flt.adjoint_to_vector(torch.from_numpy(gu).cuda(), torch.from_numpy(gw).cuda())
+        for q in range(2):
+            assert isinstance(got[q], np.ndarray) and dev[q].is_cuda
+            check(got[q], want[q][:nb], what + ("uv"[q],))
+            assert np.array_equal(got[q], dev[q].cpu().numpy(), equal_nan=True), (what, "numpy in and a device tensor in differ")
+        return
+    got = flt.adjoint(g[:nb])
+    dev = flt.adjoint(torch.from_numpy(g[:nb]).cuda())
+    assert isinstance(got, np.ndarray) and dev.is_cuda and dev.dtype == torch.float64
+    check(got, want[:nb], what)
+    assert np.array_equal(got, dev.cpu().numpy(), equal_nan=True), (what, "numpy in and a device tensor in differ")
+
+
+# ---- 2. the dot-product identity through the public API -------------------------------------------------------------------------------
+def coast_grid_vars(kind, coast, shape):
+    gv = grid_vars(kind, shape)
+    gv["wet_mask"] = T.coastline(coast, shape, seed=7, tripolar=kind.startswith("TRIPOLAR"), cuts=(20,))
+    return gv
+
+
+COAST_CASES = [(k, c) for k in LAND_KINDS for c in T.coastline_names(k.startswith("TRIPOLAR"))]
+
+
+@pytest.mark.parametrize("kind,coast", COAST_CASES, ids=[f"{k}-{c}" for k, c in COAST_CASES])
+def test_dot_product_identity_on_coastlines(kind, coast):
+    """<g, apply(f)> = <adjoint(g, like=f), f>, summed over the cells where f is finite, for every treatment of the values on land.
+    Bound: the element gate applied to both sides, 1e-11 (sum|g||apply f| + sum|adjoint g||f|)."""
+    gv = coast_grid_vars(kind, coast, SMALL)
+    flt = make_filter(kind, gv, 24)
+    f0, g = T.random_field(SMALL, 510), T.random_field(SMALL, 511)
+    for how in T.LAND_TREATMENTS:
+        f = T.treat_land(f0, gv["wet_mask"], how, seed=3)
+        y = flt.apply(f)
+        a = flt.adjoint(g, like=f)
+        fin = np.isfinite(f)
+        assert np.array_equal(np.isnan(y), np.isnan(f)) and np.isfinite(a).all()
+        assert np.all(a[~fin] == 0), (kind, coast, how, "the adjoint is not 0 where `like` is NaN")
+        lhs, rhs = np.sum(g[fin] * y[fin]), np.sum(a[fin] * f[fin])
+        bound = GATE * (np.sum(np.abs(g[fin] * y[fin])) + np.sum(np.abs(a[fin] * f[fin])))
+        print(f"{kind} {coast} {how}: <g, F f> {lhs:.15e}  <F^T g, f> {rhs:.15e}  diff {abs(lhs - rhs):.2e}  bound {bound:.2e}")
+        assert abs(lhs - rhs) <= bound, (kind, coast, how, lhs, rhs, bound)
+
+
+# ---- 3. nan_mask ------------------------------------------------------------------------------------------------------------------------
+def gappy(shape, nb, seed, frac=0.16):
+    out = fields(shape, nb, 100 + seed)
+    for b in range(nb):
+        out[b][Generator(PCG64(1000 * seed + b)).random(shape) < frac] = np.nan
+    return out
+
+
+@pytest.mark.parametrize("kind,nan_mask", [("REGULAR_WITH_LAND", True), ("REGULAR_WITH_LAND_AREA_WEIGHTED", True),
+                                           ("TRIPOLAR_REGULAR_WITH_LAND_AREA_WEIGHTED", "auto"), ("IRREGULAR_WITH_LAND", "auto"),
+                                           ("MOM5U", "auto"), ("MOM5T", "auto")])
+@pytest.mark.parametrize("shape", list(SHAPES), ids=list(SHAPES))
+def test_nan_mask_adjoint_is_the_adjoint_of_the_explicit_masks(kind, nan_mask, shape):
+    """Fields with 16 % gaps: adjoint(g, like=f) of Filter(nan_mask=...) is bit for bit the adjoint, with the same `like`, of a Filter
+    built from the explicit wet_mask * notnull(f) -- the forward guarantees those bits and the scalings are the same -- and 0 on the gaps."""
+    shape = SHAPES[shape]
+    nb = 2
+    gv = grid_vars(kind, shape)
+    f = gappy(shape, nb, seed=LAND_KINDS.index(kind))
+    g = fields(shape, nb, 620)
+    flt = make_filter(kind, gv, 24, nan_mask=nan_mask)
+    got = flt.adjoint(g, like=f)
+    assert flt.last_path == "strips"
+    assert np.isfinite(got).all() and np.all(got[np.isnan(f)] == 0)
+    masks = (gv["wet_mask"] * ~np.isnan(f)).astype(gv["wet_mask"].dtype)
+    explicit = make_filter(kind, {**gv, "wet_mask": masks}, 24)
+    want = explicit.adjoint(g, like=f)
+    assert np.array_equal(got, want), (kind, shape, rel_err(got, want))
+    # ... and it is the transpose of that filter: the dot-product identity on the finite cells
+    y = flt.apply(f)
+    fin = np.isfinite(f)
+    lhs, rhs = np.sum(g[fin] * y[fin]), np.sum(got[fin] * f[fin])
+    assert abs(lhs - rhs) <= GATE * (np.sum(np.abs(g[fin] * y[fin])) + np.sum(np.abs(got[fin] * f[fin])))
+
+
+# ---- 4. levels --------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["IRREGULAR_WITH_LAND", "MOM5U", "MOM5T"])
+@pytest.mark.parametrize("shape", list(SHAPES), ids=list(SHAPES))
+def test_stacked_levels_give_the_bits_of_the_per_level_route(kind, shape, monkeypatch):
+    from gcm_filters_amd import kernels as K
+    from test_gpu_level_stack import level_grid_vars, level_of
+    shape, nlev = SHAPES[shape], 3
+    gv = level_grid_vars(kind, shape, nlev)
+    g = fields(shape, 2 * nlev, 640).reshape((2, nlev) + shape)
+    like = g[::-1].copy()
+    like[0, 1, 5:9, 7:30] = np.nan
+    res = {}
+    for stack in ("1", "0"):
+        monkeypatch.setenv("GCMF_STACK_LEVELS", stack)
+        K.clear_plan_cache()
+        flt = make_filter(kind, gv, 24)
+        res[stack] = (flt.adjoint(g), flt.adjoint(g, like=like))
+    K.clear_plan_cache()
+    for a, b in zip(res["1"], res["0"]):
+        assert np.array_equal(a, b), (kind, shape, rel_err(a, b))
+    assert np.all(res["1"][1][np.isnan(like)] == 0)
+    spec = spec_of(make_filter(kind, gv, 24))
+    for l in range(nlev):
+        check(res["1"][0][1, l], oracle_adjoint(kind, level_of(gv, l), spec, g[1, l][None])[0], (kind, shape, "level", l))
+
+
+# ---- 5. float32 plans -------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", KINDS)
+def test_float32_plans(kind):
+    """The adjoint's rel_err against the f64 oracle is at most 4 x the rel_err the forward apply of the same Filter shows against the
+    oracle on the same case (the forward is the parent's code; 4 covers the two extra roundings and the scaling planes' own)."""
+    shape, n_steps = SMALL, (12 if kind == CGRID else 24)
+    gv, g, want = parity_case(kind, shape, n_steps)
+    gv32 = {k: v.astype("f4") for k, v in gv.items()}
+    flt = make_filter(kind, gv32, n_steps)
+    spec = spec_of(make_filter(kind, gv, n_steps))
+    if kind == CGRID:
+        gu, gw = g[0][:1].astype("f4"), g[1][:1].astype("f4")
+        fwd = flt.apply_to_vector(gu, gw)
+        adj = flt.adjoint_to_vector(gu, gw)
+        with np.errstate(all="ignore"):
+            tru = O.filter_func_vec(spec, kind, g[0][0], g[1][0], gv)
+        e_fwd = max(rel_err(fwd[q][0], tru[q]) for q in range(2))
+        e_adj = max(rel_err(adj[q][0], want[q][0]) for q in range(2))
+    else:
+        fwd, adj = flt.apply(g[:1].astype("f4")), flt.adjoint(g[:1].astype("f4"))
+        with np.errstate(all="ignore"):
+            tru = O.filter_func(spec, kind, g[0], gv)
+        e_fwd, e_adj = rel_err(fwd[0], tru), rel_err(adj[0], want[0])
+    print(f"{kind} f32: forward rel_err {e_fwd:.3e}, adjoint rel_err {e_adj:.3e}")
+    assert e_adj <= 4 * e_fwd, (kind, e_adj, e_fwd)
+
+
+# ---- 6. autograd ------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["REGULAR", "REGULAR_WITH_LAND_AREA_WEIGHTED", "IRREGULAR_WITH_LAND", "TRIPOLAR_POP_WITH_LAND"])
+@pytest.mark.parametrize("dt", ["f8", "f4"])
+def test_grad_of_apply_is_the_adjoint(kind, dt):
+    import torch
+    gv = grid_vars(kind, SMALL)
+    flt = make_filter(kind, gv, 24)
+    x0 = T.random_field(SMALL, 700).astype(dt)
+    x0[np.asarray(gv.get("wet_mask", np.ones(SMALL))) == 0] = np.nan
+    w = torch.from_numpy(T.random_field(SMALL, 701)).cuda()
+    x = torch.from_numpy(x0).cuda().requires_grad_(True)
+    y = flt.apply(x)
+    assert y.grad_fn is not None and y.dtype == torch.float64
+    (w * torch.nan_to_num(y)).sum().backward()
+    want = flt.adjoint(w, like=x.detach())
+    assert x.grad.dtype == x.dtype and x.grad.shape == x.shape
+    assert torch.equal(x.grad, want.to(x.dtype)), rel_err(x.grad.cpu().numpy(), want.cpu().numpy())
+    assert torch.all(x.grad[torch.isnan(x.detach())] == 0)
+    # a tensor under no_grad, a tensor that does not require grad and a numpy array give today's bits, without a grad_fn
+    with torch.no_grad():
+        quiet = flt.apply(x)
+    plain = flt.apply(x.detach())
+    assert quiet.grad_fn is None and plain.grad_fn is None
+    assert torch.equal(torch.nan_to_num(quiet), torch.nan_to_num(y.detach())) and torch.equal(torch.nan_to_num(plain), torch.nan_to_num(quiet))
+    assert np.array_equal(flt.apply(x0), plain.cpu().numpy(), equal_nan=True)
+
+
+def test_grad_of_apply_to_vector_is_the_adjoint():
+    import torch
+    gv = grid_vars(CGRID, SMALL)
+    flt = make_filter(CGRID, gv, 12)
+    u = torch.from_numpy(T.random_field(SMALL, 710)).cuda().requires_grad_(True)
+    v = torch.from_numpy(T.random_field(SMALL, 711)).cuda().requires_grad_(True)
+    wu, wv = (torch.from_numpy(T.random_field(SMALL, s)).cuda() for s in (712, 713))
+    fu, fv = flt.apply_to_vector(u, v)
+    assert fu.grad_fn is not None and fv.grad_fn is not None
+    ((wu * fu).sum() + (wv * fv).sum()).backward()
+    au, av = flt.adjoint_to_vector(wu, wv)
+    assert torch.equal(u.grad, au) and torch.equal(v.grad, av)
+    pu, pv = flt.apply_to_vector(u.detach(), v.detach())
+    assert pu.grad_fn is None and torch.equal(pu, fu.detach()) and torch.equal(pv, fv.detach())
+
+
+def test_the_b_grid_raises_instead_of_detaching():
+    import torch
+    (u, v), gv = T.vector_case("VECTOR_B_GRID", SMALL)
+    flt = make_filter("VECTOR_B_GRID", gv, 12)
+    tu, tv = torch.from_numpy(u).cuda().requires_grad_(True), torch.from_numpy(v).cuda()
+    with pytest.raises(NotImplementedError, match="symmetrizer"):
+        flt.apply_to_vector(tu, tv)
+    with pytest.raises(NotImplementedError, match="symmetrizer"):
+        flt.adjoint_to_vector(tv, tv)
+    out = flt.apply_to_vector(tu.detach(), tv)      # without a gradient: as before
+    assert out[0].grad_fn is None and np.array_equal(out[0].cpu().numpy(), flt.apply_to_vector(u, v)[0])
+
+
+@pytest.mark.parametrize("route", ["0", "1"], ids=["loop", "bank"])
+def test_grad_of_filter_bank_is_the_sum_of_the_adjoints(route, monkeypatch):
+    import torch
+    monkeypatch.setenv("GCMF_FILTER_BANK", route)
+    kind = "IRREGULAR_WITH_LAND"
+    gv = grid_vars(kind, SMALL)
+    dx = T.grid_dx_min(kind, gv)
+    bank = FilterBank([3 * dx, 4.5 * dx, 6 * dx], dx_min=dx, filter_shape=FilterShape.TAPER, n_steps=24, grid_type=GridType[kind], grid_vars=gv)
+    x = torch.from_numpy(T.random_field(SMALL, 720)).cuda().requires_grad_(True)
+    w = torch.from_numpy(fields(SMALL, 3, 721)).cuda()
+    y = bank.apply(x)
+    assert y.grad_fn is not None and bank.last_route == ("bank" if route == "1" else "loop")
+    (w * y).sum().backward()
+    want = None
+    for j, flt in enumerate(bank.filters):
+        term = flt.adjoint(w[j], like=x.detach())
+        want = term if want is None else want + term
+    assert torch.equal(x.grad, want)
+    with torch.no_grad():
+        assert torch.equal(bank.apply(x), y.detach())
+
+
+GRADCHECK = (16, 24)      # the smallest fixture grid with nx % 4 == 0
+
+
+def gradcheck_filter(kind):
+    gv = grid_vars(kind, GRADCHECK)
+    return make_filter(kind, gv, 8), gv
+
+
+@pytest.mark.parametrize("kind", ["IRREGULAR_WITH_LAND", "REGULAR_WITH_LAND_AREA_WEIGHTED", "TRIPOLAR_POP_WITH_LAND"])
+def test_gradcheck(kind):
+    import torch
+    flt, _ = gradcheck_filter(kind)
+    x = torch.from_numpy(T.random_field(GRADCHECK, 730)).cuda().requires_grad_(True)
+    assert torch.autograd.gradcheck(flt.apply, (x,), eps=1e-3, atol=1e-9)      # (the map is linear: any eps will do)
+
+
+def test_gradcheck_c_grid():
+    import torch
+    flt, _ = gradcheck_filter(CGRID)
+    u = torch.from_numpy(T.random_field(GRADCHECK, 731)).cuda().requires_grad_(True)
+    v = torch.from_numpy(T.random_field(GRADCHECK, 732)).cuda().requires_grad_(True)
+    assert torch.autograd.gradcheck(flt.apply_to_vector, (u, v), eps=1e-3, atol=1e-9)
+
+
+def test_gradgradcheck():
+    """The backward is a Function of its own whose derivative is the forward."""
+    import torch
+    flt, _ = gradcheck_filter("IRREGULAR_WITH_LAND")
+    x = torch.from_numpy(T.random_field(GRADCHECK, 733)).cuda().requires_grad_(True)
+    g = torch.from_numpy(T.random_field(GRADCHECK, 734)).cuda().requires_grad_(True)
+    assert torch.autograd.gradgradcheck(flt.apply, (x,), (g,), eps=1e-3, atol=1e-9)
+
+
+# ---- 7. C ABI ---------------------------------------------------------------------------------------------------------------------------
+def _status(fn, *a, **k):
+    try:
+        fn(*a, **k)
+    except _lib.GcmfError as e:
+        return e.status, e.message
+    return _lib.OK, ""
+
+
+def plan_of(kind, gv, shape, dt="f8", **kw):
+    arrs = [np.asarray(gv[k], dtype=dt) for k in ALL_KERNELS[GridType[kind]].required_grid_args()]
+    return _lib.Plan(GridType[kind].value, _lib.dtype_code(dt), shape[0], shape[1], arrs, **kw)
+
+
+def test_c_abi_refusals():
+    import torch
+    ny, nx = SMALL
+    f = torch.from_numpy(fields(SMALL, 2, 800)).cuda()
+    out = torch.empty_like(f)
+    p = np.asarray(make_filter("REGULAR", {}, 24).filter_spec.p)
+
+    (_, _), gvb = T.vector_case("VECTOR_B_GRID", SMALL)
+    plan = plan_of("VECTOR_B_GRID", gvb, SMALL)
+    st, msg = _status(plan.apply_adjoint, p, 0.1, [f[0].data_ptr(), f[1].data_ptr()], [out[0].data_ptr(), out[1].data_ptr()], 1, device_ptrs=True)
+    assert st == _lib.ERR_UNSUPPORTED and "gcmf_apply_adjoint" in msg and "VECTOR_B_GRID" in msg and "symmetrizer" in msg, (st, msg)
+    plan.close()
+
+    gv = grid_vars("IRREGULAR_WITH_LAND", SMALL)
+    slab = plan_of("IRREGULAR_WITH_LAND", gv, SMALL, row_begin=0, row_end=ny // 2, halo=8)
+    st, msg = _status(slab.apply_adjoint, p, 0.1, [f.data_ptr()], [out.data_ptr()], 1, device_ptrs=True)
+    assert st == _lib.ERR_UNSUPPORTED and "gcmf_apply_adjoint" in msg and "row slab" in msg, (st, msg)
+    slab.close()
+    ring = plan_of("IRREGULAR_WITH_LAND", gv, SMALL, halo=8, self_ring=True)
+    st, msg = _status(ring.apply_adjoint, p, 0.1, [f.data_ptr()], [out.data_ptr()], 1, device_ptrs=True)
+    assert st == _lib.ERR_UNSUPPORTED and "gcmf_apply_adjoint" in msg and "GCMF_PLAN_SELF_RING" in msg, (st, msg)
+    ring.close()
+
+    plan = plan_of("IRREGULAR_WITH_LAND", gv, SMALL)
+    st, msg = _status(plan.apply_adjoint, p, 0.1, [f.data_ptr()], [out.data_ptr()], 2, device_ptrs=True, faces_from_nan=True)
+    assert st == _lib.ERR_INVALID_ARG and "like" in msg, (st, msg)
+    mplan = plan_of("REGULAR_WITH_LAND", grid_vars("REGULAR_WITH_LAND", SMALL), SMALL)
+    st, msg = _status(mplan.apply_adjoint, p, 0.1, [f.data_ptr()], [out.data_ptr()], 2, device_ptrs=True, mask_from_nan=True)
+    assert st == _lib.ERR_INVALID_ARG and "like" in msg, (st, msg)
+    mplan.close()
+    # `out` against `in` and against `like`, as byte ranges: one row into the other plane is as wrong as the plane itself
+    big = torch.zeros(4 * ny * nx + nx, dtype=torch.float64, device="cuda")
+    base = big.data_ptr()
+    for who, ins, likes in (("in", base, None), ("like", f.data_ptr(), base)):
+        for shift in (0, nx * 8, (2 * ny * nx - nx) * 8):
+            st, msg = _status(plan.apply_adjoint, p, 0.1, [ins], [base + shift], 2, likes=None if likes is None else [likes], device_ptrs=True)
+            assert st == _lib.ERR_INVALID_ARG and f"`{who}`" in msg and "alias" in msg, (who, shift, st, msg)
+            assert "overlap" in msg or (who == "in" and shift == 0), (who, shift, msg)
+        st, msg = _status(plan.apply_adjoint, p, 0.1, [ins], [base + 2 * ny * nx * 8], 2, likes=None if likes is None else [likes], device_ptrs=True)
+        assert st == _lib.OK, (who, st, msg)
+    torch.cuda.synchronize()
+    plan.close()
+
+
+@pytest.mark.parametrize("kind", ["IRREGULAR_WITH_LAND", "REGULAR_WITH_LAND_AREA_WEIGHTED", CGRID])
+def test_scratch_bound_cuts_the_batch_with_the_same_bits(kind):
+    """"adjoint_scratch_mb" set so that a batch of 5 runs as 1 + 1 + 1 + 1 + 1 and as 2 + 2 + 1: equal bits with one run; gcmf_apply
+    before and after an adjoint call on the same plan gives the same bits."""
+    import torch
+    shape, nb = BLOCKED, 5
+    gv = grid_vars(kind, shape)
+    flt = make_filter(kind, gv, 12 if kind == CGRID else 24)
+    p, c = np.asarray(flt.filter_spec.p), 2 / flt.filter_spec.s_max * (1.0 if flt.Laplacian.is_dimensional else 1 / flt.filter_spec.dx_min_sq)
+    ncomp = 2 if kind == CGRID else 1
+    plan = plan_of(kind, gv, shape)
+    g = [torch.from_numpy(fields(shape, nb, 810 + q)).cuda() for q in range(ncomp)]
+    like = [x.clone() for x in g[::-1]]
+    if kind != CGRID:
+        like[0][2, 40:60, 100:300] = float("nan")
+
+    def forward():
+        out = [torch.empty_like(x) for x in g]
+        plan.apply(p, c, [x.data_ptr() for x in g], [x.data_ptr() for x in out], nb, device_ptrs=True)
+        torch.cuda.synchronize()
+        return out
+
+    def adjoint(mb):
+        plan.set_option("adjoint_scratch_mb", mb)
+        out = [torch.empty_like(x) for x in g]
+        plan.apply_adjoint(p, c, [x.data_ptr() for x in g], [x.data_ptr() for x in out], nb, likes=[x.data_ptr() for x in like], device_ptrs=True)
+        torch.cuda.synchronize()
+        return out, plan.last_timing()[1]
+
+    before = forward()
+    one, n_one = adjoint(4096)
+    entry_mb = ncomp * shape[0] * shape[1] * 8 / 2**20      # 0.79 MiB per component
+    pair_mb = 2 * ncomp
+    assert 2 * entry_mb <= pair_mb < 3 * entry_mb           # two entries fit, three do not
+    singles, n_singles = adjoint(0)
+    pairs, n_pairs = adjoint(pair_mb)
+    assert n_singles > n_pairs > n_one, (n_singles, n_pairs, n_one)
+    for a, b, c2 in zip(one, singles, pairs):
+        assert torch.equal(a, b) and torch.equal(a, c2)
+    plan.set_option("adjoint_scratch_mb", 4096)
+    after = forward()
+    for a, b in zip(before, after):
+        assert torch.equal(a, b)
+    if kind != CGRID:
+        assert torch.all(one[0][torch.isnan(like[0])] == 0)
+    plan.close()
+
+
+@pytest.mark.parametrize("kind,dt", [("IRREGULAR_WITH_LAND", "f8"), ("REGULAR_WITH_LAND_AREA_WEIGHTED", "f4"), (CGRID, "f4"), ("REGULAR", "f8")])
+def test_planes_one_element_off_the_16_byte_boundary(kind, dt):
+    """The caller's planes are only element-aligned: `in`, `like` and `out` one element off a 16-byte boundary give the bits of aligned
+    ones (the two passes fall back to element accesses), and nothing outside the planes is written."""
+    import torch
+    shape, nb = SMALL, 2
+    n = nb * shape[0] * shape[1]
+    gv = grid_vars(kind, shape)
+    flt = make_filter(kind, {k: v.astype(dt) for k, v in gv.items()}, 12 if kind == CGRID else 24)
+    p, c = np.asarray(flt.filter_spec.p), 2 / flt.filter_spec.s_max * (1.0 if flt.Laplacian.is_dimensional else 1 / flt.filter_spec.dx_min_sq)
+    ncomp = 2 if kind == CGRID else 1
+    tdt = torch.float64 if dt == "f8" else torch.float32
+    plan = plan_of(kind, gv, shape, dt)
+    res = {}
+    for off in (0, 1):
+        bufs = {}
+        for name, seed, fill in (("in", 820, None), ("like", 830, None), ("out", 0, 7.0)):
+            for q in range(ncomp):
+                odt = torch.float64 if name == "out" else tdt
+                b = torch.full((n + 8,), 7.0, dtype=odt, device="cuda")
+                if fill is None:
+                    b[off:off + n] = torch.from_numpy(fields(shape, nb, seed + q).ravel()).to(tdt).cuda()
+                assert b.data_ptr() % 16 == 0
+                bufs[name, q] = b
+        ptr = lambda name: [bufs[name, q].data_ptr() + off * bufs[name, q].element_size() for q in range(ncomp)]
+        plan.apply_adjoint(p, c, ptr("in"), ptr("out"), nb, likes=ptr("like"), device_ptrs=True)
+        torch.cuda.synchronize()
+        for q in range(ncomp):
+            o = bufs["out", q]
+            assert torch.all(o[:off] == 7.0) and torch.all(o[off + n:] == 7.0), (kind, off, "wrote outside `out`")
+        res[off] = [bufs["out", q][off:off + n].clone() for q in range(ncomp)]
+    for a, b in zip(res[0], res[1]):
+        assert torch.isfinite(a).all() and torch.equal(a, b), (kind, dt)
+    plan.close()
+
+
+@pytest.mark.parametrize("kind", ["IRREGULAR_WITH_LAND", CGRID])
+def test_xarray_in_xarray_out(kind, monkeypatch):
+    """DataArrays go through the same apply_ufunc route as apply's (the model of xarray, tests/fake_xarray.py): core dims moved last,
+    `like` an operand of its own, the bits of the bare-array call."""
+    from conftest import xarray_backend
+    xr = xarray_backend("model", monkeypatch)
+    shape = (64, 96)
+    gv = grid_vars(kind, shape)
+    gvx = {k: xr.DataArray(v, dims=["y", "x"]) for k, v in gv.items()}
+    n_steps = 12 if kind == CGRID else 24
+    flt, bare = make_filter(kind, gvx, n_steps), make_filter(kind, gv, n_steps)
+    g = fields(shape, 4, 860).reshape((2, 2) + shape)
+    if kind == CGRID:
+        h = fields(shape, 4, 870).reshape((2, 2) + shape)
+        got = flt.adjoint_to_vector(xr.DataArray(g, dims=["t", "z", "y", "x"]), xr.DataArray(h, dims=["t", "z", "y", "x"]), dims=["y", "x"])
+        want = bare.adjoint_to_vector(g, h)
+        for a, b in zip(got, want):
+            assert a.dims == ("t", "z", "y", "x") and np.array_equal(a.data, b)
+        return
+    like = fields(shape, 4, 880).reshape((2, 2) + shape)
+    like[1, 0, 20:24, 30:60] = np.nan
+    got = flt.adjoint(xr.DataArray(g.transpose(2, 0, 1, 3), dims=["y", "t", "z", "x"]), dims=["y", "x"],
+                      like=xr.DataArray(like, dims=["t", "z", "y", "x"]))
+    assert got.dims == ("t", "z", "y", "x") and np.array_equal(got.data, bare.adjoint(g, like=like))
+    plain = flt.adjoint(xr.DataArray(g, dims=["t", "z", "y", "x"]), dims=["y", "x"])
+    assert np.array_equal(plain.data, bare.adjoint(g))
+
+
+def test_host_pointers_give_the_device_bits():
+    import torch
+    kind, shape, nb = "MOM5T", SMALL, 3
+    gv = grid_vars(kind, shape)
+    flt = make_filter(kind, gv, 24)
+    g = fields(shape, nb, 840)
+    like = fields(shape, nb, 850)
+    like[1, 10:14, :] = np.nan
+    host = flt.adjoint(g, like=like)
+    dev = flt.adjoint(torch.from_numpy(g).cuda(), like=torch.from_numpy(like).cuda())
+    assert np.array_equal(host, dev.cpu().numpy())
+    assert np.all(host[np.isnan(like)] == 0)
