@@ -25,6 +25,13 @@ DEVICE_PTRS, OUT_F32, FORWARD_RECURRENCE, NO_RESIDENT, BACKWARD_F32, MASK_FROM_N
 FACES_FROM_NAN = 0x40   # the flux-form kinds' counterpart of MASK_FROM_NAN (include/gcmf.h)
 STEP_FIRST, STEP_LAST, STEP_LAND_ZERO, STEP_LAND_FIXED, STEP_CLENSHAW = 0x1, 0x2, 0x4, 0x8, 0x10
 
+
+def apply_flags(device_ptrs, out_f32, forward, backward_f32, mask_from_nan, faces_from_nan) -> int:
+    """The flag word of gcmf_apply / gcmf_apply_adjoint for Plan.apply's and Plan.apply_adjoint's keywords."""
+    return ((DEVICE_PTRS if device_ptrs else 0) | (OUT_F32 if out_f32 else 0) | (FORWARD_RECURRENCE if forward else 0)
+            | (BACKWARD_F32 if backward_f32 else 0) | (MASK_FROM_NAN if mask_from_nan else 0) | (FACES_FROM_NAN if faces_from_nan else 0))
+
+
 EXPORTS = [
     "gcmf_plan_create", "gcmf_plan_destroy", "gcmf_grid_nplanes", "gcmf_grid_ncomp", "gcmf_grid_is_dimensional",
     "gcmf_grid_is_tripolar", "gcmf_plan_rows", "gcmf_apply", "gcmf_laplacian", "gcmf_cheb_step", "gcmf_prepare",
@@ -368,9 +375,7 @@ class Plan:
               device_ptrs: bool, out_f32: bool = False, stream: int = 0, forward: bool = False, backward_f32: bool = False,
               mask_from_nan: bool = False, faces_from_nan: bool = False):
         p = np.ascontiguousarray(p, dtype=np.float64)
-        flags = ((DEVICE_PTRS if device_ptrs else 0) | (OUT_F32 if out_f32 else 0) | (FORWARD_RECURRENCE if forward else 0)
-                 | (BACKWARD_F32 if backward_f32 else 0) | (MASK_FROM_NAN if mask_from_nan else 0)
-                 | (FACES_FROM_NAN if faces_from_nan else 0))
+        flags = apply_flags(device_ptrs, out_f32, forward, backward_f32, mask_from_nan, faces_from_nan)
         check(load().gcmf_apply(self._h, p.ctypes.data_as(C.POINTER(C.c_double)), len(p) - 1, float(c),
                                 _ptr_array(ins), _ptr_array(outs), int(nbatch), flags, C.c_void_p(stream or None)))
 
@@ -382,9 +387,7 @@ class Plan:
         and the result is 0; required with mask_from_nan / faces_from_nan, whose gaps are the NaNs of `likes`.  VECTOR_B_GRID, row
         slabs and self-ring plans raise GcmfError(ERR_UNSUPPORTED).  flags: further GCMF_* bits (GCMF_NO_RESIDENT)."""
         p = np.ascontiguousarray(p, dtype=np.float64)
-        bits = ((DEVICE_PTRS if device_ptrs else 0) | (OUT_F32 if out_f32 else 0) | (FORWARD_RECURRENCE if forward else 0)
-                | (BACKWARD_F32 if backward_f32 else 0) | (MASK_FROM_NAN if mask_from_nan else 0)
-                | (FACES_FROM_NAN if faces_from_nan else 0) | int(flags))
+        bits = apply_flags(device_ptrs, out_f32, forward, backward_f32, mask_from_nan, faces_from_nan) | int(flags)
         check(load().gcmf_apply_adjoint(self._h, p.ctypes.data_as(C.POINTER(C.c_double)), len(p) - 1, float(c), _ptr_array(ins),
                                         None if likes is None else _ptr_array(likes), _ptr_array(outs), int(nbatch), bits,
                                         C.c_void_p(stream or None)))

@@ -28,7 +28,7 @@ import numpy as np
 
 from . import _lib
 from .filter import FilterShape, _compute_filter_spec, _compute_n_steps_default
-from .kernels import ALL_KERNELS, GridType
+from .kernels import ALL_KERNELS, CallOptions, GridType
 
 
 def slab_bounds(ny: int, world: int, rank: int):
@@ -135,7 +135,7 @@ class SlabFilter:
             n = int(_compute_n_steps_default(ndim, shape, fk["filter_scale"], fk["dx_min"], tw))
         self.spec = _compute_filter_spec(fk["filter_scale"], fk["dx_min"], shape, tw, ndim, n)
         self.n_steps = n
-        self.c = 2 / self.spec.s_max if self.lap_cls.is_dimensional else 2 / (self.spec.s_max * self.spec.dx_min_sq)
+        self.c = CallOptions(spec=self.spec).shift(self.lap_cls.is_dimensional)
 
         self.row_begin, self.row_end = slab_bounds(self.ny, self.world, self.rank)
         min_rows = self.ny // self.world

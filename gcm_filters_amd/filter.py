@@ -23,6 +23,7 @@ from .kernels import (
     AreaWeightedMixin,
     BaseScalarLaplacian,
     BaseVectorLaplacian,
+    CallOptions,
     GridType,
     _is_torch,
 )
@@ -170,25 +171,30 @@ def _compute_filter_spec(filter_scale, dx_min, filter_shape, transition_width=np
 # ------------------------------------------------------------------------------------------------
 # the operator interface xarray.apply_ufunc calls (reference filter.py:154-291)
 # ------------------------------------------------------------------------------------------------
+def _make_run(filter_spec: FilterSpec, Laplacian, evaluation, plan_cache, **nan_flags):
+    """The `run(fields, args, adjoint=False, like=None)` closure of the two factories below; the call's options are built HERE, once
+    per factory -- a call constructs none.  The factory sets `run.func`, the function whose `last_path` a call updates."""
+    forward = CallOptions(spec=filter_spec, forward=_forward_only(evaluation), backward_f32=evaluation == "backward", **nan_flags)
+    adjoint_of = forward._replace(adjoint=True)
+    memo = _LaplacianMemo(Laplacian)
+
+    def run(fields, args, adjoint=False, like=None):
+        with plan_cache_mode(plan_cache):
+            out = memo.get(args)._run_with(fields, adjoint_of if adjoint else forward, like)   # (plan cached while the grid is unchanged)
+        run.func.last_path = kernels_last_path()
+        return out
+
+    return run
+
+
 def _create_filter_func(filter_spec: FilterSpec, Laplacian, evaluation: str = "auto", plan_cache=None, nan_mask=False):
     """Returns ``filter_func(field, *grid_args)``: first argument the field (last two axes = y, x; leading
     axes are independent batches), then the grid variables in ``Laplacian.required_grid_args()`` order.
     ``evaluation``, ``plan_cache``, ``nan_mask``: see ``Filter``."""
-    forward = _forward_only(evaluation)
-    backward = evaluation == "backward"
-    memo = _LaplacianMemo(Laplacian)
     # nan_mask="auto": per-slice masks by whichever route the library has for the kind -- mask bytes (the land-mask kinds) or face
     # coefficients (the flux-form kinds)
     faces = nan_mask == "auto" and Laplacian.GRID_TYPE in GAP_FOLD_GRID_TYPES
-    masks = bool(nan_mask) and not faces
-
-    def run(fields, args, adjoint=False, like=None):
-        with plan_cache_mode(plan_cache):
-            laplacian = memo.get(args)  # device plan: cached while the grid arrays are unchanged
-            out = laplacian._run(fields, spec=filter_spec, forward=forward, backward_f32=backward, mask_from_nan=masks,
-                                 faces_from_nan=faces, adjoint=adjoint, like=like)
-        filter_func.last_path = kernels_last_path()
-        return out
+    run = _make_run(filter_spec, Laplacian, evaluation, plan_cache, mask_from_nan=bool(nan_mask) and not faces, faces_from_nan=faces)
 
     def filter_func(field, *args):
         assert len(args) == len(Laplacian.required_grid_args())
@@ -206,6 +212,7 @@ def _create_filter_func(filter_spec: FilterSpec, Laplacian, evaluation: str = "a
         assert len(args) == len(Laplacian.required_grid_args())
         return run([field], args, adjoint=True, like=[like])[0]
 
+    run.func = filter_func
     filter_func.last_path = None
     filter_func.adjoint, filter_func.adjoint_like = adjoint_func, adjoint_like_func
     filter_func.operator = lambda args: _Operator(run, args)
@@ -345,16 +352,7 @@ def _check_nan_mask(nan_mask, grid_type):
 
 def _create_filter_func_vec(filter_spec: FilterSpec, Laplacian, evaluation: str = "auto", plan_cache=None):
     """Returns ``filter_func_vec(u, v, *grid_args) -> (u_filtered, v_filtered)``."""
-    forward = _forward_only(evaluation)
-    backward = evaluation == "backward"
-    memo = _LaplacianMemo(Laplacian)
-
-    def run(fields, args, adjoint=False, like=None):
-        with plan_cache_mode(plan_cache):
-            laplacian = memo.get(args)
-            u, v = laplacian._run(fields, spec=filter_spec, forward=forward, backward_f32=backward, adjoint=adjoint, like=like)
-        filter_func_vec.last_path = kernels_last_path()
-        return (u, v)
+    run = _make_run(filter_spec, Laplacian, evaluation, plan_cache)
 
     def filter_func_vec(ufield, vfield, *args):
         assert len(args) == len(Laplacian.required_grid_args())
@@ -365,13 +363,14 @@ def _create_filter_func_vec(filter_spec: FilterSpec, Laplacian, evaluation: str 
             import torch
             both = [x if _is_torch(x) else torch.as_tensor(np.asarray(x), device=y.device) for x, y in ((ufield, vfield), (vfield, ufield))]
             return tuple(_differentiable(_Operator(run, args), both))
-        return run([ufield, vfield], args)
+        return tuple(run([ufield, vfield], args))
 
     def adjoint_func_vec(ufield, vfield, *args):
         """The transpose of filter_func_vec applied to (ufield, vfield)."""
         assert len(args) == len(Laplacian.required_grid_args())
-        return run([ufield, vfield], args, adjoint=True)
+        return tuple(run([ufield, vfield], args, adjoint=True))
 
+    run.func = filter_func_vec
     filter_func_vec.last_path = None
     filter_func_vec.adjoint = adjoint_func_vec
     return filter_func_vec

@@ -17,7 +17,7 @@ Measured (MI355X, PCIe 5, 2400x3600 f64 numpy in / out): config 2 3.19 -> 2.66 m
 
 Costs: K extra plans (coefficient slabs of all blocks = (1 + 2 K n_steps / ny) x one set, plus eight state planes per block)
 and ~50 ms to build them, so the pipeline is only built for a plan that keeps being called with single host fields
-(`kernels._DeviceLaplacian._run`: from the third such call on).  `GCMF_HOST_BLOCKS=0` turns it off, `=K` fixes K.
+(`kernels._DeviceLaplacian._run_with`, for calls whose `CallOptions` are `plain`: from the third such call on).  `GCMF_HOST_BLOCKS=0` turns it off, `=K` fixes K.
 """
 import os
 import threading

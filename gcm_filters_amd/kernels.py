@@ -11,12 +11,13 @@ from __future__ import annotations
 import enum
 import contextlib
 import contextvars
+import operator
 import os
 import threading
 import warnings
 import weakref
 from collections import OrderedDict
-from typing import Any, Dict, Optional, Sequence, Tuple
+from typing import Any, Dict, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -75,7 +76,7 @@ ArrayType = np.ndarray
 # array plumbing: numpy (host) and torch (host or MI355X-resident) arrays
 # ------------------------------------------------------------------------------------------------
 def _is_torch(x) -> bool:
-    return type(x).__module__.split(".")[0] == "torch"
+    return (type(x).__module__ + ".").startswith("torch.")     # (the top-level package is torch; no list built per call)
 
 
 def _unwrap(x):
@@ -437,6 +438,91 @@ def current_device() -> int:
 
 
 # ------------------------------------------------------------------------------------------------
+# one call's options and the staging of its arrays
+# ------------------------------------------------------------------------------------------------
+class CallOptions(NamedTuple):
+    """What one call of a Laplacian asks for: ONE value that every driver below `_run` hands on (fields and `like` are data, beside it).
+    spec None: one Laplacian (__call__); a FilterSpec: the whole polynomial (filter_func).  out_f32: an f32 plan gives an f32 result.
+    forward: evaluate the polynomial by the reference's forward recurrence with its accumulation scheme (f64 running sum also for f32
+    state) even where the library would evaluate it backwards (Filter(evaluation="reference")).  backward_f32: evaluate it backwards
+    also for f32 scalar / B-grid fields, whose default is the forward recurrence (Filter(evaluation="backward"): faster, all f32).
+    mask_from_nan: every 2-D slice of the field is filtered with its own wet mask, wet_mask * [slice is not NaN] (Filter(nan_mask=True);
+    the three land-mask grid types, spec given).  faces_from_nan: the same contract on the three flux-form grid types
+    (Filter(nan_mask="auto"), spec given): the library folds every slice's face coefficients from the plan's and the slice's NaNs inside
+    the call (GCMF_FACES_FROM_NAN); where that call is not on offer -- forward, float32, nx % 4 != 0, no backward cut -- the explicit
+    masks run as grid variables (_gap_fallback).  adjoint: the TRANSPOSE of that filter application (spec given; gcmf_apply_adjoint,
+    adjoint.py) applied to the fields.  Its `like` is None or the forward application's inputs, one per field and of their shape: where
+    they are NaN the result is 0, and the masks / faces of mask_from_nan / faces_from_nan are derived from them (required then).  The
+    plan, and with it the precision, is the forward application's: chosen from `like` (from the fields without it) and the grid variables."""
+    spec: Any = None
+    out_f32: bool = False
+    forward: bool = False
+    backward_f32: bool = False
+    mask_from_nan: bool = False
+    faces_from_nan: bool = False
+    adjoint: bool = False
+
+    def check(self, grid_type, have_like):
+        """The combinations no grid type or no library call takes, refused before anything is staged."""
+        if not (self.adjoint or self.mask_from_nan or self.faces_from_nan):
+            return
+        if self.adjoint:
+            if self.spec is None:
+                raise ValueError("adjoint needs a filter application")
+            if grid_type is GridType.VECTOR_B_GRID:
+                raise NotImplementedError("VECTOR_B_GRID has no adjoint: its Laplacian has no diagonal symmetrizer D with L^T = D L D^-1; "
+                                          "it needs a transposed stencil kernel")
+            if (self.mask_from_nan or self.faces_from_nan) and not have_like:
+                raise ValueError("the adjoint of a nan_mask filter needs `like`, the forward input whose NaNs are the gaps")
+        if self.mask_from_nan and (self.spec is None or grid_type not in NAN_MASK_GRID_TYPES):
+            raise ValueError("mask_from_nan needs a filter application on one of the grid types "
+                             + ", ".join(g.name for g in NAN_MASK_GRID_TYPES))
+        if self.faces_from_nan and (self.spec is None or self.mask_from_nan or grid_type not in GAP_FOLD_GRID_TYPES):
+            raise ValueError("faces_from_nan needs a filter application (without mask_from_nan) on one of the grid types "
+                             + ", ".join(g.name for g in GAP_FOLD_GRID_TYPES))
+
+    def shift(self, is_dimensional):
+        """The factor c that shifts the Laplacian's spectrum to [-1, 1] (reference filter.py:170-173)."""
+        spec = self.spec
+        return 2 / spec.s_max if is_dimensional else 2 / (spec.s_max * spec.dx_min_sq)
+
+    @property
+    def p(self):
+        return np.asarray(self.spec.p, dtype=np.float64)
+
+    @property
+    def plain(self):
+        """Nothing but a polynomial and a result dtype: the calls that a plan with the static mask (a row block) answers as well."""
+        return not (self.forward or self.backward_f32 or self.mask_from_nan or self.faces_from_nan or self.adjoint)
+
+    def without_faces(self):
+        return self._replace(faces_from_nan=False)
+
+
+_DEVICE_PTR, _HOST_PTR = operator.methodcaller("data_ptr"), operator.attrgetter("ctypes.data")     # of a torch tensor, of a numpy array
+
+
+def _stage(a, dtype, device=None, full=None):
+    """A field, or a `like`, as the library reads it: in the plan's `dtype`, contiguous, on `device` (a torch.device; None: the host,
+    as numpy), broadcast to the shape `full` first where one is given.  Returns (array, whether it is a temporary of this call): what
+    is all of that already passes through as the same object; the temporaries of a device call must outlive it (record_stream)."""
+    if device is None:
+        host = a.detach().cpu().numpy() if _is_torch(a) else np.asarray(a)
+        if full is not None and tuple(host.shape) != tuple(full):
+            host = np.broadcast_to(host, full)
+        out = np.ascontiguousarray(host, dtype=_lib.np_dtype(dtype))
+        return out, out is not a
+    import torch
+    tdt = torch.float64 if dtype == _lib.F64 else torch.float32
+    t = a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a))     # (a numpy `like` beside device fields)
+    if full is not None and tuple(t.shape) != tuple(full):
+        t = t.expand(*full)
+    if not (t.dtype == tdt and t.is_contiguous() and t.device == device):
+        t = t.detach().to(device=device, dtype=tdt).contiguous()
+    return t, t is not a
+
+
+# ------------------------------------------------------------------------------------------------
 # base classes (reference kernels.py:43-104)
 # ------------------------------------------------------------------------------------------------
 class _DeviceLaplacian:
@@ -567,72 +653,48 @@ class _DeviceLaplacian:
             except _lib.GcmfError as e:
                 raise _translate(e) from None
 
+        return self._cached_plan(key, factory, on_gpu)
+
+    def _cached_plan(self, key, factory, on_gpu) -> _lib.Plan:
+        """The shared tail of _plan and _stacked_plan: the plan of `key` from the cache, or -- plan cache off -- a fresh one of our own."""
         mode = cache_mode()
-        if mode == "off":
+        if mode == "off":   # the reference's behaviour: a fresh Laplacian (validation + precompute) per call
             old = getattr(self, "_own_plan", None)
             if old is not None:
                 old.close()
             self._own_plan = factory()
             return self._own_plan
+        # ("verify": the key holds a hash of every plane -- nothing to protect, the caller's arrays stay writable)
         return PLAN_CACHE.get(key, factory, () if (on_gpu or mode == "verify") else self._planes)
 
-    def _run_stacked(self, given, field, spec, out_lead, core, adjoint=False, like=None):
+    def _run_stacked(self, given, field, opts, out_lead, core, like=None):
         """One call of the stacked plan on the field broadcast to (..., *glead, ny, nx), or None where that plan does not take the call
-        (the library offers no backward evaluation for this polynomial: the per-level route then runs).
-        adjoint: the transpose of that call (gcmf_apply_adjoint), like: None or the forward call's input."""
+        (no backward evaluation for this polynomial: the per-level route then runs).  like: None or the adjoint's forward input."""
         nbatch = int(np.prod(out_lead, dtype=np.int64))
         full = tuple(out_lead) + tuple(core)
-        c = 2 / spec.s_max if self.is_dimensional else 2 / (spec.s_max * spec.dx_min_sq)
-        p = np.asarray(spec.p, dtype=np.float64)
-        gpu = _on_gpu(field)
-        plan = self._stacked_plan(field.device.index if gpu else None)
+        device = field.device if _on_gpu(field) else None
+        plan = self._stacked_plan(None if device is None else device.index)
         if (plan.ny, plan.nx) != tuple(core):
             raise ValueError(f"field has spatial shape {tuple(core)} but the grid variables have shape {(plan.ny, plan.nx)}")
-        if nbatch and not plan.clenshaw_cut(int(spec.n_steps), nbatch):
+        if nbatch and not plan.clenshaw_cut(int(opts.spec.n_steps), nbatch):
             return None
-        try:
-            if gpu:
-                import torch
-                dev = field.device.index
-                fb = field if tuple(field.shape) == full else field.expand(*full)
-                src = fb if (fb.dtype == torch.float64 and fb.is_contiguous()) else fb.to(torch.float64).contiguous()
-                out = torch.empty(full, dtype=torch.float64, device=field.device)
-                lk = None
-                if like is not None:
-                    lk = like if _is_torch(like) else torch.as_tensor(np.asarray(like))
-                    lk = lk.detach().to(field.device).expand(*full).to(torch.float64).contiguous()
-                if nbatch:
-                    cur = torch.cuda.current_stream(dev)
-                    if adjoint:
-                        plan.apply_adjoint(p, c, [src.data_ptr()], [out.data_ptr()], nbatch, likes=None if lk is None else [lk.data_ptr()],
-                                           device_ptrs=True, stream=cur.cuda_stream)
-                    else:
-                        plan.apply(p, c, [src.data_ptr()], [out.data_ptr()], nbatch, device_ptrs=True, stream=cur.cuda_stream)
-                    if src is not field:
-                        src.record_stream(cur)
-                    if lk is not None and lk is not like:
-                        lk.record_stream(cur)
-            else:
-                host = field.detach().cpu().numpy() if _is_torch(field) else np.asarray(field)
-                src = np.ascontiguousarray(np.broadcast_to(host, full), dtype=np.float64)
-                out = _host_output(full, np.float64)
-                lk = None
-                if like is not None:
-                    lk = like.detach().cpu().numpy() if _is_torch(like) else np.asarray(like)
-                    lk = np.ascontiguousarray(np.broadcast_to(lk, full), dtype=np.float64)
-                if nbatch and adjoint:
-                    plan.apply_adjoint(p, c, [src.ctypes.data], [out.ctypes.data], nbatch, likes=None if lk is None else [lk.ctypes.data],
-                                       device_ptrs=False)
-                elif nbatch:
-                    plan.apply(p, c, [src.ctypes.data], [out.ctypes.data], nbatch, device_ptrs=False)
-            if nbatch:
-                _note_path(plan.last_path(), plan.device)
-        except _lib.GcmfError as e:
-            raise _translate(e) from None
+        staged = [_stage(a, _lib.F64, device, full) for a in ((field,) if like is None else (field, like))]
+        if device is None:
+            ptr, cur, out = _HOST_PTR, None, _host_output(full, np.float64)
+        else:
+            import torch
+            ptr, cur, out = _DEVICE_PTR, torch.cuda.current_stream(device.index), torch.empty(full, dtype=torch.float64, device=device)
+        if nbatch:
+            # (a float64 plan: out_f32 and backward_f32 say nothing about it, and this call has never carried them)
+            self._invoke(plan, CallOptions(spec=opts.spec, adjoint=opts.adjoint), [ptr(staged[0][0])], [ptr(out)], nbatch,
+                         device is not None, 0 if cur is None else cur.cuda_stream, None if like is None else [ptr(staged[1][0])])
+            if cur is not None:
+                for t, temporary in staged:
+                    if temporary:
+                        t.record_stream(cur)
         return [_same_kind(out, given)]
 
-    def _run_levels(self, fields, spec, out_f32, forward=False, backward_f32=False, mask_from_nan=False, faces_from_nan=False,
-                    adjoint=False, like=None):
+    def _run_levels(self, fields, opts, like=None):
         given = list(fields)
         fields = [_unwrap(f) for f in fields]
         like = None if like is None else [_unwrap(a) for a in like]
@@ -645,23 +707,18 @@ class _DeviceLaplacian:
         # the stacked plan: a whole filter, backward evaluation; entry b of the flattened leading shape runs on level b % nlev, so the
         # grid variables' leading shape must be the TAIL of the field's (none of its size-1 dims stretched by the field)
         # (faces_from_nan: the stacked plan's levels are not the entries' -- the per-level plans run the flagged call, as for mask_from_nan)
-        if self._stacked and spec is not None and not forward and not mask_from_nan and not faces_from_nan and self._NCOMP == 1 \
-                and out_lead[pad:] == self._glead:
-            res = self._run_stacked(given[0], fields[0], spec, out_lead, core, adjoint, None if like is None else like[0])
+        if self._stacked and opts.spec is not None and not (opts.forward or opts.mask_from_nan or opts.faces_from_nan) \
+                and self._NCOMP == 1 and out_lead[pad:] == self._glead:
+            res = self._run_stacked(given[0], fields[0], opts, out_lead, core, None if like is None else like[0])
             if res is not None:
                 return res
+        def level(arrays, idx):
+            return [(a.expand(*out_lead, *core) if _is_torch(a) else np.broadcast_to(a, out_lead + core))[idx] for a in arrays]
+
         outs = None
         for g, lap in self._level_laps().items():
             idx = tuple([slice(None)] * pad + [slice(None) if n == 1 else i for i, n in zip(g, self._glead)])
-            sub = []
-            for f in fields:
-                fb = f.expand(*out_lead, *core) if _is_torch(f) else np.broadcast_to(f, out_lead + core)
-                sub.append(fb[idx])
-            sub_like = None
-            if like is not None:
-                sub_like = [(a.expand(*out_lead, *core) if _is_torch(a) else np.broadcast_to(a, out_lead + core))[idx] for a in like]
-            res = lap._run(sub, spec=spec, out_f32=out_f32, forward=forward, backward_f32=backward_f32, mask_from_nan=mask_from_nan,
-                           faces_from_nan=faces_from_nan, adjoint=adjoint, like=sub_like)
+            res = lap._run_with(level(fields, idx), opts, None if like is None else level(like, idx))
             if outs is None:
                 if _is_torch(res[0]):
                     import torch
@@ -703,48 +760,19 @@ class _DeviceLaplacian:
             except _lib.GcmfError as e:
                 raise _translate(e) from None
 
-        mode = cache_mode()
-        if mode == "off":   # the reference's behaviour: a fresh Laplacian (validation + precompute) per call
-            old = getattr(self, "_own_plan", None)
-            if old is not None:
-                old.close()
-            self._own_plan = factory()
-            return self._own_plan
-        # ("verify": the key holds a hash of every plane -- nothing to protect, the caller's arrays stay writable)
-        return PLAN_CACHE.get(key, factory, () if (on_gpu or mode == "verify") else self._planes)
+        return self._cached_plan(key, factory, on_gpu)
 
     def _run(self, fields: Sequence, spec=None, out_f32: bool = False, forward: bool = False, backward_f32: bool = False,
              mask_from_nan: bool = False, faces_from_nan: bool = False, adjoint: bool = False, like: Optional[Sequence] = None):
-        """Shared driver of __call__ (spec None: one Laplacian) and of filter_func (spec: whole polynomial).
-        forward: evaluate the polynomial by the reference's forward recurrence with its accumulation scheme (f64 running sum
-        also for f32 state) even where the library would evaluate it backwards (Filter(evaluation="reference")).
-        backward_f32: evaluate it backwards also for f32 scalar / B-grid fields, whose default is the forward recurrence
-        (Filter(evaluation="backward"): faster, all f32).
-        mask_from_nan: every 2-D slice of the field is filtered with its own wet mask, wet_mask * [slice is not NaN]
-        (Filter(nan_mask=True); the three land-mask grid types, spec given).
-        faces_from_nan: the same contract on the three flux-form grid types (Filter(nan_mask="auto"), spec given): the library folds
-        every slice's face coefficients from the plan's and the slice's NaNs inside the call (GCMF_FACES_FROM_NAN); where that call is
-        not on offer -- forward, float32, nx % 4 != 0, no backward cut -- the explicit masks run as grid variables (_gap_fallback).
-        adjoint: the TRANSPOSE of that filter application (spec given; gcmf_apply_adjoint, adjoint.py) applied to `fields`.  like: None
-        or the forward application's inputs, one per field and of their shape: where they are NaN the result is 0, and the masks /
-        faces of mask_from_nan / faces_from_nan are derived from them (required then).  The plan, and with it the precision, is the
-        forward application's: chosen from `like` (from `fields` without it) and the grid variables."""
-        if adjoint:
-            if spec is None:
-                raise ValueError("adjoint needs a filter application")
-            if self.GRID_TYPE is GridType.VECTOR_B_GRID:
-                raise NotImplementedError("VECTOR_B_GRID has no adjoint: its Laplacian has no diagonal symmetrizer D with L^T = D L D^-1; "
-                                          "it needs a transposed stencil kernel")
-            if (mask_from_nan or faces_from_nan) and like is None:
-                raise ValueError("the adjoint of a nan_mask filter needs `like`, the forward input whose NaNs are the gaps")
-        if mask_from_nan and (spec is None or self.GRID_TYPE not in NAN_MASK_GRID_TYPES):
-            raise ValueError("mask_from_nan needs a filter application on one of the grid types "
-                             + ", ".join(g.name for g in NAN_MASK_GRID_TYPES))
-        if faces_from_nan and (spec is None or mask_from_nan or self.GRID_TYPE not in GAP_FOLD_GRID_TYPES):
-            raise ValueError("faces_from_nan needs a filter application (without mask_from_nan) on one of the grid types "
-                             + ", ".join(g.name for g in GAP_FOLD_GRID_TYPES))
+        """Shared driver of __call__ and filter_func: the keywords are CallOptions' fields (see there) and `like`, the adjoint's forward inputs."""
+        return self._run_with(fields, CallOptions(spec=spec, out_f32=out_f32, forward=forward, backward_f32=backward_f32,
+                                                  mask_from_nan=mask_from_nan, faces_from_nan=faces_from_nan, adjoint=adjoint), like)
+
+    def _run_with(self, fields: Sequence, opts: CallOptions, like: Optional[Sequence] = None):
+        """_run with its options in one value (filter.py builds its own once); device and host arrays take the same steps, in one body."""
+        opts.check(self.GRID_TYPE, like is not None)
         if self._glead is not None:
-            return self._run_levels(fields, spec, out_f32, forward, backward_f32, mask_from_nan, faces_from_nan, adjoint, like)
+            return self._run_levels(fields, opts, like)
         given = list(fields)
         fields = [_unwrap(f) for f in fields]
         if like is not None:
@@ -760,79 +788,50 @@ class _DeviceLaplacian:
         dtype = compute_dtype(list(fields if like is None else like) + list(self._planes))
         ny, nx = shape[-2:]
         nbatch = int(np.prod(shape[:-2], dtype=np.int64)) if len(shape) > 2 else 1
-        gpu = all(_on_gpu(f) for f in fields)
-        if faces_from_nan and nbatch and (forward or dtype != _lib.F64 or nx % 4):
-            return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32, adjoint, like)
-        if spec is None:
-            out_np = _lib.np_dtype(dtype)
+        spec = opts.spec
+        device = fields[0].device if all(_on_gpu(f) for f in fields) else None     # None: the host
+        gaps = opts.faces_from_nan and nbatch     # ... where the flagged call is not on offer: known from the call itself, or the plan's cut
+        plan = None
+        if not (gaps and (opts.forward or dtype != _lib.F64 or nx % 4)):
+            plan = self._plan(dtype, (ny, nx), None if device is None else device.index)
+        if gaps and (plan is None or not plan.clenshaw_cut(int(spec.n_steps), nbatch)):
+            return self._gap_fallback(given, fields, opts, like)
+        out_np = _lib.np_dtype(dtype) if spec is None else (np.float32 if (dtype == _lib.F32 and opts.out_f32) else np.float64)
+        ins = [_stage(f, dtype, device) for f in fields]      # pairs: (the staged array, whether it is a temporary of this call)
+        likes = None if like is None else [_stage(a, dtype, device) for a in like]
+        if device is None:
+            ptr, cur, outs = _HOST_PTR, None, [_host_output(shape, out_np) for _ in fields]
         else:
-            out_np = np.float32 if (dtype == _lib.F32 and out_f32) else np.float64
-        if gpu:
+            # (the device index is passed explicitly: torch.cuda.current_stream() without one costs ~10 us per call, and
+            # libgcmf selects the plan's device itself -- no device context manager on this path)
             import torch
-            dev = fields[0].device.index
-            plan = self._plan(dtype, (ny, nx), dev)
-            if faces_from_nan and nbatch and not plan.clenshaw_cut(int(spec.n_steps), nbatch):
-                return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32, adjoint, like)
-            tdt = torch.float64 if dtype == _lib.F64 else torch.float32
-            ins = [f if (f.dtype == tdt and f.is_contiguous()) else f.to(tdt).contiguous() for f in fields]
-            likes = None
-            if like is not None:
-                likes = [a if _is_torch(a) else torch.as_tensor(np.asarray(a)) for a in like]
-                likes = [a if (a.device == fields[0].device and a.dtype == tdt and a.is_contiguous())
-                         else a.detach().to(device=fields[0].device, dtype=tdt).contiguous() for a in likes]
-            outs = [torch.empty(shape, dtype=torch.float64 if out_np == np.float64 else torch.float32,
-                                device=fields[0].device) for _ in fields]
-            if nbatch:
-                # (the device index is passed explicitly: torch.cuda.current_stream() without one costs ~10 us per call, and
-                # libgcmf selects the plan's device itself -- no device context manager on this path)
-                cur = torch.cuda.current_stream(dev)
-                try:
-                    self._call(plan, spec, [t.data_ptr() for t in ins], [t.data_ptr() for t in outs], nbatch,
-                               True, out_f32, cur.cuda_stream, forward, backward_f32, mask_from_nan, faces_from_nan,
-                               adjoint, None if likes is None else [t.data_ptr() for t in likes])
-                except _lib.GcmfError as e:
-                    if not (faces_from_nan and _no_backward_cut(e)):
-                        raise
-                    return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32, adjoint, like)
-                for t, f in zip(ins, fields):   # inputs converted above are temporaries: keep them alive until the stream is done
-                    if t is not f:
-                        t.record_stream(cur)
-                for t, f in zip(likes or (), like or ()):
-                    if t is not f:
-                        t.record_stream(cur)
-            return [_same_kind(o, g) for o, g in zip(outs, given)]   # (cupy in, cupy out -- as the reference's gpu_compat path)
-        plan = self._plan(dtype, (ny, nx))
-        if faces_from_nan and nbatch and not plan.clenshaw_cut(int(spec.n_steps), nbatch):
-            return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32, adjoint, like)
-        host = [f.detach().cpu().numpy() if _is_torch(f) else np.asarray(f) for f in fields]
-        ins = [np.ascontiguousarray(f, dtype=_lib.np_dtype(dtype)) for f in host]
-        outs = [_host_output(shape, out_np) for _ in fields]
-        likes = None
-        if like is not None:
-            likes = [np.ascontiguousarray(a.detach().cpu().numpy() if _is_torch(a) else np.asarray(a), dtype=_lib.np_dtype(dtype)) for a in like]
-        if nbatch == 1 and spec is not None and self._NCOMP == 1 and ny * nx >= host_blocks.MIN_CELLS and not forward and not backward_f32 \
-                and not mask_from_nan and not faces_from_nan and not adjoint:   # (the row blocks are plans of their own, with the static mask)
-            # one large host field: upload / recurrence / download overlapped by row blocks (host_blocks.py)
+            ptr, cur = _DEVICE_PTR, torch.cuda.current_stream(device.index)
+            outs = [torch.empty(shape, dtype=torch.float64 if out_np == np.float64 else torch.float32, device=device) for _ in fields]
+        if device is None and nbatch == 1 and spec is not None and self._NCOMP == 1 and ny * nx >= host_blocks.MIN_CELLS and opts.plain:
+            # one large host field: upload / recurrence / download overlapped by row blocks (host_blocks.py: plans of their own, with the
+            # static mask).  Host only and deliberately forgiving: _row_blocks swallows the GcmfError of a pipeline that cannot be built
             pipe = self._row_blocks(plan, dtype, ny, nx, spec)
             if pipe is not None:
-                c = 2 / spec.s_max if self.is_dimensional else 2 / (spec.s_max * spec.dx_min_sq)
                 try:
-                    pipe.apply(np.asarray(spec.p, dtype=np.float64), c, ins[0].reshape(ny, nx), outs[0].reshape(ny, nx),
-                               bool(out_f32 and dtype == _lib.F32))
+                    pipe.apply(opts.p, opts.shift(self.is_dimensional), ins[0][0].reshape(ny, nx), outs[0].reshape(ny, nx),
+                               bool(opts.out_f32 and dtype == _lib.F32))
                 except _lib.GcmfError as e:
                     raise _translate(e) from None
                 _PATH.last = "host-row-blocks"
                 return outs
         if nbatch:
             try:
-                self._call(plan, spec, [a.ctypes.data for a in ins], [a.ctypes.data for a in outs], nbatch, False,
-                           out_f32, 0, forward, backward_f32, mask_from_nan, faces_from_nan,
-                           adjoint, None if likes is None else [a.ctypes.data for a in likes])
+                self._invoke(plan, opts, [ptr(t) for t, _ in ins], [ptr(t) for t in outs], nbatch, device is not None,
+                             0 if cur is None else cur.cuda_stream, None if likes is None else [ptr(t) for t, _ in likes])
             except _lib.GcmfError as e:
-                if not (faces_from_nan and _no_backward_cut(e)):
+                if not (opts.faces_from_nan and _no_backward_cut(e)):
                     raise
-                return self._gap_fallback(given, fields, spec, out_f32, forward, backward_f32, adjoint, like)
-        return outs
+                return self._gap_fallback(given, fields, opts, like)
+            if cur is not None:
+                for t, temporary in ins + (likes or []):   # converted above: keep them alive until the stream is done
+                    if temporary:
+                        t.record_stream(cur)
+        return [_same_kind(o, g) for o, g in zip(outs, given)]   # (cupy in, cupy out -- as the reference's gpu_compat path)
 
     def _run_bank(self, field, specs, faces_from_nan: bool = False):
         """FilterBank's one-batch route: the polynomials of `specs` (one degree, one s_max) on every 2-D slice of `field` through
@@ -866,20 +865,18 @@ class _DeviceLaplacian:
         plan = self._plan(_lib.F64, (ny, nx), dev)
         if not plan.bank_cut(n_steps, max(1, nbank * nfield)):
             return None
-        spec = specs[0]
-        c = 2 / spec.s_max if self.is_dimensional else 2 / (spec.s_max * spec.dx_min_sq)
-        P = np.ascontiguousarray([np.asarray(s.p, dtype=np.float64) for s in specs])
+        c = CallOptions(spec=specs[0]).shift(self.is_dimensional)
+        P =np.ascontiguousarray([np.asarray(s.p, dtype=np.float64) for s in specs])
         try:
             bound = max(1, int(os.environ.get("GCMF_BANK_ENTRIES", "") or BANK_ENTRIES))
         except ValueError:
             bound = BANK_ENTRIES
+        src, temporary = _stage(f, _lib.F64, f.device if gpu else None)
         if gpu:
-            src = f if (f.dtype == torch.float64 and f.is_contiguous()) else f.to(torch.float64).contiguous()
             out = torch.empty((nbank,) + shape, dtype=torch.float64, device=f.device)
             out4 = out.view(nbank, nfield, ny, nx)
-        else:
-            host = f.detach().cpu().numpy() if _is_torch(f) else np.asarray(f)
-            src = torch.as_tensor(np.ascontiguousarray(host, dtype=np.float64)).to(f"cuda:{dev}")
+        else:   # a host array goes up through torch
+            src = torch.as_tensor(src).to(f"cuda:{dev}")
             out = _host_output((nbank,) + shape, np.float64)
             out4 = torch.from_numpy(out.reshape(nbank, nfield, ny, nx))
         if nfield == 0:
@@ -902,15 +899,15 @@ class _DeviceLaplacian:
             _note_path(plan.last_path(), plan.device)
         except _lib.GcmfError as e:
             raise _translate(e) from None
-        if gpu and src is not f:
+        if gpu and temporary:
             src.record_stream(cur)
         return _same_kind(out, given)
 
-    def _gap_fallback(self, given, fields, spec, out_f32, forward, backward_f32, adjoint=False, like=None):
+    def _gap_fallback(self, given, fields, opts, like=None):
         """faces_from_nan where the flagged call is not on offer: wet_mask * notnull(field) built here and handed in as a grid variable
         with the field's leading dims -- the per-level (or stacked) route that existed before the flag, the same contract, slower.  The
         plans it makes belong to this one field's gaps and do not stay in the plan cache."""
-        f = like[0] if adjoint else fields[0]   # (the adjoint's gaps are the forward input's)
+        f = like[0] if opts.adjoint else fields[0]   # (the adjoint's gaps are the forward input's)
         wm = self._planes[0]   # (wet_mask is the first grid argument of the three kinds)
         if _is_torch(f):
             import torch
@@ -921,7 +918,7 @@ class _DeviceLaplacian:
             m = (~np.isnan(np.asarray(f))).astype(w.dtype) * w
         with plan_cache_mode("off"):
             lap = type(self)(m, *self._planes[1:], _skip_kappa_one=True, _stack_levels=self._stack_levels)
-            return lap._run(given, spec=spec, out_f32=out_f32, forward=forward, backward_f32=backward_f32, adjoint=adjoint, like=like)
+            return lap._run_with(given, opts.without_faces(), like)
 
     def _row_blocks(self, plan, dtype, ny, nx, spec):
         """The row-block pipeline of `plan` for this polynomial length, built once the plan has seen a few single-field
@@ -953,23 +950,21 @@ class _DeviceLaplacian:
             st["pipes"][n] = pipe
             return pipe
 
-    def _call(self, plan, spec, ins, outs, nbatch, device_ptrs, out_f32, stream, forward=False, backward_f32=False,
-              mask_from_nan=False, faces_from_nan=False, adjoint=False, likes=None):
+    def _invoke(self, plan, opts, ins, outs, nbatch, device_ptrs, stream, likes=None):
+        """The one call into the library: `opts` on `plan`, with host or device pointers (likes: the adjoint's, or None)."""
+        spec, out_f32, forward, backward_f32, mask_from_nan, faces_from_nan, adjoint = opts     # (one unpacking: this is the device path)
         try:
             if spec is None:
                 plan.laplacian(ins, outs, nbatch, device_ptrs=device_ptrs, stream=stream)
+                return
+            if adjoint:
+                plan.apply_adjoint(opts.p, opts.shift(self.is_dimensional), ins, outs, nbatch, likes=likes, device_ptrs=device_ptrs,
+                                   out_f32=out_f32, stream=stream, forward=forward, backward_f32=backward_f32,
+                                   mask_from_nan=mask_from_nan, faces_from_nan=faces_from_nan)
             else:
-                # shift of the spectrum to [-1, 1]: reference filter.py:170-173
-                c = 2 / spec.s_max if self.is_dimensional else 2 / (spec.s_max * spec.dx_min_sq)
-                if adjoint:
-                    plan.apply_adjoint(np.asarray(spec.p, dtype=np.float64), c, ins, outs, nbatch, likes=likes, device_ptrs=device_ptrs,
-                                       out_f32=out_f32, stream=stream, forward=forward, backward_f32=backward_f32,
-                                       mask_from_nan=mask_from_nan, faces_from_nan=faces_from_nan)
-                else:
-                    plan.apply(np.asarray(spec.p, dtype=np.float64), c, ins, outs, nbatch, device_ptrs=device_ptrs,
-                               out_f32=out_f32, stream=stream, forward=forward, backward_f32=backward_f32,
-                               mask_from_nan=mask_from_nan, faces_from_nan=faces_from_nan)
-                _note_path(plan.last_path(), plan.device)
+                plan.apply(opts.p, opts.shift(self.is_dimensional), ins, outs, nbatch, device_ptrs=device_ptrs, out_f32=out_f32,
+                           stream=stream, forward=forward, backward_f32=backward_f32, mask_from_nan=mask_from_nan, faces_from_nan=faces_from_nan)
+            _note_path(plan.last_path(), plan.device)
         except _lib.GcmfError as e:
             raise _translate(e) from None
 
