@@ -443,6 +443,41 @@ def cgrid_coast_vars(name, shape, seed=0, independent_q=False):
     return {k: gv[k] for k in FIXTURE_ARG_ORDER["VECTOR_C_GRID"]}
 
 
+VECTOR_MASKS = ("wet_mask_t", "wet_mask_q")
+VECTOR_KAPPAS = ("kappa_iso", "kappa_aniso")
+
+
+def vector_grid_vars_irregular(grid_type: str, shape=(128, 256), seed0=50, coast="", independent_q=False, coast_seed=0):
+    """VECTOR_C_GRID / VECTOR_B_GRID grid variables (plain float64, FIXTURE_ARG_ORDER order) on which no two planes are equal and none
+    is constant along x or along y -- what `vector_grid_vars` cannot offer: there no plane varies along x, every dy* plane is one
+    constant, dxT == dxCu, dxBu == dxCv, HUS == HTE, HUW == HTN == DXU, the areas are products of the spacings, and the B-grid's
+    coupling weights dmc, dme and dmw are exactly 0.
+
+    Every spacing and area plane is `vector_grid_vars`' times ``irregular_metric(shape, seed0 + position in FIXTURE_ARG_ORDER)`` (the
+    areas independently of the spacings: the reference takes them as inputs of their own).  C-grid kappas: ``smooth_kappa(13)`` and
+    ``0.5 * smooth_kappa(14)``, each times the same kind of noise; kappa_iso divided by its maximum, which so stays exactly 1.  Masks: the
+    fixture's, or with `coast` those of `cgrid_coast_vars(coast, shape, coast_seed, independent_q)` (C-grid only)."""
+    names = FIXTURE_ARG_ORDER[grid_type]
+    base = vector_grid_vars(grid_type, shape)
+    if coast:
+        if grid_type != "VECTOR_C_GRID":
+            raise ValueError("vector_grid_vars_irregular: only the C-grid has masks to draw a coastline with")
+        masks = cgrid_coast_vars(coast, shape, coast_seed, independent_q=independent_q)
+    gv = {}
+    for pos, name in enumerate(names):
+        noise = irregular_metric(shape, seed0 + pos)
+        if name in VECTOR_MASKS:
+            gv[name] = np.array(masks[name] if coast else base[name], dtype=np.float64)
+        elif name == "kappa_iso":
+            k = smooth_kappa(shape, 13) * noise
+            gv[name] = k / k.max()
+        elif name == "kappa_aniso":
+            gv[name] = 0.5 * smooth_kappa(shape, 14) * noise
+        else:
+            gv[name] = base[name] * noise
+    return gv
+
+
 def roll_rows(r, fields, gv):
     """(fields, grid variables) rolled by `r` rows along y (``np.roll(axis=-2)``): global row j becomes row (j + r) % ny.  A ring of slabs
     exchanges only across row ny-1 / row 0, so rolling every plane and the field alike moves that seam onto another row of the same

@@ -23,6 +23,10 @@ Outputs (committed):
                            gcm_filters_amd.testing.COASTLINES (and two C-grid mask variants) at 40 x 64: the 24-step Gaussian filter
                            and L(f) from the imported reference, in three treatments of the values on land.
 
+  reference_vector_metrics.npz (`--vector-metrics`) both vector kinds at 40 x 64 on testing.vector_grid_vars_irregular -- metric planes that
+                           all differ and vary along both axes, B-grid coupling weights that are not zero: L(u, v), the Gaussian at
+                           8 dx_min and the Taper at 4 dx_min from the imported reference; the C-grid also on a speckle coastline.
+
 `--out DIR` writes into DIR instead of this directory (to check that the committed files regenerate).
 
 No reference source text is copied anywhere: only numbers leave this script.
@@ -342,6 +346,56 @@ def make_coastlines(rf, rk, outdir):
               f"{os.path.getsize(os.path.join(outdir, fname)) // 1024} KiB on disk")
 
 
+# ------------------------------------------------------------------------------------------------
+# the vector kinds on metric planes that differ from one another: reference_vector_metrics.npz -- case builder shared with the tests
+# ------------------------------------------------------------------------------------------------
+VECTOR_METRICS_FILE = "reference_vector_metrics.npz"
+
+
+def vector_metrics_case_names():
+    """`grid/kind[/speckle_indq]`: L(u, v), the Gaussian at 8 dx_min and the Taper at 4 dx_min (default step counts) for both vector kinds
+    on testing.vector_grid_vars_irregular; the C-grid's Laplacian and Gaussian also on a speckle coastline with a wet_mask_q of its own."""
+    names = [f"{g}/{k}" for g in ("VECTOR_C_GRID", "VECTOR_B_GRID") for k in ("lap", "gauss", "taper")]
+    return names + ["VECTOR_C_GRID/lap/speckle_indq", "VECTOR_C_GRID/gauss/speckle_indq"]
+
+
+def build_vector_metrics_case(name: str, shape=SMALL):
+    """(grid, fields, grid_vars, filter kwargs or None) of a case of vector_metrics_case_names(): the seeded fields of vector_case."""
+    sys.path.insert(0, REPO)
+    from gcm_filters_amd import testing as T
+
+    parts = name.split("/")
+    grid, kind = parts[0], parts[1]
+    coast = dict(coast="speckle", independent_q=True) if len(parts) > 2 else {}
+    fields = (T.random_field(shape, 42), T.random_field(shape, 43))
+    gv = T.vector_grid_vars_irregular(grid, shape, **coast)
+    dx_min = T.grid_dx_min(grid, gv)
+    fk = {"lap": None, "gauss": dict(filter_scale=8.0 * dx_min, dx_min=dx_min, filter_shape="GAUSSIAN", n_steps=0),
+          "taper": dict(filter_scale=4.0 * dx_min, dx_min=dx_min, filter_shape="TAPER", n_steps=0)}[kind]
+    return grid, fields, gv, fk
+
+
+def make_vector_metrics(rf, rk, outdir):
+    out = {}
+    for name in vector_metrics_case_names():
+        grid, fields, gv, fk = build_vector_metrics_case(name)
+        cls = rk.ALL_KERNELS[rk.GridType[grid]]
+        args = [gv[k] for k in cls.required_grid_args()]
+        with np.errstate(all="ignore"):
+            if fk is None:
+                res = cls(**gv)(*fields)
+            else:
+                shape = rf.FilterShape[fk["filter_shape"]]
+                n = rf._compute_n_steps_default(2, shape, fk["filter_scale"], fk["dx_min"], np.pi)
+                spec = rf._compute_filter_spec(fk["filter_scale"], fk["dx_min"], shape, np.pi, 2, n)
+                res = rf._create_filter_func_vec(spec, cls)(*fields, *args)
+        out[name] = np.stack(res)
+        assert out[name].dtype == np.float64 and np.isfinite(out[name]).all(), name
+    path = os.path.join(outdir, VECTOR_METRICS_FILE)
+    np.savez_compressed(path, **out)
+    print(f"{VECTOR_METRICS_FILE}: {len(out)} arrays, {sum(v.nbytes for v in out.values()) // 1024} KiB raw, {os.path.getsize(path) // 1024} KiB on disk")
+
+
 # full-size cases: key -> (BASELINE config, filter scale in dx_min units (0 = the config's own), NaN on land?[, options])
 # options: level = the vertical level of config 5 (its fields are seeded per level); f32 = field AND grid variables cast to float32
 # before the reference sees them (its f32-input path: f32 recurrence, f64 running sum and result, SURVEY 8a A2)
@@ -418,6 +472,9 @@ def main():
         return 0
     if "--coastlines" in sys.argv:
         make_coastlines(rf, rk, HERE)
+        return 0
+    if "--vector-metrics" in sys.argv:
+        make_vector_metrics(rf, rk, HERE)
         return 0
 
     # 1. the reference's own goldens

@@ -72,6 +72,29 @@ def test_the_transpose_is_the_filter_between_two_scalings(kind):
         assert np.all(flat(pre, n) == 1) and np.all(flat(post, n) == 1)
 
 
+def test_the_c_grid_rule_holds_with_areas_of_their_own():
+    """On testing.vector_grid_vars_irregular area_u and area_v are independent planes, not dxCu * dyCu and dxCv * dyCv, and every metric
+    varies along x: D = (area_u, area_v) still symmetrizes the filter, and taking one area for the other does not."""
+    kind = "VECTOR_C_GRID"
+    n = SHAPE[0] * SHAPE[1]
+    gv = T.vector_grid_vars_irregular(kind, SHAPE)
+    spec = spec_for(kind, gv)
+    F = np.empty((2 * n, 2 * n))
+    for q in range(2 * n):
+        e = np.zeros(2 * n)
+        e[q] = 1.0
+        u, v = O.filter_func_vec(spec, kind, e[:n].reshape(SHAPE), e[n:].reshape(SHAPE), gv)
+        F[:, q] = np.concatenate([u.ravel(), v.ravel()])
+    assert np.isfinite(F).all()
+    pre, post = adjoint_scaling(GridType[kind], gv)
+    err = miss(F, flat(pre, 2 * n), flat(post, 2 * n))
+    print(f"{kind} on irregular metrics: max|F^T - post F pre| / max|F| = {err:.2e}")
+    assert err <= GATE, err
+    swapped = miss(F, flat(pre[::-1], 2 * n), flat(post[::-1], 2 * n))
+    print(f"{kind} on irregular metrics: area_u and area_v swapped miss by {swapped:.2e}")
+    assert swapped > 1e-3, swapped
+
+
 @pytest.mark.parametrize("kind,area", [("REGULAR_AREA_WEIGHTED", "area"), ("IRREGULAR_WITH_LAND", "area"), ("MOM5U", "area_u"),
                                        ("TRIPOLAR_POP_WITH_LAND", "tarea")])
 def test_the_wrong_power_of_the_area_misses(kind, area):

@@ -116,6 +116,42 @@ def test_oracle_parity(kind, shape, long, nb, evaluation):
     assert np.array_equal(got, dev.cpu().numpy(), equal_nan=True), (what, "numpy in and a device tensor in differ")
 
 
+@functools.lru_cache(maxsize=None)
+def irregular_c_grid_case(n_steps=12):
+    """`parity_case` for the C-grid on testing.vector_grid_vars_irregular: area_u and area_v are planes of their own there (on the spherical
+    fixture they are dxCu * dyCu and dxCv * dyCv and constant along x), and so are the scalings D = (area_u, area_v)."""
+    gv = T.vector_grid_vars_irregular(CGRID, SMALL)
+    assert not np.array_equal(gv["area_u"], gv["dxCu"] * gv["dyCu"]) and not np.array_equal(gv["area_u"], gv["area_v"])
+    spec = spec_of(make_filter(CGRID, gv, n_steps))
+    g = (fields(SMALL, 1, 300), fields(SMALL, 1, 400))
+    return gv, g, oracle_adjoint(CGRID, gv, spec, g)
+
+
+@pytest.mark.parametrize("evaluation", ["auto", "reference"])
+def test_oracle_parity_c_grid_irregular_metrics(evaluation):
+    n_steps = 12
+    gv, (gu, gw), want = irregular_c_grid_case(n_steps)
+    flt = make_filter(CGRID, gv, n_steps, evaluation=evaluation)
+    got = flt.adjoint_to_vector(gu, gw)
+    for q in range(2):
+        check(got[q], want[q], (CGRID, "irregular", SMALL, n_steps, 1, evaluation, "uv"[q]))
+
+
+def test_dot_product_identity_c_grid_irregular_metrics():
+    """<g, apply(f)> = <adjoint(g), f> over both components, on the irregular metrics.  Bound: the element gate applied to both sides."""
+    gv, _, _ = irregular_c_grid_case()
+    flt = make_filter(CGRID, gv, 12)
+    f = [T.random_field(SMALL, 520 + q) for q in range(2)]
+    g = [T.random_field(SMALL, 530 + q) for q in range(2)]
+    y = flt.apply_to_vector(*f)
+    a = flt.adjoint_to_vector(*g)
+    assert all(np.isfinite(x).all() for x in tuple(y) + tuple(a))
+    lhs, rhs = sum(np.sum(g[q] * y[q]) for q in range(2)), sum(np.sum(a[q] * f[q]) for q in range(2))
+    bound = GATE * sum(np.sum(np.abs(g[q] * y[q])) + np.sum(np.abs(a[q] * f[q])) for q in range(2))
+    print(f"C-grid irregular: <g, F f> {lhs:.15e}  <F^T g, f> {rhs:.15e}  diff {abs(lhs - rhs):.2e}  bound {bound:.2e}")
+    assert abs(lhs - rhs) <= bound, (lhs, rhs, bound)
+
+
 # ---- 2. the dot-product identity through the public API -------------------------------------------------------------------------------
 def coast_grid_vars(kind, coast, shape):
     gv = grid_vars(kind, shape)

@@ -63,6 +63,7 @@ class Case:
     coast: str = ""                     # a coastline of testing.COASTLINES instead of the fixture mask ("name", "name:kappa": with
                                         # testing.kappa_with_zeros, C-grid "name:indq": an independent wet_mask_q); tests/test_gpu_coastlines.py
     land_values: str = "nan"            # the values on land of a `coast` case: testing.LAND_TREATMENTS
+    metrics: str = ""                   # "irregular": a vector kind on testing.vector_grid_vars_irregular (tests/test_gpu_vector_metrics.py)
 
     def kernels(self):
         """The kernels this case reaches: `reaches`, else the one its regex names (a regex over several names names none)."""
@@ -296,7 +297,10 @@ def _coast_inputs(c: Case):
     name, _, variant = c.coast.partition(":")
     seed = zlib.crc32(c.id.encode()) % 10007
     if c.grid == "VECTOR_C_GRID":
-        gv = T.cgrid_coast_vars(name, c.shape, seed, independent_q=variant == "indq")
+        if c.metrics == "irregular":
+            gv = T.vector_grid_vars_irregular(c.grid, c.shape, coast=name, independent_q=variant == "indq", coast_seed=seed)
+        else:
+            gv = T.cgrid_coast_vars(name, c.shape, seed, independent_q=variant == "indq")
         fields = [np.stack([T.random_field(c.shape, s + 2 * l) for l in range(c.nb)]) if c.nb else T.random_field(c.shape, s)
                   for s in (42, 43)]
     else:
@@ -316,7 +320,7 @@ def _inputs(c: Case):
         return _coast_inputs(c)
     rng_shape = ((c.nb,) if c.nb else ()) + c.shape
     if c.grid in T.VECTOR_GRIDS:
-        gv = T.vector_grid_vars(c.grid, c.shape)
+        gv = T.vector_grid_vars_irregular(c.grid, c.shape) if c.metrics == "irregular" else T.vector_grid_vars(c.grid, c.shape)
         fields = [np.stack([T.random_field(c.shape, s + 2 * l) for l in range(c.nb)]) if c.nb else T.random_field(c.shape, s)
                   for s in (42, 43)]
     else:

@@ -57,6 +57,7 @@ class SeamCase:
     dt: str                              # f8 | f4
     ev: str                              # SlabFilter(evaluation=...): auto | reference | backward
     coast: str                           # testing.coastline name ("name:kappa": with testing.kappa_with_zeros; C-grid "name:indq"); "" = a kind without a mask
+                                         # a vector kind with a last variant ":irr" ("name:indq:irr", B-grid ":irr"): testing.vector_grid_vars_irregular
     roll: Union[int, str]                # rows the planes and the field are rolled by; "kappa0" / "kappa-1": the all-zero row of kappa_s -> row 0 / row ny-1
     halo: Union[int, str]                # an int, or relative to the backward cut of THIS plan: "cut-1", "cut", "cut+1", "2cut-1", "2cut"; "n" = n_steps
     kernel: str                          # regex sf.engine.plan.last_kernel() must match
@@ -141,6 +142,17 @@ def _every_kind():
     for dt, ev, nb, halo in (("f8", "auto", 2, 3), ("f8", "auto", 2, 4), ("f4", "backward", 3, 4), ("f4", "auto", 3, 4)):
         back = halo >= 4 and (dt, ev) != ("f4", "auto")
         add(SeamCase(f"kind-VECTOR_B_GRID-{dt}-{ev}-nb{nb}-h{halo}", "VECTOR_B_GRID", dt, ev, "", -6, halo,
+                     _kernel("VECTOR_B_GRID", dt, ev if back else "reference", halo), shape=(96, 128), nb=nb, land_values="finite",
+                     expect=_t(vec_backward=1 if back else 0), scheme="bgrid_backward" if (back and dt == "f4") else "forward"))
+    # the same drivers cutting and rolling metric planes that differ from one another and vary along x (testing.vector_grid_vars_irregular):
+    # on the spherical fixture a ghost row of a coefficient plane read one column off, or one plane sent for another, is the same number
+    for dt, nb, halo in (("f4", 4, 3), ("f4", 4, 4), ("f8", 3, 4)):
+        add(SeamCase(f"kind-VECTOR_C_GRID-{dt}-nb{nb}-h{halo}-speckle:indq:irr", "VECTOR_C_GRID", dt, "auto", "speckle:indq:irr", 0, halo,
+                     _kernel("VECTOR_C_GRID", dt, "auto", halo), shape=(96, 128), nb=nb, land_values="finite",
+                     expect=_t(vec_backward=1 if halo >= 4 else 0), scheme="cgrid_backward" if (dt == "f4" and halo >= 4) else "forward"))
+    for dt, ev, nb, halo in (("f8", "auto", 2, 3), ("f8", "auto", 2, 4), ("f4", "backward", 3, 4), ("f4", "auto", 3, 4)):
+        back = halo >= 4 and (dt, ev) != ("f4", "auto")
+        add(SeamCase(f"kind-VECTOR_B_GRID-{dt}-{ev}-nb{nb}-h{halo}-irr", "VECTOR_B_GRID", dt, ev, ":irr", -6, halo,
                      _kernel("VECTOR_B_GRID", dt, ev if back else "reference", halo), shape=(96, 128), nb=nb, land_values="finite",
                      expect=_t(vec_backward=1 if back else 0), scheme="bgrid_backward" if (back and dt == "f4") else "forward"))
 
@@ -256,7 +268,11 @@ _kernel_forms()
 def grid_and_roll(c: SeamCase):
     """The UNROLLED grid variables (f64) of a case and its roll as a number of rows."""
     name, _, variant = c.coast.partition(":")
-    if c.grid == "VECTOR_C_GRID":
+    irregular = variant.split(":")[-1] == "irr"      # "name:irr", "name:indq:irr"; the B-grid, which has no mask: ":irr"
+    variant = variant.split(":")[0]
+    if irregular:
+        gv = T.vector_grid_vars_irregular(c.grid, c.shape, coast=name, independent_q=variant == "indq", coast_seed=SEED)
+    elif c.grid == "VECTOR_C_GRID":
         gv = T.cgrid_coast_vars(name, c.shape, SEED, independent_q=variant == "indq")
     elif c.vec:
         gv = dict(T.vector_grid_vars(c.grid, c.shape))

@@ -154,6 +154,26 @@ def test_oracle_grid_variables_with_leading_dims(grid):
     assert np.array_equal(got, want_f)
 
 
+@pytest.mark.parametrize("name", MG.vector_metrics_case_names())
+def test_oracle_on_irregular_vector_metrics(name):
+    """Both vector kinds on testing.vector_grid_vars_irregular -- every metric plane different and varying along x and y, the B-grid's
+    coupling weights dmc, dme, dmw non-zero, which no other fixture of the oracle offers: fp64, bit-equal to the imported reference
+    (make_golden.py --vector-metrics), as test_oracle_matches_imported_reference holds the generated cases."""
+    import os
+    with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", MG.VECTOR_METRICS_FILE)) as z:
+        want = z[name]
+    grid, fields, gv, fk = MG.build_vector_metrics_case(name)
+    with np.errstate(divide="ignore"):
+        if fk is None:
+            res = _stack(O.make_laplacian(grid, gv)(*fields))
+        else:
+            spec = O.make_spec(fk["filter_scale"], fk["dx_min"], fk["filter_shape"])
+            res = np.stack(O.filter_func_vec(spec, grid, *fields, gv))
+    assert res.dtype == want.dtype and res.shape == want.shape
+    assert np.array_equal(res, want, equal_nan=True)
+    assert np.isfinite(res).all() and np.abs(res).max() > 0
+
+
 @pytest.mark.parametrize("name", MG.coast_case_names())
 def test_oracle_on_coastlines_the_fixture_never_draws(name):
     """Speckled, checkerboard, channel, lake, open-south, one-cell, all-land, on-the-cuts and land-on-the-fold masks (testing.COASTLINES)

@@ -23,7 +23,7 @@ def test_roll_rows_moves_row_minus_r_onto_row_zero():
 
 def test_every_row_has_on_its_seam_what_it_claims():
     for c in CASES:
-        if not c.coast:
+        if not c.coast.partition(":")[0]:      # no coastline ("", or the B-grid's ":irr": irregular metrics, still no mask)
             assert c.live and not c.closed_in and c.grid in ("REGULAR", "REGULAR_AREA_WEIGHTED", "VECTOR_B_GRID"), c.id
             continue
         if c.grid == "VECTOR_C_GRID":
