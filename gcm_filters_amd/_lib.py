@@ -52,6 +52,8 @@ EXPORTS_BANK = ["gcmf_apply_bank", "gcmf_bank_cut"]
 EXPORTS_BANK_GAPS = ["gcmf_apply_bank_gaps"]
 # ... and of the adjoint application (gcmf_apply_adjoint): likewise
 EXPORTS_ADJOINT = ["gcmf_apply_adjoint"]
+# ... and of the filter followed by weighted block means (gcmf_apply_coarsen): likewise
+EXPORTS_COARSEN = ["gcmf_coarsen_weights", "gcmf_apply_coarsen"]
 PATH_NAMES = {0: None, 1: "resident", 2: "strips", 3: "resident-lock-busy", 4: "resident-disabled"}
 RESIDENT_STATES = {0: "ok", 1: "lock-busy", 2: "disabled", 3: "off"}
 PLAN_SELF_RING, PLAN_SKIP_KAPPA_ONE = 0x1, 0x2
@@ -131,6 +133,10 @@ def load() -> C.CDLL:
         lib.gcmf_apply.restype = C.c_int
         lib.gcmf_apply_adjoint.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_double, vpp, vpp, vpp, C.c_int64, C.c_uint32, vp]
         lib.gcmf_apply_adjoint.restype = C.c_int
+        lib.gcmf_coarsen_weights.argtypes = [vp, vp, C.c_int64, C.c_uint32]
+        lib.gcmf_coarsen_weights.restype = C.c_int
+        lib.gcmf_apply_coarsen.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_double, vpp, vpp, vpp, C.c_int64, C.c_int, C.c_int, C.c_uint32, vp]
+        lib.gcmf_apply_coarsen.restype = C.c_int
         lib.gcmf_apply_bank.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double, vp, vp, C.c_int64, C.c_uint32, vp]
         lib.gcmf_apply_bank.restype = C.c_int
         lib.gcmf_apply_bank_gaps.argtypes = lib.gcmf_apply_bank.argtypes
@@ -392,6 +398,36 @@ class Plan:
                                         None if likes is None else _ptr_array(likes), _ptr_array(outs), int(nbatch), bits,
                                         C.c_void_p(stream or None)))
 
+    def set_coarsen_weights(self, weights, nlev: int = 1, *, device_ptrs: bool = False):
+        """The weight planes of this plan's later apply_coarsen calls (gcmf_coarsen_weights): `nlev` float64 planes of (ny, nx), copied
+        into HBM the plan owns; entry b of a call uses level b % nlev.  weights: None (every cell has weight 1, as on a new plan), a
+        host array of nlev * ny * nx values, or with device_ptrs a device pointer to as many.  Waits for the device: set the weights
+        once per weights array, not once per call."""
+        if weights is None:
+            check(load().gcmf_coarsen_weights(self._h, None, 0, 0))
+            return
+        nlev = int(nlev)
+        if device_ptrs:
+            check(load().gcmf_coarsen_weights(self._h, C.c_void_p(int(weights)), nlev, DEVICE_PTRS))
+            return
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+        if nlev >= 1 and w.size != nlev * self.ny * self.nx:      # (nlev < 1: the library refuses it)
+            raise ValueError(f"coarsen weights have {w.size} values, expected {nlev} planes of {(self.ny, self.nx)}")
+        check(load().gcmf_coarsen_weights(self._h, C.c_void_p(w.ctypes.data), nlev, 0))
+
+    def apply_coarsen(self, p: np.ndarray, c: float, ins: Sequence[int], outs: Sequence[int], nbatch: int, fy: int, fx: int, *,
+                      wsums: Optional[Sequence[int]] = None, device_ptrs: bool, stream: int = 0, forward: bool = False,
+                      backward_f32: bool = False, mask_from_nan: bool = False, faces_from_nan: bool = False, flags: int = 0):
+        """apply() followed by weighted block means of its result (gcmf_apply_coarsen): outs[0] receives nbatch float64 planes of
+        (ny / fy, nx / fx), wsums[0] (None: not wanted) the sums of the counted weights, by the rule of include/gcmf.h with the weights
+        of set_coarsen_weights.  ins, outs and wsums are all host or all device pointers.  Vector plans, row slabs, self-ring plans
+        and out_f32 raise GcmfError(ERR_UNSUPPORTED).  flags: further GCMF_* bits (GCMF_NO_RESIDENT)."""
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        bits = apply_flags(device_ptrs, False, forward, backward_f32, mask_from_nan, faces_from_nan) | int(flags)
+        check(load().gcmf_apply_coarsen(self._h, p.ctypes.data_as(C.POINTER(C.c_double)), len(p) - 1, float(c), _ptr_array(ins),
+                                        _ptr_array(outs), None if wsums is None else _ptr_array(wsums), int(nbatch), int(fy), int(fx), bits,
+                                        C.c_void_p(stream or None)))
+
     def apply_bank(self, p: np.ndarray, c: float, src: int, out: int, nfield: int, *, device_ptrs: bool = True, stream: int = 0,
                    flags: int = 0, faces_from_nan: bool = False):
         """A filter bank (gcmf_apply_bank): the rows of `p`, (nbank, n_steps + 1), are polynomials of one degree; out[j, i] = row j
@@ -594,7 +630,8 @@ class Plan:
         state planes non-temporally so that the constant planes stay in the memory-side cache: 1 (default) where the table's owned cells x
         65 bytes exceed 256 MiB, 2 whenever such a launch runs, 0 never; same bits), "gap_scratch_mb" (apply(faces_from_nan=True): the most scratch, in MiB, the
         per-entry planes of one launch may take; default 4096, longer batches run as consecutive launches), "adjoint_scratch_mb" (apply_adjoint:
-        the same bound for its pre-scaled planes, one per component and entry)."""
+        the same bound for its pre-scaled planes, one per component and entry), "coarsen_scratch_mb" (apply_coarsen: the same bound for the
+        fine planes of one run of entries)."""
         check(load().gcmf_set_option(self._h, name.encode(), int(value)))
 
 

@@ -288,6 +288,8 @@ void gcmf_plan_destroy(gcmf_plan *pl) {
   if (pl->dev_p) (void)hipFree(pl->dev_p);
   if (pl->bank_rev) (void)hipFree(pl->bank_rev);
   if (pl->bank_fwd) (void)hipFree(pl->bank_fwd);
+  if (pl->coarsen_w) (void)hipFree(pl->coarsen_w);
+  if (pl->coarsen_buf) (void)hipFree(pl->coarsen_buf);
   resident_free(pl);
   if (pl->stream) (void)hipStreamDestroy(pl->stream);
   delete pl;

@@ -197,7 +197,17 @@ struct gcmf_plan {
   // in the work buffer behind everything else; longer batches are cut so that it stays at or under "adjoint_scratch_mb".
   const void *adj_area[2] = {nullptr, nullptr};
   int adjoint_scratch_mb = 4096;   // gcmf_set_option "adjoint_scratch_mb"
-  int zero_land = 1;     // env GCMF_ZERO_LAND=0 turns it off
+  // gcmf_apply_coarsen (gcmf_coarsen.hip): the weight planes gcmf_coarsen_weights copied ((coarsen_nlev, ny, nx) f64; nullptr: every
+  // weight is 1) and the call's own work buffer -- the fine planes of one run of entries, at or under "coarsen_scratch_mb", and with host
+  // pointers the staged input and coarse planes (grow-only).  coarsen_mu is held for a whole call, OUTSIDE mu, which the gcmf_apply
+  // inside takes run by run.
+  void *coarsen_w = nullptr;
+  int64_t coarsen_nlev = 0;
+  void *coarsen_buf = nullptr;
+  size_t coarsen_bytes = 0;
+  int coarsen_scratch_mb = 4096;   // gcmf_set_option "coarsen_scratch_mb"
+  std::mutex coarsen_mu;
+  int zero_land = 1;    // env GCMF_ZERO_LAND=0 turns it off
   int ring = 1;           // env GCMF_RING=0: deep launches stay with k_flux_multi2 / k_scalar_multi
   unsigned *ring_nfb = nullptr;    // device counter behind gcmf_ring_fallbacks (lives behind zero_row)
   const void *zero_row = nullptr;  // nx zeros: what rows beyond a closed boundary read as coefficients / mask bits (k_ring)

@@ -675,6 +675,55 @@ class Filter:
         u_filtered, v_filtered = self._through_apply_ufunc(filter_func_vec, [ufield, vfield], dims)
         return (u_filtered, v_filtered)
 
+    # -- filter, then coarse-grain (not in the reference) --------------------------------------------
+    def apply_coarsened(self, field, factor, dims=None, weights=None, return_weights=False):
+        """``apply``, then one weighted mean per block of ``factor`` cells -- "smooth the 0.1 degree field to 1 degree, then keep one value
+        per 1 degree box" in one call (``gcmf_apply_coarsen``): the fine result never leaves the device, and a numpy caller gets back
+        only the coarse planes.
+
+        ``factor``: an int, or ``(fy, fx)``; each must divide its grid length (``ValueError`` gives both lengths).  ``field``: numpy, a
+        torch tensor (host or MI355X-resident) or a DLPack / ``__cuda_array_interface__`` array, filtered over its last two axes with
+        any leading dims; the same kind comes back, of shape ``lead + (ny / fy, nx / fx)`` and dtype float64.  ``dims`` is accepted for
+        symmetry with ``apply`` and not used.
+
+        The rule (``gcm_filters_amd.coarsen``): a cell counts where its weight is > 0 and the filtered value is not NaN (+-inf is data);
+        a block's value is the sum of ``weight * value`` over its counted cells over the sum of their weights -- NaN where no cell
+        counts.  Cells that do not count are skipped, never multiplied, so neither the finite junk ``apply`` leaves on land nor the gaps
+        of a ``nan_mask`` filter reach a mean.  The sums run in float64 in one fixed order: the bits of a block do not depend on the
+        batch, on where the arrays lie or on whether they are host or device arrays.
+
+        ``weights``: ``None`` -- the grid's own: 1 (``REGULAR``), ``wet_mask`` (``REGULAR_WITH_LAND``), ``area``
+        (``REGULAR_AREA_WEIGHTED``), and the cell area times ``wet_mask`` on the other scalar grid types (``area``, ``area_u``,
+        ``area_t``, ``tarea``), with the level axis of grid variables that have leading dims --, or one plane (y, x), or planes with
+        the grid variables' leading dims; negative or NaN entries raise ``ValueError``.  The weights go to the device once per
+        weights array (and plan), not once per call: to change them pass another array, not the same one edited in place.
+        ``return_weights=True`` returns ``(coarse, wsum)``, ``wsum`` being the blocks' sums of counted weights (0 where ``coarse`` is NaN).
+
+        ``evaluation``, ``plan_cache`` and ``nan_mask`` carry over from the Filter.  ``NotImplementedError``: xarray objects (the core
+        dims shrink: pass ``.data`` and re-wrap the result), tensors that require grad (``detach()`` them, or coarsen ``apply``'s
+        result with torch to keep the gradient), and vector grid types."""
+        if issubclass(self.Laplacian, BaseVectorLaplacian):
+            raise NotImplementedError(f"{self.grid_type.name} is a vector grid type: apply_coarsened coarsens scalar fields only; filter "
+                                      f"with apply_to_vector and coarsen each component on the scalar grid of its points")
+        if hasattr(field, "dims") and not _is_torch(field) and not isinstance(field, np.ndarray):
+            raise NotImplementedError("apply_coarsened does not take xarray objects (the core dims of the result are shorter than the "
+                                      "input's): pass the array itself, `field.data`, with (y, x) as its last two axes, and wrap the result")
+        if _wants_grad(field):
+            raise NotImplementedError("apply_coarsened has no backward: pass `field.detach()` to coarsen without a gradient, or call "
+                                      "apply() -- which is differentiable -- and take the block means with torch")
+        from . import coarsen
+        if not _is_bare_array(field):
+            field = np.asarray(field)
+        hit = self.__dict__.get("_coarsen_memo")
+        if hit is None:
+            hit = self.__dict__["_coarsen_memo"] = _LaplacianMemo(self.Laplacian)
+        faces = self.nan_mask == "auto" and self.grid_type in GAP_FOLD_GRID_TYPES
+        opts = CallOptions(spec=self.filter_spec, forward=_forward_only(self.evaluation), backward_f32=self.evaluation == "backward",
+                           mask_from_nan=bool(self.nan_mask) and not faces, faces_from_nan=faces)
+        out = coarsen.apply_coarsened(self, hit, opts, field, factor, weights, return_weights)
+        self._operator(_create_filter_func).last_path = kernels_last_path()
+        return out
+
     # -- the adjoint (not in the reference) --------------------------------------------------------
     def adjoint(self, field, dims=None, like=None):
         """Apply the TRANSPOSE of ``apply`` to ``field`` (a gradient with respect to the filtered field, say): ``F^T field``, where

@@ -287,6 +287,51 @@ extern int gcmf_apply_adjoint(gcmf_plan *plan, const double *p, int n_steps, dou
                               void *const *out, int64_t nbatch, uint32_t flags, void *stream);
 
 /*
+ * FILTER, THEN COARSE-GRAIN: gcmf_apply followed by weighted block means of its result, so that less than a full-resolution plane comes
+ * back -- over PCIe, with host pointers, only the coarse planes.  (The reference has no counterpart: its users coarsen the fine result.)
+ * THE RULE (csrc/gcmf_coarsen.hpp, which also holds a plain C++ restatement, coarsen_plane).  For factors (fy, fx) that divide (ny, nx),
+ * the fine result F of one batch entry and its weight plane w, block (J, I) = rows [J fy, (J + 1) fy) x columns [I fx, (I + 1) fx):
+ *     count(j,i)  = w(j,i) > 0  &&  F(j,i) == F(j,i)
+ *     wsum(J,I)   = sum of w over the counted cells of the block
+ *     coarse(J,I) = sum of w * F over the counted cells / wsum(J,I);   NaN (and wsum = 0) when no cell counts
+ * +-inf in F is data.  A NaN in F (a gap of a flagged call, a NaN the caller put on land), a weight <= 0 and a NaN weight are SKIPPED,
+ * never multiplied (0 * inf is NaN, and the fine result on land is finite junk): weights that are 0 on land keep land out of the means.
+ * Everything is summed in f64 in ONE fixed order -- each fine column of a block from south to north, then the columns from west to east
+ * -- without atomics, so the bits of a coarse cell depend on neither nbatch, the entry's place in the batch, pointer alignment, host or
+ * device pointers, "coarsen_scratch_mb" nor the run.
+ *
+ * gcmf_coarsen_weights: the weight planes of the plan's later gcmf_apply_coarsen calls -- `nlev` >= 1 f64 planes of ny x nx, one after
+ * the other, copied into HBM that the plan owns (freed with the plan, replaced by a later call).  Host planes by default, device planes
+ * with GCMF_DEVICE_PTRS (the only flag taken; the copy is complete on return).  Entry b of a call uses level b % nlev, for any nlev >= 1,
+ * whatever the plan's own levels.  w == NULL drops the weights: every cell has weight 1, the state of a new plan.  Takes the plan's
+ * mutex and waits for the device: set the weights once per weights array, not once per call.
+ *
+ * gcmf_apply_coarsen: `plan`, `p`, `n_steps`, `c`, `in`, `nbatch`, `stream` and the flags GCMF_DEVICE_PTRS, GCMF_FORWARD_RECURRENCE,
+ * GCMF_BACKWARD_F32, GCMF_MASK_FROM_NAN, GCMF_FACES_FROM_NAN (and GCMF_NO_RESIDENT) are gcmf_apply's and are handed to it: the gaps of a
+ * flagged call are NaN in F and drop out of the means by the rule.  out[0]: nbatch planes of (ny / fy) x (nx / fx) f64, whatever the
+ * plan dtype.  `wsum`: NULL, or wsum[0] of the same shape receives the sums of the counted weights.  `in`, `out` and `wsum` are all host
+ * pointers, or all device pointers with GCMF_DEVICE_PTRS (then everything is enqueued on `stream`, as for gcmf_apply; the planes may
+ * start at any element boundary).
+ * How it runs: the schedule gcmf_apply takes for the plan and the flags (on-chip or strips, k_land_fix included) writes the fine f64
+ * planes into a work buffer of the plan's, and ONE streaming launch behind it on the same stream -- a further form of k_prepare
+ * (csrc/gcmf_coarsen.hip), the name of the plane passes before and after a schedule -- reads the fine plane and the weight plane once,
+ * 16 bytes per load where nx is even and the planes lie on 16-byte boundaries and element by element otherwise, and writes the coarse
+ * plane (and wsum).  gcmf_last_kernel, gcmf_last_kernel_geometry and gcmf_plan_last_path answer for the schedule; gcmf_last_timing
+ * counts the pass as one launch more (its time covers the schedule).
+ * Scratch: the fine planes of a run of entries (grow-only, freed by gcmf_plan_destroy); option "coarsen_scratch_mb" (default 4096) bounds
+ * them: a longer batch is cut into consecutive runs of at least one entry each (a stacked plan's: of whole sets of levels).  With host
+ * pointers a run's input and coarse planes are staged beside them, one run at a time, without gcmf_apply's chunk pipeline; the call is
+ * synchronous.  Stacked plans (gcmf_plan_create_levels): entry b takes level b % nlev of the plan and of the weights, each with its own nlev.
+ * GCMF_ERR_INVALID_ARG, naming the argument, nothing written: fy < 1, fx < 1 or a factor that does not divide its length; a null `in`
+ * or `out` (or wsum[0]); `out` or `wsum` overlapping `in` or each other as byte ranges; a stacked plan's nbatch that is no multiple of
+ * its levels.  GCMF_ERR_UNSUPPORTED, naming the function and the limit: vector plans (ncomp == 2), row slabs, GCMF_PLAN_SELF_RING,
+ * GCMF_OUT_F32 (the coarse planes are always f64); and whatever gcmf_apply refuses for these flags.  nbatch == 0: GCMF_OK.
+ */
+extern int gcmf_coarsen_weights(gcmf_plan *plan, const void *w, int64_t nlev, uint32_t flags);
+extern int gcmf_apply_coarsen(gcmf_plan *plan, const double *p, int n_steps, double c, const void *const *in, void *const *out,
+                              void *const *wsum, int64_t nbatch, int fy, int fx, uint32_t flags, void *stream);
+
+/*
  * A FILTER BANK: nbank polynomials of ONE degree applied to the same nfield fields in one call -- a sweep over filter scales, whose
  * polynomials share n_steps, c and the grid (s_max does not depend on the filter scale) and differ in p alone:
  *     out[j * nfield + i] = the polynomial p[j * (n_steps + 1) .. (j + 1) * (n_steps + 1)) applied to in[i]      (j < nbank, i < nfield)
@@ -602,7 +647,9 @@ int gcmf_set_tuning(gcmf_plan *plan, int rows_per_wave, int xcd_remap, int multi
  * "gap_scratch_mb" N (GCMF_FACES_FROM_NAN: the most scratch, in MiB, the per-entry planes of one launch may take; default 4096; a batch
  * whose planes need more is cut into consecutive launches of at least one entry; same bits; gcmf_apply_bank_gaps: per field, not per
  * entry, and the FIELDS are cut into runs), "adjoint_scratch_mb" N (gcmf_apply_adjoint: the most scratch, in MiB, the pre-scaled planes
- * of one launch may take; default 4096; a longer batch is cut into consecutive launches of at least one entry; same bits).  Unknown
+ * of one launch may take; default 4096; a longer batch is cut into consecutive launches of at least one entry; same bits),
+ * "coarsen_scratch_mb" N (gcmf_apply_coarsen: the most scratch, in MiB, the fine planes of one run of entries may take; default 4096; a
+ * longer batch is cut into consecutive runs of at least one entry; same bits).  Unknown
  * names: GCMF_ERR_INVALID_ARG. */
 int gcmf_set_option(gcmf_plan *plan, const char *name, int value);
 
