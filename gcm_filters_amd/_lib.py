@@ -54,6 +54,8 @@ EXPORTS_BANK_GAPS = ["gcmf_apply_bank_gaps"]
 EXPORTS_ADJOINT = ["gcmf_apply_adjoint"]
 # ... and of the filter followed by weighted block means (gcmf_apply_coarsen): likewise
 EXPORTS_COARSEN = ["gcmf_coarsen_weights", "gcmf_apply_coarsen"]
+# ... and of the subfilter covariances (gcmf_apply_cov): likewise
+EXPORTS_COV = ["gcmf_apply_cov"]
 PATH_NAMES = {0: None, 1: "resident", 2: "strips", 3: "resident-lock-busy", 4: "resident-disabled"}
 RESIDENT_STATES = {0: "ok", 1: "lock-busy", 2: "disabled", 3: "off"}
 PLAN_SELF_RING, PLAN_SKIP_KAPPA_ONE = 0x1, 0x2
@@ -137,6 +139,8 @@ def load() -> C.CDLL:
         lib.gcmf_coarsen_weights.restype = C.c_int
         lib.gcmf_apply_coarsen.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_double, vpp, vpp, vpp, C.c_int64, C.c_int, C.c_int, C.c_uint32, vp]
         lib.gcmf_apply_coarsen.restype = C.c_int
+        lib.gcmf_apply_cov.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_double, vp, vp, vp, C.c_int64, C.c_uint32, vp]
+        lib.gcmf_apply_cov.restype = C.c_int
         lib.gcmf_apply_bank.argtypes = [vp, C.POINTER(C.c_double), C.c_int, C.c_int, C.c_double, vp, vp, C.c_int64, C.c_uint32, vp]
         lib.gcmf_apply_bank.restype = C.c_int
         lib.gcmf_apply_bank_gaps.argtypes = lib.gcmf_apply_bank.argtypes
@@ -428,6 +432,18 @@ class Plan:
                                         _ptr_array(outs), None if wsums is None else _ptr_array(wsums), int(nbatch), int(fy), int(fx), bits,
                                         C.c_void_p(stream or None)))
 
+    def apply_cov(self, p: np.ndarray, c: float, f: int, g: Optional[int], out: int, npair: int, *, device_ptrs: bool, stream: int = 0,
+                  forward: bool = False, mask_from_nan: bool = False, faces_from_nan: bool = False, flags: int = 0):
+        """Subfilter covariances (gcmf_apply_cov): out = F(f g) - F(f) F(g) for npair pairs of float64 planes of (ny, nx), the three
+        entries of every pair filtered as one batch between two streaming passes.  f, g, out: all host or all device pointers to
+        npair planes each; g None (or g == f): the variance, two entries per pair.  mask_from_nan / faces_from_nan are apply()'s and
+        also give all three entries of a pair the common gaps isnan(f) | isnan(g).  Vector plans, float32 plans, row slabs and
+        self-ring plans raise GcmfError(ERR_UNSUPPORTED).  flags: further GCMF_* bits (GCMF_NO_RESIDENT)."""
+        p = np.ascontiguousarray(p, dtype=np.float64)
+        bits = apply_flags(device_ptrs, False, forward, False, mask_from_nan, faces_from_nan) | int(flags)
+        check(load().gcmf_apply_cov(self._h, p.ctypes.data_as(C.POINTER(C.c_double)), len(p) - 1, float(c), C.c_void_p(f or None),
+                                    C.c_void_p(g or None), C.c_void_p(out or None), int(npair), bits, C.c_void_p(stream or None)))
+
     def apply_bank(self, p: np.ndarray, c: float, src: int, out: int, nfield: int, *, device_ptrs: bool = True, stream: int = 0,
                    flags: int = 0, faces_from_nan: bool = False):
         """A filter bank (gcmf_apply_bank): the rows of `p`, (nbank, n_steps + 1), are polynomials of one degree; out[j, i] = row j
@@ -631,7 +647,8 @@ class Plan:
         65 bytes exceed 256 MiB, 2 whenever such a launch runs, 0 never; same bits), "gap_scratch_mb" (apply(faces_from_nan=True): the most scratch, in MiB, the
         per-entry planes of one launch may take; default 4096, longer batches run as consecutive launches), "adjoint_scratch_mb" (apply_adjoint:
         the same bound for its pre-scaled planes, one per component and entry), "coarsen_scratch_mb" (apply_coarsen: the same bound for the
-        fine planes of one run of entries)."""
+        fine planes of one run of entries), "cov_scratch_mb" (apply_cov: the same bound for the six planes per pair -- four for a variance
+        -- of one run of pairs)."""
         check(load().gcmf_set_option(self._h, name.encode(), int(value)))
 
 

@@ -290,6 +290,7 @@ void gcmf_plan_destroy(gcmf_plan *pl) {
   if (pl->bank_fwd) (void)hipFree(pl->bank_fwd);
   if (pl->coarsen_w) (void)hipFree(pl->coarsen_w);
   if (pl->coarsen_buf) (void)hipFree(pl->coarsen_buf);
+  if (pl->cov_buf) (void)hipFree(pl->cov_buf);
   resident_free(pl);
   if (pl->stream) (void)hipStreamDestroy(pl->stream);
   delete pl;

@@ -145,6 +145,7 @@ int gcmf_set_option(gcmf_plan *pl, const char *name, int value) {
   else if (n == "gap_scratch_mb") pl->gap_scratch_mb = value;
   else if (n == "adjoint_scratch_mb") pl->adjoint_scratch_mb = value;
   else if (n == "coarsen_scratch_mb") pl->coarsen_scratch_mb = value;
+  else if (n == "cov_scratch_mb") pl->cov_scratch_mb = value;
   else {
     set_error("gcmf_set_option: unknown option '%s'", name);
     return GCMF_ERR_INVALID_ARG;

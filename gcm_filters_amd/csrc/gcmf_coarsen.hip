@@ -158,28 +158,6 @@ static int launch_coarsen(const gcmf_plan *pl, const double *fine, double *coars
   return GCMF_OK;
 }
 
-static size_t up256(size_t x) { return (x + 255) / 256 * 256; }
-
-static bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
-  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
-  return na && nb && a0 < b0 + nb && b0 < a0 + na;
-}
-
-// The call's scratch is the plan's, shared by all calls like the work buffers of gcmf_apply: a call on ANOTHER stream than the plan's
-// last one orders itself behind it before it touches the scratch (gcmf_apply does the same for its own buffers, gcmf_api.hip).
-static int order_behind_last_call(gcmf_plan *pl, hipStream_t s) {
-  std::lock_guard<std::mutex> lk(pl->mu);
-  if (pl->busy_valid && pl->busy_stream != s) {
-    if (pl->busy_recorded || hipEventRecord(pl->ev_busy, pl->busy_stream) == hipSuccess) {
-      GCMF_HIP(hipStreamWaitEvent(s, pl->ev_busy, 0));
-    } else {
-      (void)hipGetLastError();
-      GCMF_HIP(hipDeviceSynchronize());
-    }
-  }
-  return GCMF_OK;
-}
-
 }  // namespace gcmf
 
 using namespace gcmf;

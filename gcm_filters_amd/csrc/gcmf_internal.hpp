@@ -207,6 +207,13 @@ struct gcmf_plan {
   size_t coarsen_bytes = 0;
   int coarsen_scratch_mb = 4096;   // gcmf_set_option "coarsen_scratch_mb"
   std::mutex coarsen_mu;
+  // gcmf_apply_cov (gcmf_cov.hip): the call's own work buffer -- per pair of a run the three planes the pre pass writes (f', g', f' g';
+  // two for a variance) and their three filtered planes, at or under "cov_scratch_mb" (grow-only).  cov_mu is held for a whole call,
+  // OUTSIDE mu, like coarsen_mu.
+  void *cov_buf = nullptr;
+  size_t cov_bytes = 0;
+  int cov_scratch_mb = 4096;   // gcmf_set_option "cov_scratch_mb"
+  std::mutex cov_mu;
   int zero_land = 1;    // env GCMF_ZERO_LAND=0 turns it off
   int ring = 1;           // env GCMF_RING=0: deep launches stay with k_flux_multi2 / k_scalar_multi
   unsigned *ring_nfb = nullptr;    // device counter behind gcmf_ring_fallbacks (lives behind zero_row)
@@ -431,4 +438,27 @@ int launch_field_masks(gcmf_plan *pl, const uint8_t *wet, const void *fields, ui
 // planes (cE, cN, ra) and the entries' NaNs (k_pre_isolated<double, true, MOM5>, gcmf_gap_fold.hpp); nx must be a multiple of 4
 int launch_gap_fold(gcmf_plan *pl, const double *cE, const double *cN, const double *ra, const void *fields, double *cEo, double *cNo,
                     double *rao, uint8_t *bits, int64_t nbatch, hipStream_t s);
+// helpers of the calls that wrap gcmf_apply between passes of their own (gcmf_coarsen.hip, gcmf_cov.hip)
+inline size_t up256(size_t x) { return (x + 255) / 256 * 256; }
+
+inline bool ranges_overlap(const void *a, size_t na, const void *b, size_t nb) {
+  const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;
+  return na && nb && a0 < b0 + nb && b0 < a0 + na;
+}
+
+// Such a call's scratch is the plan's, shared by all calls like the work buffers of gcmf_apply: a call on ANOTHER stream than the plan's
+// last one orders itself behind it before it touches the scratch (gcmf_apply does the same for its own buffers, gcmf_api.hip).
+inline int order_behind_last_call(gcmf_plan *pl, hipStream_t s) {
+  std::lock_guard<std::mutex> lk(pl->mu);
+  if (pl->busy_valid && pl->busy_stream != s) {
+    if (pl->busy_recorded || hipEventRecord(pl->ev_busy, pl->busy_stream) == hipSuccess) {
+      GCMF_HIP(hipStreamWaitEvent(s, pl->ev_busy, 0));
+    } else {
+      (void)hipGetLastError();
+      GCMF_HIP(hipDeviceSynchronize());
+    }
+  }
+  return GCMF_OK;
+}
+
 }  // namespace gcmf

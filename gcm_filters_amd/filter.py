@@ -493,6 +493,11 @@ class Filter:
         built here and run as grid variables with a leading axis: the same contract, slower.  ``ValueError`` on the other five grid
         types, and for any other string.
 
+    Beyond ``apply`` and ``apply_to_vector`` (none of these is in the reference class): ``adjoint``, ``apply_coarsened`` (filter, then
+    weighted block means) and ``apply_covariance(field, other=None)`` -- the subfilter covariance ``F(f g) - F(f) F(g)`` of two scalar
+    fields (``other=None``: the variance) in one call, float64, bit for bit the composition of three ``apply`` calls, with the gaps of
+    a ``nan_mask`` filter taken from both fields together.
+
     Attributes
     ----------
     filter_spec: FilterSpec
@@ -721,6 +726,53 @@ class Filter:
         opts = CallOptions(spec=self.filter_spec, forward=_forward_only(self.evaluation), backward_f32=self.evaluation == "backward",
                            mask_from_nan=bool(self.nan_mask) and not faces, faces_from_nan=faces)
         out = coarsen.apply_coarsened(self, hit, opts, field, factor, weights, return_weights)
+        self._operator(_create_filter_func).last_path = kernels_last_path()
+        return out
+
+    # -- subfilter covariances (not in the reference) ------------------------------------------------
+    def apply_covariance(self, field, other=None, dims=None):
+        """The subfilter (eddy) covariance ``tau(f, g) = F(f g) - F(f) F(g)`` of ``field`` and ``other`` in one call
+        (``gcmf_apply_cov``); ``other=None`` is the subfilter variance ``F(f f) - F(f) F(f)``.  Eddy kinetic energy is
+        ``(tau(u, u) + tau(v, v)) / 2``; eddy fluxes and subgrid forcings are covariances, too.
+
+        ``field``, ``other``: numpy, torch tensors (host or MI355X-resident) or DLPack / ``__cuda_array_interface__`` arrays of one
+        shape, filtered over their last two axes with any leading dims; the kind of ``field`` comes back, float64, of the shape
+        ``apply`` would return.  ``dims`` is accepted for symmetry with ``apply`` and not used.
+
+        The three applications of every pair run as one batch on the device between two streaming passes, and the result equals, bit
+        for bit, ``apply(f * g) - apply(f) * apply(g)`` computed in float64 (``gcm_filters_amd.covariance.composition``).  With
+        ``nan_mask`` all three share the gaps ``isnan(field) | isnan(other)``: the result is NaN exactly where either field is, and
+        it is the composition on the two fields with those common gaps put in -- three masks from three sets of NaNs would not give a
+        covariance.  ``evaluation``, ``plan_cache`` and ``nan_mask`` carry over from the Filter.
+
+        ``ValueError``: the two differ in shape, or have fewer than two dims.  ``NotImplementedError``: xarray objects (pass
+        ``.data`` and re-wrap the result), tensors that require grad (``detach()`` them, or compose the covariance from ``apply``,
+        which is differentiable), vector grid types (take the covariance of each component on the scalar grid of its points), and a
+        float32 compute dtype -- float32 fields with float32 grid variables: cast to float64, tau being a small difference of large
+        numbers."""
+        if issubclass(self.Laplacian, BaseVectorLaplacian):
+            raise NotImplementedError(f"{self.grid_type.name} is a vector grid type: apply_covariance takes scalar fields only; take the "
+                                      f"covariance of each component on the scalar grid type of its points")
+        for a in (field, other):
+            if hasattr(a, "dims") and not _is_torch(a) and not isinstance(a, np.ndarray):
+                raise NotImplementedError("apply_covariance does not take xarray objects: pass the arrays themselves, `field.data` and "
+                                          "`other.data`, with (y, x) as their last two axes, and wrap the result")
+            if _wants_grad(a):
+                raise NotImplementedError("apply_covariance has no backward: pass `field.detach()` (and `other.detach()`), or compose "
+                                          "apply(f * g) - apply(f) * apply(g) from apply(), which is differentiable")
+        from . import covariance
+        if not _is_bare_array(field):
+            field = np.asarray(field)
+        if other is not None and not _is_bare_array(other):
+            other = np.asarray(other)
+        f, g = covariance.check_pair(self, field, other)
+        hit = self.__dict__.get("_coarsen_memo")
+        if hit is None:
+            hit = self.__dict__["_coarsen_memo"] = _LaplacianMemo(self.Laplacian)
+        faces = self.nan_mask == "auto" and self.grid_type in GAP_FOLD_GRID_TYPES
+        opts = CallOptions(spec=self.filter_spec, forward=_forward_only(self.evaluation), mask_from_nan=bool(self.nan_mask) and not faces,
+                           faces_from_nan=faces)
+        out = covariance.apply_covariance(self, hit, opts, field, f, g)
         self._operator(_create_filter_func).last_path = kernels_last_path()
         return out
 

@@ -332,6 +332,45 @@ extern int gcmf_apply_coarsen(gcmf_plan *plan, const double *p, int n_steps, dou
                               void *const *wsum, int64_t nbatch, int fy, int fx, uint32_t flags, void *stream);
 
 /*
+ * SUBFILTER COVARIANCES: tau(f, g) = F(f g) - F(f) F(g) of `npair` pairs of fields in one call (g = f: the subfilter variance) -- what
+ * eddy kinetic energy, eddy fluxes and subgrid-forcing datasets are made of.  (The reference has no counterpart: its users compose it
+ * from three applications.)
+ * THE RULE (csrc/gcmf_cov.hpp, which also holds a plain C++ restatement, cov_pre_plane and cov_post_plane).  Per cell of a pair, with
+ * `common` = the call carries GCMF_MASK_FROM_NAN or GCMF_FACES_FROM_NAN:
+ *     n  = (f == f) && (g == g)                         +-inf is data
+ *     f' = (common && !n) ? NaN : f,   g' likewise      common gaps: all three entries of a pair see isnan(f) | isnan(g)
+ *     fg = f' * g'                                      one rounding
+ *     out = F(fg) - F(f') * F(g')                       two roundings, no fused multiply-add; NaN in any operand gives NaN
+ * Without `common`, f and g reach the filter bit for bit.  out equals, bit for bit, the composition of three gcmf_apply calls on f' g',
+ * f' and g' and the two roundings above, whatever npair, a pair's place in the call, pointer alignment, host or device pointers and
+ * "cov_scratch_mb": an entry has the same bits alone and inside a batch.
+ *
+ * gcmf_apply_cov: `plan`, `p`, `n_steps`, `c`, `stream` are gcmf_apply's.  `f`, `g`, `out`: npair planes of ny x nx f64 each, one after
+ * the other -- all host pointers, or all device pointers with GCMF_DEVICE_PTRS (then everything is enqueued on `stream`, as for
+ * gcmf_apply; the planes may start at any element boundary).  g == NULL or g == f: the variance, which filters two entries per pair,
+ * not three.  Flags handed to gcmf_apply with its usual checks: GCMF_FORWARD_RECURRENCE, GCMF_MASK_FROM_NAN, GCMF_FACES_FROM_NAN,
+ * GCMF_NO_RESIDENT; the two NaN flags also switch on the common gaps of the rule (the faces of a pair are folded three times, once per
+ * entry).
+ * How it runs: a pre pass writes the batch [f'_0 .. f'_{N-1} | g'_0 .. | fg_0 ..] of a run of N pairs into scratch of the plan's (with
+ * host pointers f and g are uploaded straight into their slots, and the pass only applies the common gaps and writes fg), ONE gcmf_apply
+ * filters the 3 N (variance: 2 N) entries, and a post pass reads the filtered planes and writes out (a device `out` directly).  Both
+ * passes are further forms of k_prepare (csrc/gcmf_cov.hip): 16 bytes per load and store where every plane of the call lies on a
+ * 16-byte boundary and ny * nx is even, element by element otherwise, with the same bits.  gcmf_last_kernel and gcmf_plan_last_path
+ * answer for the schedule; gcmf_last_timing sums the runs, the two passes included (launches of the schedule + 2 per run).
+ * Scratch: 6 planes per pair of a run (4 for a variance), grow-only, freed by gcmf_plan_destroy; option "cov_scratch_mb" (default 4096)
+ * bounds it: a longer call is cut into consecutive runs of at least one pair each, and under GCMF_FACES_FROM_NAN a run's entries are
+ * also kept at or under "gap_scratch_mb".  Stacked plans (gcmf_plan_create_levels): pair i runs on level i % nlev -- entry k N + i of a
+ * run's batch is level i % nlev, because a run is whole sets of levels.  With host pointers the call is synchronous.
+ * GCMF_ERR_INVALID_ARG, naming the argument, nothing written: a null `plan`, `p`, `f` or `out`; n_steps < 1; npair < 0; `out`
+ * overlapping `f` or `g` as byte ranges (f and g may overlap each other: nothing writes them); a stacked plan's npair that is no
+ * multiple of its levels.  GCMF_ERR_UNSUPPORTED, naming the cause: vector plans (ncomp == 2), f32 plans and GCMF_OUT_F32 (tau is a small
+ * difference of large numbers: f32 intermediates are not offered), GCMF_PLAN_SELF_RING, row slabs; and whatever gcmf_apply refuses for
+ * these flags.  npair == 0: GCMF_OK.
+ */
+extern int gcmf_apply_cov(gcmf_plan *plan, const double *p, int n_steps, double c, const void *f, const void *g,
+                          void *out, int64_t npair, uint32_t flags, void *stream);
+
+/*
  * A FILTER BANK: nbank polynomials of ONE degree applied to the same nfield fields in one call -- a sweep over filter scales, whose
  * polynomials share n_steps, c and the grid (s_max does not depend on the filter scale) and differ in p alone:
  *     out[j * nfield + i] = the polynomial p[j * (n_steps + 1) .. (j + 1) * (n_steps + 1)) applied to in[i]      (j < nbank, i < nfield)
@@ -649,7 +688,9 @@ int gcmf_set_tuning(gcmf_plan *plan, int rows_per_wave, int xcd_remap, int multi
  * entry, and the FIELDS are cut into runs), "adjoint_scratch_mb" N (gcmf_apply_adjoint: the most scratch, in MiB, the pre-scaled planes
  * of one launch may take; default 4096; a longer batch is cut into consecutive launches of at least one entry; same bits),
  * "coarsen_scratch_mb" N (gcmf_apply_coarsen: the most scratch, in MiB, the fine planes of one run of entries may take; default 4096; a
- * longer batch is cut into consecutive runs of at least one entry; same bits).  Unknown
+ * longer batch is cut into consecutive runs of at least one entry; same bits), "cov_scratch_mb" N (gcmf_apply_cov: the most scratch, in
+ * MiB, one run of pairs may take -- 6 planes per pair, 4 for a variance; default 4096; a longer call is cut into consecutive runs of at
+ * least one pair; same bits).  Unknown
  * names: GCMF_ERR_INVALID_ARG. */
 int gcmf_set_option(gcmf_plan *plan, const char *name, int value);
 
